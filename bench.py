@@ -13,10 +13,14 @@ the reference -- on synthetic COCO-shaped batches already resident in HBM.
 Weak scaling: every rank owns its own 16+16 images; gradients are averaged with
 bucketed RCCL all-reduces overlapped with backward.
 
-One JSON line is printed by rank 0 with `roofline` (dominant kernel, fp32 MFMA
-bound, timed with hipEvents recorded inside the library around that kernel's
-launches during extra, untimed steps of the same workload) and `cpu_baseline`
-(the CPU oracle's step on a bounded sample, host cores of this box).
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the
+K steps and prints it; `--dump-outputs DIR` also writes the arrays the last
+timed step returned (dump_outputs).  Everything else is measured only with
+`--full`: `roofline` (dominant kernel, fp32 MFMA bound, timed with hipEvents
+recorded inside the library around that kernel's launches during extra, untimed
+steps of the same workload), `cpu_baseline` (the CPU oracle's step on a bounded
+sample, host cores of this box), decode latency, inference, the one-rank RCCL
+leg, the other configs and the DCN offset regimes.
 """
 import argparse
 import json
@@ -108,6 +112,63 @@ def fresh(batch):
     # target by its sigmoid on every call (losses/centernet.py:117) -- not a bench workload -- so the same resident
     # batch is reused
     return batch
+
+
+def rewind_point(plugin):
+    """--dump-outputs: remembers the parameters of every optimizer of `plugin` as they are before the first step; the
+    returned function puts them back and zeroes the Adam moments and step counts.  A step's forward pass is bit-
+    reproducible from run to run, its backward pass is not (atomic accumulation order), and Adam turns that last-bit
+    noise into differences of 1e-4 after two steps and 0.2 after five (measured on the headline step).  The timed step
+    whose outputs are dumped therefore starts from this state: its inputs, and so its outputs, are the same in every
+    run, and two builds compare output for output.  (Train-mode BatchNorm does not read its running statistics.)"""
+    import hip_runtime as hr
+    from hip_runtime.arena import arena_for
+    opts = [o for o in (plugin.optimizer, getattr(plugin, 'discriminator_optimizer', None)) if o is not None]
+    params = [p for o in opts for g in o.param_groups for p in g['params']]
+    saved = [p.detach().clone() for p in params]
+
+    def rewind():
+        with torch.no_grad():
+            for p, s in zip(params, saved):
+                p.copy_(s)
+            for o in opts:
+                for st in o.state.values():
+                    for t in st.values():
+                        t.zero_()                   # exp_avg, exp_avg_sq (views of the fused kernel's moments), step
+                o._step = 0                         # (the count the fused kernel's bias correction uses)
+                # parameters written behind the library's back: the packed weights follow, as after optimizer.step()
+                hr.bump_param_epoch(arena_for(o.param_groups[0]['params']).flat_param)
+    return rewind
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000      # array data: under 64 MB in all with the .npy headers, in either unit
+
+
+def dump_outputs(out, dirname, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of `out` (what plugin.step returned: both domains' head maps, the loss stats) as
+    DIR/<key path joined by '.'>.npy, float64 kept, everything else as float32.  Above `limit` bytes in all, each
+    array is cut to the same fraction of its elements (at least one), a fixed seeded sample (flattened, in index order)."""
+    arrays = {}
+
+    def walk(name, v):
+        if isinstance(v, dict):
+            for k in sorted(v):
+                walk('%s.%s' % (name, k) if name else str(k), v[k])
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk('%s.%d' % (name, i), x)
+        elif torch.is_tensor(v):
+            a = v.detach().cpu().numpy()
+            arrays[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    walk('', out)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        if total > limit:
+            k = max(1, a.size * limit // total)
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).permutation(a.size)[:k])]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+    return sorted(arrays)
 
 
 def _cpu_step_fn():
@@ -530,13 +591,20 @@ def main():
     ap.add_argument('--backend', default='dla34', choices=['dla34', 'resnet18'])
     ap.add_argument('--config', type=int, default=None, choices=sorted(CONFIGS),
                     help='BASELINE.json configs[N]: sets --backend/--uda/--size/--batch (2 = the default headline workload)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the arrays the last timed step returned as DIR/<name>.npy (dump_outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg beyond the headline: roofline profile steps, cpu_baseline, decode latency, '
+                         'inference, the one-rank RCCL leg, other configs, DCN offset regimes (the options below)')
     ap.add_argument('--cpu-baseline-budget', type=float, default=150.0,
                     help='seconds of host time the cpu_baseline leg may spend (the 512x512 sample is skipped beyond it)')
-    ap.add_argument('--profile-steps', type=int, default=1)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the decode-latency and inference legs (profiling runs)')
+    ap.add_argument('--profile-steps', type=int, default=1, help='with --full: untimed steps of the roofline leg')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the cpu_baseline leg')
+    ap.add_argument('--no-extras', action='store_true',
+                    help='with --full: skip the decode-latency, inference and other legs (profiling runs)')
     ap.add_argument('--matrix-mode-split', action='store_true',
-                    help='also time the step in matrix mode 1 (split bf16 operands; round-1 kernel set): `matrix_mode_split`')
+                    help='with --full: also time the step in matrix mode 1 (split bf16 operands; round-1 kernel set): '
+                         '`matrix_mode_split`')
     ap.add_argument('--dcn-offset-std', type=float, default=None,
                     help='profiling runs only: re-initialise every conv_offset_mask for sampling offsets of this standard '
                          'deviation in pixels before the warm-up (set_dcn_offset_std); the metric name then says so')
@@ -578,6 +646,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    rewind = rewind_point(plugin) if args.dump_outputs else None
     for _ in range(args.warmup):
         plugin.step(fresh(batch))
     # Python's cyclic collector: a full (generation-2) pass over the ~10^5 long-lived objects of the model, the tape
@@ -592,14 +661,25 @@ def main():
         dp.reset_exchange_stats(measure=True)
     barrier()
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    starts = marks[:-1]
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
+        if rewind is not None and i == args.steps - 1:
+            # the dumped step starts from the state before the warm-up (rewind_point); neither the clock nor this
+            # step's start event counts the rewind
+            torch.cuda.synchronize()
+            t_rewind = time.perf_counter()
+            rewind()
+            torch.cuda.synchronize()
+            starts[i] = torch.cuda.Event(enable_timing=True)
+            starts[i].record()
+            t0 += time.perf_counter() - t_rewind
         out = plugin.step(fresh(batch))
         marks[i + 1].record()                 # (an event record does not block: the timed region is unchanged)
     barrier()
     elapsed = time.perf_counter() - t0
-    per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+    per_step = [starts[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     collective = dp.exchange_stats() if dp is not None else None
     if dp is not None:
         dp.reset_exchange_stats(measure=False)
@@ -608,9 +688,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     stats = {k: float(v) for k, v in out['stats'].items()}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+    # a plain run stops here: the legs below run with --full only
+    extras = args.full and world == 1 and not args.no_extras
 
     roofline = None
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         # extra, untimed steps with the in-library kernel timer.  EVERY rank runs them (the gradient all-reduce
         # inside step() is collective); only rank 0 records and reports.
         import hip_runtime as hr
@@ -696,7 +780,7 @@ def main():
                                 for k, v in sorted(hbm_kernels.items(), key=lambda kv: -kv[1]['ms'])},
             })
     split_leg = None
-    if world == 1 and not args.no_extras and args.matrix_mode_split:
+    if extras and args.matrix_mode_split:
         # (opt-in since round 6, --matrix-mode-split: mode 1 keeps the round-1 kernel set -- no wave-specialised, halo-tile,
         # short-K or window kernels -- so beside the round-6 f32 set it is no longer an A/B of the matrix pipe alone)
         # the same step with the convolution GEMMs on the bf16 matrix pipe (exact three-way operand split, six
@@ -719,7 +803,7 @@ def main():
                          'note': 'cnuda_set_matrix_mode(1) for conv forward / input-gradient / DCN column-gradient '
                                  'GEMMs; weight-gradient and DCN forward GEMMs stay on the f32 MFMA'}
     dp1 = None
-    if world == 1 and not args.no_extras:
+    if extras:
         try:
             dp1 = dp1_rccl_leg(device, args)
         except Exception as e:                       # (a box without a usable RCCL: report, do not lose the line)
@@ -772,19 +856,19 @@ def main():
             'losses': {k: round(v, 5) for k, v in stats.items()},
             'roofline': roofline,
             'decode_latency': decode_latency(device, with_cpu=not args.no_cpu_baseline)
-            if world == 1 and not args.no_extras else None,
+            if extras else None,
             'inference': inference_throughput(device, getattr(plugin.backend, 'module', plugin.backend), args.size,
-                                              args.batch) if world == 1 and not args.no_extras else None,
+                                              args.batch) if extras else None,
             'matrix_mode_split': split_leg,
             'dp1_rccl': dp1,
             'other_configs': other_configs(device, args.config if args.config is not None else 2)
-            if world == 1 and not args.no_extras and args.config in (None, 2) and args.uda == 'entropy'
+            if extras and args.config in (None, 2) and args.uda == 'entropy'
             and args.size == 512 and args.batch == 16 else None,
             'dcn_offsets': dcn_offsets_leg(device)
-            if world == 1 and not args.no_extras and args.config in (None, 2) and args.uda == 'entropy'
+            if extras and args.config in (None, 2) and args.uda == 'entropy'
             and args.size == 512 and args.batch == 16 and args.backend == 'dla34' else None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(args.cpu_baseline_budget)
         else:
             line['cpu_baseline'] = None

@@ -2,6 +2,7 @@
 #   gpurun --timeout 2400 -- 'bash profiles/collect_all.sh r2'
 # -> gpurun_out/<tag>_bench_line.json, <tag>_bench_kernel_stats.csv, <tag>_pmc_traffic.json, <tag>_pmc_mfma.{json,md}, <tag>_decode_kernel_stats.csv, <tag>_pmc_dcn*,
 #    <tag>_bench_configs.jsonl   (copy them to profiles/ and run profiles/make_summary.py <tag>)
+#    The bench line (bench.py --full) is written straight to profiles/<tag>_bench_line.json.
 TAG=${1:-rX}
 R=$GRAFT_REPO_ROOT
 # the counter passes first, and their result into the box's own profiles/: bench.py's `roofline.traffic` reads the newest
@@ -10,8 +11,8 @@ bash $R/profiles/collect_pmc_traffic.sh > $R/gpurun_out/${TAG}_pmc_traffic.txt 2
 cp $R/gpurun_out/pmc_traffic.json $R/gpurun_out/${TAG}_pmc_traffic.json
 cp $R/gpurun_out/pmc_traffic.json $R/profiles/${TAG}_pmc_traffic.json
 head -12 $R/gpurun_out/${TAG}_pmc_traffic.txt
-python3 $R/bench.py > $R/gpurun_out/${TAG}_bench_line.json 2> $R/gpurun_out/${TAG}_bench_line.err
-tail -c 300 $R/gpurun_out/${TAG}_bench_line.json
+python3 $R/bench.py --full > $R/profiles/${TAG}_bench_line.json
+tail -c 300 $R/profiles/${TAG}_bench_line.json
 bash $R/profiles/collect_kernel_stats.sh > $R/gpurun_out/${TAG}_kernel_stats.txt 2>&1
 cp $(ls -t $R/gpurun_out/prof_tmp/*/*kernel_stats.csv | head -1) $R/gpurun_out/${TAG}_bench_kernel_stats.csv
 cp $R/gpurun_out/launches_per_step.json $R/gpurun_out/${TAG}_launches_per_step.json

@@ -97,7 +97,7 @@ if fam:
                  'without the BatchNorm-statistics tail, §13): together %.1f ms per step at %.1f TFLOP/s = %.3f of the peak.'
                  % (fam['ms_per_step'], fam['tflops'], fam['frac']))
 state.append('Per-step kernel time by bucket: ' + ', '.join('%s %.1f ms' % (k, v) for k, v in sorted(bk.items(), key=lambda kv: -kv[1])) + '.')
-state.append('Other BASELINE configs at full size on one GPU (`bench.py --config i`, `profiles/%s_bench_configs.jsonl`; the default '
+state.append('Other BASELINE configs at full size on one GPU (`bench.py --config i`, `profiles/%s_bench_configs.jsonl`; the --full '
              'run times them too, `other_configs`): ' % TAG +
              '; '.join('%s %.1f ms = %.1f img/s' % (c['config']['workload'].split(':')[0] + ' (' + c['config']['workload'].split('uda=')[1].split(',')[0] + ', %dx%d)' % tuple(c['config']['input'][1:]),
                                                     c['ms_per_step'], c['value']) for c in cfgs) + '.')

@@ -2,7 +2,7 @@
 """Writes profiles/<tag>_final_summary.md from the committed artefacts of a round's final measurement
 (`profiles/collect_all.sh <tag>`, copied from gpurun_out/ into profiles/):
 <tag>_bench_kernel_stats.csv (rocprofv3 --kernel-trace --stats of collect_kernel_stats.sh, 10 steps),
-<tag>_bench_line.json (python bench.py), <tag>_pmc_traffic.json, <tag>_pmc_mfma.md, <tag>_bench_configs.jsonl.
+<tag>_bench_line.json (python bench.py --full), <tag>_pmc_traffic.json, <tag>_pmc_mfma.md, <tag>_bench_configs.jsonl.
 
     python profiles/make_summary.py r2          # round 1's files carry the prefix r1_final_ / r1_"""
 import csv
