@@ -248,6 +248,59 @@ __global__ void softmax_loss_bwd_kernel(const float* __restrict__ x, const float
         }
     }
 }
+// eta-weighted entropy (losses/entropy.py:17-22, the FDA plugin's form): e = -sum_c f(v_c) / log2(C) per pixel,
+// loss = mean (e^2 + 1e-30)^eta
+__global__ __launch_bounds__(kT) void entropy_eta_fwd_kernel(const float* __restrict__ x, double* __restrict__ partial,
+                                                             int B, int C, long long HW, float eta) {
+    __shared__ double red[16];
+    const float inv = 1.0f / log2f((float)C);
+    double acc = 0.0;
+    const long long total = (long long)B * HW;
+    for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < total; i += (long long)gridDim.x * kT) {
+        const long long b = i / HW, hw = i - b * HW;
+        const float* px = x + (size_t)b * C * HW + hw;
+        float mx = px[0];
+        for (int c = 1; c < C; ++c) mx = fmaxf(mx, px[(size_t)c * HW]);
+        float den = 0.0f;
+        for (int c = 0; c < C; ++c) den += expf(px[(size_t)c * HW] - mx);
+        float s = 0.0f;
+        for (int c = 0; c < C; ++c) s += fent(expf(px[(size_t)c * HW] - mx) / den);
+        const float e = -s * inv;
+        acc += (double)powf(e * e + 1e-30f, eta);
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+// dx_j = up/(B HW) * 2 eta e (e^2 + 1e-30)^(eta-1) * (-1/log2 C) * v_j (f'_j - sum_i v_i f'_i)
+__global__ void entropy_eta_bwd_kernel(const float* __restrict__ x, const float* __restrict__ upstream, float scale,
+                                       float eta, float* __restrict__ grad, int B, int C, long long HW) {
+    const float up = upstream[0] * scale;
+    const float inv = 1.0f / log2f((float)C);
+    const long long total = (long long)B * HW;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const long long b = i / HW, hw = i - b * HW;
+        const float* px = x + (size_t)b * C * HW + hw;
+        float* pg = grad + (size_t)b * C * HW + hw;
+        float mx = px[0];
+        for (int c = 1; c < C; ++c) mx = fmaxf(mx, px[(size_t)c * HW]);
+        float den = 0.0f;
+        for (int c = 0; c < C; ++c) den += expf(px[(size_t)c * HW] - mx);
+        float s = 0.0f, dot = 0.0f;
+        for (int c = 0; c < C; ++c) {
+            const float v = expf(px[(size_t)c * HW] - mx) / den;
+            s += fent(v);
+            dot += v * dfent(v);
+        }
+        const float e = -s * inv;
+        const float ge = 2.0f * eta * e * powf(e * e + 1e-30f, eta - 1.0f);
+        const float k = -up * ge * inv;
+        for (int c = 0; c < C; ++c) {
+            const float v = expf(px[(size_t)c * HW] - mx) / den;
+            pg[(size_t)c * HW] = k * v * (dfent(v) - dot);
+        }
+    }
+}
 // entropy_map: out_c = -f(v_c) / log2(C)
 __global__ void entropy_map_fwd_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int C,
                                        long long HW) {
@@ -548,6 +601,28 @@ extern "C" int cnuda_softmax_loss_backward(const float* logits, const float* ups
                        (hipStream_t)stream, logits, upstream, (float)softmax_loss_scale(kind, B, C, HW), grad_logits, B,
                        C, HW, kind);
     return check_launch("cnuda_softmax_loss_backward");
+}
+extern "C" int cnuda_entropy_eta_loss_forward(const float* logits, float* out1, int B, int C, long long HW, float eta,
+                                              void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
+    CNUDA_REQUIRE(logits && out1 && B > 0 && C > 0 && HW > 0, "cnuda_entropy_eta_loss_forward: bad arguments");
+    CNUDA_REQUIRE(workspace && workspace_bytes >= cnuda_loss_workspace_bytes(),
+                  "cnuda_entropy_eta_loss_forward: workspace");
+    hipStream_t st = (hipStream_t)stream;
+    int blocks = stream_grid((long long)B * HW, kT);
+    if (blocks > kLossBlocks) blocks = kLossBlocks;
+    double* partial = ws_ptr(workspace);
+    CNUDA_LAUNCH(entropy_eta_fwd_kernel, dim3(blocks), dim3(kT), 0, st, logits, partial, B, C, HW, eta);
+    CNUDA_LAUNCH(scalar_finalize_kernel, dim3(1), dim3(kT), 0, st, partial, blocks, 1.0 / ((double)B * (double)HW),
+                 out1);
+    return check_launch("cnuda_entropy_eta_loss_forward");
+}
+extern "C" int cnuda_entropy_eta_loss_backward(const float* logits, const float* upstream, float* grad_logits, int B,
+                                               int C, long long HW, float eta, cnuda_stream_t stream) {
+    CNUDA_REQUIRE(logits && upstream && grad_logits && B > 0 && C > 0 && HW > 0,
+                  "cnuda_entropy_eta_loss_backward: bad arguments");
+    CNUDA_LAUNCH(entropy_eta_bwd_kernel, dim3(stream_grid((long long)B * HW, kT)), dim3(kT), 0, (hipStream_t)stream,
+                 logits, upstream, (float)(1.0 / ((double)B * (double)HW)), eta, grad_logits, B, C, HW);
+    return check_launch("cnuda_entropy_eta_loss_backward");
 }
 extern "C" int cnuda_entropy_map_forward(const float* logits, float* out, int B, int C, long long HW,
                                          cnuda_stream_t stream) {

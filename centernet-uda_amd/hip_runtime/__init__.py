@@ -129,11 +129,15 @@ class _Sig:
     cnuda_softmax_loss_backward = (_I, [_P] * 3 + [_I, _I, _LL, _I, _P])
     cnuda_entropy_map_forward = (_I, [_P, _P, _I, _I, _LL, _P])
     cnuda_entropy_map_backward = (_I, [_P] * 3 + [_I, _I, _LL, _P])
+    cnuda_entropy_eta_loss_forward = (_I, [_P, _P, _I, _I, _LL, _F] + _WS)
+    cnuda_entropy_eta_loss_backward = (_I, [_P] * 3 + [_I, _I, _LL, _F, _P])
     cnuda_bce_const_forward = (_I, [_P, _F, _P, _LL, _P])
     cnuda_bce_const_backward = (_I, [_P, _F, _P, _P, _LL, _P])
     cnuda_sigmoid_clamp_ = (_I, [_P, _P, _LL, _P])
     cnuda_gather_feat = (_I, [_P] * 3 + [_I, _I, _I, _LL, _P])
     cnuda_encode_targets = (_I, [_P] * 10 + [_I] * 5 + [_P])
+    cnuda_fda_workspace_bytes = (c_size_t, [_I] * 4)
+    cnuda_fda_source_to_target = (_I, [_P] * 4 + [_I] * 4 + _WS)
     cnuda_adam_step = (_I, [_P] * 4 + [_LL] + [_F] * 5 + [_I, _P])
     cnuda_set_matrix_mode = (_I, [_I])
     cnuda_get_matrix_mode = (_I, [])

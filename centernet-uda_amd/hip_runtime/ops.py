@@ -1027,6 +1027,38 @@ def max_square_loss(hm_logits):
     return _SoftmaxLoss.apply(hm_logits, 1)
 
 
+class _EntropyEtaLoss(Function):
+    @staticmethod
+    def forward(ctx, logits, eta):
+        require_gpu(logits)
+        logits = f32c(logits)
+        B, C = logits.shape[0], logits.shape[1]
+        HW = logits.numel() // (B * C)
+        out = torch.empty(1, dtype=torch.float32, device=logits.device)
+        wp, wn = _loss_ws(logits)
+        check(lib().cnuda_entropy_eta_loss_forward(ptr(logits), ptr(out), B, C, HW, float(eta), wp, wn, stream()),
+              'entropy_eta_loss_forward')
+        ctx.args = (B, C, HW, float(eta))
+        ctx.save_for_backward(logits)
+        return out[0].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gloss):
+        (logits,) = ctx.saved_tensors
+        grad = torch.empty_like(logits)
+        up = f32c(gloss.reshape(1))
+        check(lib().cnuda_entropy_eta_loss_backward(ptr(logits), ptr(up), ptr(grad), *ctx.args, stream()),
+              'entropy_eta_loss_backward')
+        return grad, None
+
+
+def entropy_eta_loss(hm_logits, eta):
+    """EntropyLoss(eta) (losses/entropy.py:17-22): mean over pixels of (e^2 + 1e-30)^eta, e the normalised softmax
+    entropy over the channels."""
+    return _EntropyEtaLoss.apply(hm_logits, eta)
+
+
 class _EntropyMap(Function):
     @staticmethod
     def forward(ctx, logits):
@@ -1117,3 +1149,29 @@ def adam_step_(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_d
     check(lib().cnuda_adam_step(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr),
                                 float(beta1), float(beta2), float(eps), float(weight_decay), int(step), stream()),
           'adam_step')
+
+
+# ---------------------------------------------------------------------------
+# Fourier domain adaptation (csrc/fda.hip)
+# ---------------------------------------------------------------------------
+def fda_source_to_target(src, trg, use_target_amp):
+    """The amplitude transfer of FDA_source_to_target (utils/image.py:137-230) for a whole batch: src, trg [B,C,H,W]
+    fp32 on the GPU, use_target_amp a uint8 [H, W//2+1] device tensor (non-zero: the bin takes the target's
+    amplitude).  Returns a new [B,C,H,W] tensor.  Not differentiable: an input that requires grad is an error."""
+    require_gpu(src, trg, use_target_amp)
+    if src.requires_grad or trg.requires_grad:
+        raise RuntimeError("fda_source_to_target is not differentiable (the reference never back-propagates "
+                           "through it): pass detached inputs")
+    if src.dim() != 4 or src.shape != trg.shape:
+        raise RuntimeError("fda_source_to_target: src and trg must be [B,C,H,W] of one shape, got %s and %s"
+                           % (tuple(src.shape), tuple(trg.shape)))
+    B, C, H, W = src.shape
+    if use_target_amp.dtype != torch.uint8 or tuple(use_target_amp.shape) != (H, W // 2 + 1):
+        raise RuntimeError("fda_source_to_target: use_target_amp must be uint8 [%d, %d], got %s %s"
+                           % (H, W // 2 + 1, use_target_amp.dtype, tuple(use_target_amp.shape)))
+    src, trg, m = f32c(src), f32c(trg), use_target_amp.contiguous()
+    out = torch.empty_like(src)
+    wp, wn = _ws(lib().cnuda_fda_workspace_bytes(B, C, H, W), src)
+    check(lib().cnuda_fda_source_to_target(ptr(src), ptr(trg), ptr(m), ptr(out), B, C, H, W, wp, wn, stream()),
+          'fda_source_to_target')
+    return out

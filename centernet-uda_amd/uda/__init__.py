@@ -1,6 +1,7 @@
 """UDA step plugins.  The driver resolves them by class name from the config (`uda.<ClassName>`, train.py:104-106);
-the classes are imported on first use.  FDA (uda/fda.py) is not part of this build: it needs `torch.rfft`, which
-current PyTorch no longer has."""
+the classes are imported on first use.  FDA lives at uda.fda.FDA (its module path in the reference too) and is not
+registered here yet: the reference's transform is spelled with `torch.rfft`, which current PyTorch no longer has, and
+this build replaces it with a HIP transform (utils/image.FDA_source_to_target)."""
 import importlib
 
 _PLUGINS = {
@@ -18,7 +19,8 @@ def __getattr__(name):
         globals()[name] = cls
         return cls
     if name == 'FDA':
-        raise AttributeError("uda.FDA is outside this build (uda/fda.py uses torch.rfft, removed from PyTorch)")
+        raise AttributeError("uda.FDA is not registered in this build (the reference's uda/fda.py uses torch.rfft, "
+                             "removed from PyTorch): use uda.fda.FDA, which runs on a HIP transform")
     raise AttributeError("module 'uda' has no attribute %r" % name)
 
 

@@ -533,6 +533,12 @@ int cnuda_softmax_loss_backward(const float* logits, const float* upstream, floa
 int cnuda_entropy_map_forward(const float* logits, float* out, int B, int C, long long HW, cnuda_stream_t stream);
 int cnuda_entropy_map_backward(const float* logits, const float* grad_out, float* grad_logits,
                                int B, int C, long long HW, cnuda_stream_t stream);
+/* eta-weighted EntropyLoss (losses/entropy.py:17-22, used by the FDA plugin): e = -sum_c v log2(v + 1e-30) / log2(C)
+ * per pixel of softmax(logits) over C, out1 = mean over B x HW of (e^2 + 1e-30)^eta.  Same workspace as the other losses. */
+int cnuda_entropy_eta_loss_forward(const float* logits, float* out1, int B, int C, long long HW, float eta,
+                                   void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+int cnuda_entropy_eta_loss_backward(const float* logits, const float* upstream, float* grad_logits,
+                                    int B, int C, long long HW, float eta, cnuda_stream_t stream);
 int cnuda_bce_const_forward(const float* logits, float label, float* out1, long long n, cnuda_stream_t stream);
 int cnuda_bce_const_backward(const float* logits, float label, const float* upstream, float* grad_logits,
                              long long n, cnuda_stream_t stream);
@@ -541,6 +547,19 @@ int cnuda_sigmoid_clamp_(float* x, float* y, long long n, cnuda_stream_t stream)
 /* feat [B,ch,HW], ind [B,M] -> out [B,M,ch]  (utils/tensor.py:10-25) */
 int cnuda_gather_feat(const float* feat, const int64_t* ind, float* out, int B, int M, int ch, long long HW,
                       cnuda_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Fourier domain adaptation (utils/image.py:137-230, FDA_source_to_target): out = irfft2 of the source's half
+ * spectrum (columns 0 .. W/2) whose amplitude is replaced by the target's where use_target_amp[ky][kx] != 0
+ * (a bin with |S| = 0 becomes (|T|, 0)); the DC and Nyquist columns contribute their real part only.
+ *   src, trg, out [B,C,H,W] f32;  use_target_amp [H][W/2+1] u8, shared by every image and channel.
+ * H, W <= 4096.  Workspace: cnuda_fda_workspace_bytes (the two half spectra, 2*B*C*H*(W/2+1) complex fp32).
+ * Deterministic (no atomics).  Not differentiable (the reference never back-propagates through it).
+ * ---------------------------------------------------------------------- */
+size_t cnuda_fda_workspace_bytes(int B, int C, int H, int W);
+int cnuda_fda_source_to_target(const float* src, const float* trg, const uint8_t* use_target_amp, float* out,
+                               int B, int C, int H, int W, void* workspace, size_t workspace_bytes,
+                               cnuda_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Optimizer -- torch.optim.Adam arithmetic (train.py:88-90) over a flat arena.
