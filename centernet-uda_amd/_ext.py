@@ -3,7 +3,9 @@
 libs/DCNv2/dcn_v2.py:13).  Same two function names, same positional argument
 order (input, weight, bias, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, dg),
 same return values; the work is done by libcenternet_uda_hip.so on the current
-HIP stream.  Deformable PSROI pooling is not provided (no backend calls it).
+HIP stream.  The module's other two functions, deformable PSROI pooling forward
+and backward (vision.cpp:6-7), are at the end of this file, with the reference's
+positional order (libs/DCNv2/src/dcn_v2.h:95-190) as well.
 """
 import torch
 
@@ -166,3 +168,79 @@ def dcn_v2_backward_om(input, weight, bias, om, grad_output, kernel_h, kernel_w,
                                         hr.ptr(grads[1]), hr.ptr(grads[2]), hr.ptr(grads[3]), *geom, hr.ptr(ws), ws.numel(),
                                         hr.stream()), 'dcn_v2_backward_om')
     return grads
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Deformable position-sensitive ROI pooling (libs/DCNv2/src/dcn_v2.h:95-190; csrc/psroi.hip).  fp32 only.
+# ---------------------------------------------------------------------------------------------------------------------
+def _psroi_geom(input, rois, offset, no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size,
+                sample_per_part, trans_std):
+    if input.dim() != 4:
+        raise RuntimeError("dcn_v2_psroi_pooling: input must be 4-D")
+    if rois.dim() != 2 or rois.shape[1] != 5:
+        raise RuntimeError("dcn_v2_psroi_pooling: rois must be [N, 5] (batch index, x1, y1, x2, y2), got %s"
+                           % (tuple(rois.shape),))
+    B, C, H, W = input.shape
+    N = rois.shape[0]
+    if C != output_dim * group_size * group_size:
+        raise RuntimeError("dcn_v2_psroi_pooling: input has %d channels, output_dim * group_size^2 = %d"
+                           % (C, output_dim * group_size * group_size))
+    if no_trans:
+        num_classes = 1
+    else:
+        if offset.dim() != 4 or offset.shape[0] != N or offset.shape[1] % 2 or offset.shape[1] == 0 or \
+                tuple(offset.shape[2:]) != (part_size, part_size):
+            raise RuntimeError("dcn_v2_psroi_pooling: offset %s does not match [%d, 2 * num_classes, %d, %d]"
+                               % (tuple(offset.shape), N, part_size, part_size))
+        num_classes = offset.shape[1] // 2
+        if output_dim % num_classes:
+            raise RuntimeError("dcn_v2_psroi_pooling: output_dim %d is not a multiple of the offset's %d classes"
+                               % (output_dim, num_classes))
+    return (B, C, H, W, N, 1 if no_trans else 0, float(spatial_scale), int(output_dim), int(group_size),
+            int(pooled_size), int(part_size), int(sample_per_part), float(trans_std), num_classes)
+
+
+def dcn_v2_psroi_pooling_forward(input, rois, offset, no_trans, spatial_scale, output_dim, group_size, pooled_size,
+                                 part_size, sample_per_part, trans_std):
+    """-> (output, output_count), both [N, output_dim, pooled_size, pooled_size]; `offset` is an empty tensor with no_trans."""
+    hr.require_gpu(input, rois, offset)
+    input, rois = hr.f32c(input), hr.f32c(rois)
+    geom = _psroi_geom(input, rois, offset, no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size,
+                       sample_per_part, trans_std)
+    offset = None if no_trans else hr.f32c(offset)
+    shape = (rois.shape[0], output_dim, pooled_size, pooled_size)
+    out = torch.empty(shape, dtype=torch.float32, device=input.device)
+    count = torch.empty(shape, dtype=torch.float32, device=input.device)
+    hr.check(hr.lib().cnuda_dcn_v2_psroi_pooling_forward(hr.ptr(input), hr.ptr(rois), hr.ptr(offset), hr.ptr(out),
+                                                         hr.ptr(count), *geom, hr.stream()),
+             'dcn_v2_psroi_pooling_forward')
+    return out, count
+
+
+def dcn_v2_psroi_pooling_backward(grad_output, input, rois, offset, output_count, no_trans, spatial_scale, output_dim,
+                                  group_size, pooled_size, part_size, sample_per_part, trans_std, _grad_input=None):
+    """-> (grad_input, grad_offset).  _grad_input (not part of the reference's signature): a buffer that already holds
+    another consumer's share of the input's gradient; this call adds to it (as dcn_v2_backward does)."""
+    hr.require_gpu(grad_output, input, rois, offset, output_count)
+    grad_output, input, rois, output_count = [hr.f32c(t) for t in (grad_output, input, rois, output_count)]
+    geom = _psroi_geom(input, rois, offset, no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size,
+                       sample_per_part, trans_std)
+    shape = (rois.shape[0], output_dim, pooled_size, pooled_size)
+    if tuple(grad_output.shape) != shape or tuple(output_count.shape) != shape:
+        raise RuntimeError("dcn_v2_psroi_pooling_backward: grad_output %s / output_count %s do not match %s"
+                           % (tuple(grad_output.shape), tuple(output_count.shape), shape))
+    offset = None if no_trans else hr.f32c(offset)
+    if _grad_input is not None and (_grad_input.shape != input.shape or _grad_input.dtype != torch.float32 or
+                                    not _grad_input.is_contiguous() or not _grad_input.is_cuda):
+        raise RuntimeError("dcn_v2_psroi_pooling_backward: _grad_input must be a contiguous fp32 GPU tensor like input")
+    grad_input = _grad_input if _grad_input is not None else torch.empty_like(input)
+    grad_offset = torch.empty(0, dtype=torch.float32, device=input.device) if no_trans else torch.empty_like(offset)
+    L = hr.lib()
+    ws = hr.workspace(L.cnuda_dcn_v2_psroi_pooling_workspace_bytes(geom[0], geom[4], geom[7], geom[9]), input.device)
+    hr.check(L.cnuda_dcn_v2_psroi_pooling_backward(hr.ptr(grad_output), hr.ptr(input), hr.ptr(rois), hr.ptr(offset),
+                                                   hr.ptr(output_count), hr.ptr(grad_input),
+                                                   1 if _grad_input is not None else 0,
+                                                   None if no_trans else hr.ptr(grad_offset), *geom, hr.ptr(ws),
+                                                   ws.numel(), hr.stream()),
+             'dcn_v2_psroi_pooling_backward')
+    return grad_input, grad_offset

@@ -75,6 +75,9 @@ class _Sig:
     cnuda_dcn_v2_backward_om = (_I, [_P] * 7 + [_I] + [_P] * 3 + [_I] * 14 + _WS)
     cnuda_dcn_v2_backward_cols = (_I, [_P] * 12 + [_I] * 14 + _WS)
     cnuda_dcn_v2_backward_acc = (_I, [_P] * 8 + [_I] + [_P] * 4 + [_I] * 14 + _WS)
+    cnuda_dcn_v2_psroi_pooling_workspace_bytes = (c_size_t, [_I] * 4)
+    cnuda_dcn_v2_psroi_pooling_forward = (_I, [_P] * 5 + [_I] * 6 + [_F] + [_I] * 5 + [_F, _I, _P])
+    cnuda_dcn_v2_psroi_pooling_backward = (_I, [_P] * 6 + [_I, _P] + [_I] * 6 + [_F] + [_I] * 5 + [_F, _I] + _WS)
     cnuda_conv2d_workspace_bytes = (c_size_t, [_I] * 11)
     cnuda_conv2d_forward = (_I, [_P] * 4 + [_I] * 11 + [_F] + _WS)
     cnuda_conv2d_forward_res = (_I, [_P] * 5 + [_I] * 11 + [_F] + _WS)

@@ -1,4 +1,6 @@
 """Python face of the deformable convolution: `dcn_v2_conv`, `DCNv2`, `DCN`
+-- and, at the end of the file, of the deformable PSROI pooling: `dcn_v2_pooling`,
+`DCNv2Pooling`, `DCNPooling` (libs/DCNv2/dcn_v2.py:132-303) --
 with the constructor/forward signatures, parameter names (`weight`, `bias`,
 `conv_offset_mask.{weight,bias}` -- checkpoint keys) and initialisation of the
 reference (libs/DCNv2/dcn_v2.py:18-128), running on the MI355X kernels behind
@@ -244,3 +246,89 @@ class DCN(DCNv2):
         n2, n3 = counts.tolist()
         total = float(B * taps * HW)
         return (1 if n2 > self.CENSUS_SHARES[0] * total else 0) | (2 if n3 > self.CENSUS_SHARES[1] * total else 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Deformable position-sensitive ROI pooling (libs/DCNv2/dcn_v2.py:132-303) on csrc/psroi.hip
+# ---------------------------------------------------------------------------------------------------------------------
+class _DCNv2Pooling(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, input, rois, offset, spatial_scale, pooled_size, output_dim, no_trans, group_size=1,
+                part_size=None, sample_per_part=4, trans_std=.0):
+        ctx.args = (int(no_trans), spatial_scale, output_dim, group_size, pooled_size,
+                    pooled_size if part_size is None else part_size, sample_per_part, trans_std)
+        output, output_count = _backend.dcn_v2_psroi_pooling_forward(input, rois, offset, *ctx.args)
+        ctx.save_for_backward(input, rois, offset, output_count)
+        return output
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        input, rois, offset, output_count = ctx.saved_tensors
+        grad_input, grad_offset = _backend.dcn_v2_psroi_pooling_backward(grad_output, input, rois, offset, output_count,
+                                                                         *ctx.args)
+        return grad_input, None, grad_offset, None, None, None, None, None, None, None, None
+
+
+def dcn_v2_pooling(input, rois, offset, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None,
+                   sample_per_part=4, trans_std=.0):
+    return _DCNv2Pooling.apply(input, rois, offset, spatial_scale, pooled_size, output_dim, no_trans, group_size,
+                               part_size, sample_per_part, trans_std)
+
+
+class DCNv2Pooling(nn.Module):
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None,
+                 sample_per_part=4, trans_std=.0):
+        super().__init__()
+        self.spatial_scale = spatial_scale
+        self.pooled_size = pooled_size
+        self.output_dim = output_dim
+        self.no_trans = no_trans
+        self.group_size = group_size
+        self.part_size = pooled_size if part_size is None else part_size
+        self.sample_per_part = sample_per_part
+        self.trans_std = trans_std
+
+    def forward(self, input, rois, offset):
+        # the reference's assertion (dcn_v2.py:209): through this layer only group_size 1 is reachable; the R-FCN layout
+        # (channels = output_dim * group_size^2) goes through _ext directly
+        assert input.shape[1] == self.output_dim
+        if self.no_trans:
+            offset = input.new()
+        return dcn_v2_pooling(input, rois, offset, self.spatial_scale, self.pooled_size, self.output_dim, self.no_trans,
+                              self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+
+
+class DCNPooling(DCNv2Pooling):
+    """DCNv2Pooling that predicts its own offsets and modulation mask: plain pooling, three fully connected layers, then
+    the deformable pooling times the sigmoid mask.  The two poolings run on this library's kernels; `offset_mask_fc`
+    (nn.Linear + ReLU, [N, pooled_size^2 * output_dim] x deform_fc_dim matmuls) runs on torch as in the reference -- it is
+    not part of the layer path this package replaces.  State-dict names as there: offset_mask_fc.{0,2,4}.{weight,bias}."""
+
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None,
+                 sample_per_part=4, trans_std=.0, deform_fc_dim=1024):
+        super().__init__(spatial_scale, pooled_size, output_dim, no_trans, group_size, part_size, sample_per_part,
+                         trans_std)
+        self.deform_fc_dim = deform_fc_dim
+        if not no_trans:
+            self.offset_mask_fc = nn.Sequential(
+                nn.Linear(self.pooled_size * self.pooled_size * self.output_dim, self.deform_fc_dim),
+                nn.ReLU(inplace=True),
+                nn.Linear(self.deform_fc_dim, self.deform_fc_dim),
+                nn.ReLU(inplace=True),
+                nn.Linear(self.deform_fc_dim, self.pooled_size * self.pooled_size * 3))
+            with torch.no_grad():        # zero init: offsets 0, mask sigmoid(0) = 0.5 (dcn_v2.py:256-257)
+                self.offset_mask_fc[4].weight.zero_()
+                self.offset_mask_fc[4].bias.zero_()
+
+    def forward(self, input, rois):
+        geom = (self.spatial_scale, self.pooled_size, self.output_dim)
+        tail = (self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+        if self.no_trans:
+            return dcn_v2_pooling(input, rois, input.new(), *geom, True, *tail)
+        n = rois.shape[0]
+        roi = dcn_v2_pooling(input, rois, input.new(), *geom, True, *tail)
+        offset_mask = self.offset_mask_fc(roi.view(n, -1)).view(n, 3, self.pooled_size, self.pooled_size)
+        o1, o2, mask = torch.chunk(offset_mask, 3, dim=1)
+        offset = torch.cat((o1, o2), dim=1)
+        return dcn_v2_pooling(input, rois, offset, *geom, False, *tail) * torch.sigmoid(mask)

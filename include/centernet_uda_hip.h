@@ -283,6 +283,34 @@ int cnuda_dcn_v2_backward_acc(const float* input, const float* weight, const flo
                               void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Deformable position-sensitive ROI pooling -- the other two functions of the native module
+ * (libs/DCNv2/src/vision.cpp:6-7, cuda/dcn_v2_psroi_pooling_cuda.cu, float instantiation).
+ *   input [B, channels, H, W], channels == output_dim * group_size^2;  rois [num_rois, 5] = (batch index, x1, y1, x2,
+ *   y2), corners rounded half away from zero;  trans [num_rois, 2 * num_classes, part_size, part_size] (NULL and
+ *   num_classes = 1 with no_trans != 0);  output, output_count [num_rois, output_dim, pooled_size, pooled_size], the
+ *   count being the number of samples that fell inside the map (output 0 where it is 0).
+ * pooled_size <= 64; output_dim % num_classes == 0.  The batch indices are read back to the host first (one stream
+ * synchronisation per call): a ROI that names no image is CNUDA_ERR_INVALID_ARGUMENT, nothing is launched.
+ * backward: grad_input [B, channels, H, W] is written (accumulate_input == 0) or added to (!= 0); grad_trans like
+ * trans (untouched with no_trans).  Workspace (backward only): cnuda_dcn_v2_psroi_pooling_workspace_bytes.
+ * No atomics: forward and backward are bit-stable from run to run (the reference's backward is not).
+ * ---------------------------------------------------------------------- */
+size_t cnuda_dcn_v2_psroi_pooling_workspace_bytes(int B, int num_rois, int output_dim, int pooled_size);
+int cnuda_dcn_v2_psroi_pooling_forward(const float* input, const float* rois, const float* trans,
+                                       float* output, float* output_count,
+                                       int B, int channels, int H, int W, int num_rois, int no_trans,
+                                       float spatial_scale, int output_dim, int group_size, int pooled_size,
+                                       int part_size, int sample_per_part, float trans_std, int num_classes,
+                                       cnuda_stream_t stream);
+int cnuda_dcn_v2_psroi_pooling_backward(const float* grad_output, const float* input, const float* rois,
+                                        const float* trans, const float* output_count,
+                                        float* grad_input, int accumulate_input, float* grad_trans,
+                                        int B, int channels, int H, int W, int num_rois, int no_trans,
+                                        float spatial_scale, int output_dim, int group_size, int pooled_size,
+                                        int part_size, int sample_per_part, float trans_std, int num_classes,
+                                        void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Dense convolution (groups 1, dilation 1) -- replaces torch.nn.Conv2d -> cuDNN
  * on the hot path: backends/dla.py:37-44,153-155,234-235,281-283,478-483 (DLA
  * trunk, roots, heads), libs/DCNv2/dcn_v2.py:104-110 (offset/mask conv),
