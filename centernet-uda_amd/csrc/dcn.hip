@@ -1842,6 +1842,9 @@ static int dcn_forward_impl(const float* input, const float* weight, const float
         CNUDA_REQUIRE(workspace && cv.cur <= cv.end, "cnuda_dcn_v2_forward: workspace too small");
         if (hipMemsetAsync(zero, 0, (size_t)Cout * sizeof(float), st) != hipSuccess) return check_launch("cnuda_dcn_v2_forward(dg>1)");
         const DcnStrides gs{dg * 2 * T * HoWo, dg * T * HoWo, 0, 0, 0};
+        // every group's weights pass through `wg`: under the caller's pack stamp the inner calls would all ask the pack cache
+        // for the same image of the same source, and groups 1.. would multiply with group 0's weights -- they do not cache
+        const PackStampSuspend uncached;
         for (int grp = 0; grp < dg; ++grp) {
             if (int rc = cnuda_copy_channels(input, xg, B, Cg, HW, C, grp * Cg, Cg, 0, stream)) return rc;
             if (int rc = cnuda_copy_channels(weight, wg, Cout, Cg, T, C, grp * Cg, Cg, 0, stream)) return rc;
@@ -2083,6 +2086,7 @@ static int dcn_backward_impl(const float* input, const float* weight, const floa
         void* iws = cv.take<char>(inner);
         CNUDA_REQUIRE(workspace && cv.cur <= cv.end, "cnuda_dcn_v2_backward: workspace too small");
         const DcnStrides gs{dg * 2 * T * HoWo, dg * T * HoWo, dg * 2 * T * HoWo, dg * T * HoWo, 0};
+        const PackStampSuspend uncached;       // (`wg` and the inner calls' transposed weights: one buffer for every group)
         for (int grp = 0; grp < dg; ++grp) {
             if (int rc = cnuda_copy_channels(input, xg, B, Cg, HW, C, grp * Cg, Cg, 0, stream)) return rc;
             if (int rc = cnuda_copy_channels(weight, wg, Cout, Cg, T, C, grp * Cg, Cg, 0, stream)) return rc;

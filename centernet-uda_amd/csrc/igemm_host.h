@@ -43,6 +43,18 @@ const float* launch_pack(const float* W, float* dst, size_t room, int Co, int C,
 const float* launch_pack_taps(const float* W, float* dst, size_t room, int Co, int C, int T, const int* taps, int ntaps,
                               int Kp, int Mp, hipStream_t st);
 
+// Sets the calling thread's pack stamp aside for its lifetime: every launch_pack / launch_pack_taps in its scope packs into
+// the caller's workspace, as an unstamped call does.  For an entry point that runs inner calls on operands it builds in ONE
+// workspace buffer per call (the per-group weights of the composed deformable_group > 1 path): under the caller's stamp
+// all of them would share one cache key, and the first one's image would be taken for the others'.
+struct PackStampSuspend {
+    unsigned long long token, version;
+    PackStampSuspend();
+    ~PackStampSuspend();
+    PackStampSuspend(const PackStampSuspend&) = delete;
+    PackStampSuspend& operator=(const PackStampSuspend&) = delete;
+};
+
 // gw[o][c][tap] = sum_z slabs[z][o][tap*C + c]; with bslab ([Z][Mp]: the GEMM's per-split row sums of grad_y, written by
 // igemm_wgrad_*_kernel when it is given the pointer) also gb[o] = sum_z bslab[z][o] -- the bias gradient, same launch
 void launch_slab_reduce(const float* slabs, float* gw, int Z, int Mp, int Jp,

@@ -243,6 +243,9 @@ float* pack_slot(const PackKey& key, size_t bytes, bool& fill, int cpad = 0, con
 
 }  // namespace
 
+PackStampSuspend::PackStampSuspend() : token(g_pack_token), version(g_pack_version) { g_pack_token = 0; g_pack_version = 0; }
+PackStampSuspend::~PackStampSuspend() { g_pack_token = token; g_pack_version = version; }
+
 const float* launch_pack(const float* W, float* dst, size_t room, int Co, int C, int T, PackMode mode, int Kp, int Mp,
                          int Cpad, hipStream_t st) {
     bool fill = true;

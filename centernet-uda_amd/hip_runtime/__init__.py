@@ -9,6 +9,7 @@ HIP stream only.
 import ctypes
 import os
 import threading
+import weakref
 
 import torch
 
@@ -251,13 +252,42 @@ class PackToken:
         return 'PackToken(%d)' % self.id
 
 
+# torch's version counter belongs to one tensor OBJECT: a module whose weight is replaced by a fresh tensor
+# (`m.weight = nn.Parameter(t)`) may get one with the counter of the tensor it replaces, and -- once that one is freed -- at
+# its address too.  Token, source pointer and version would all be equal and the old packed image would be taken for the
+# new weights'.  So every tensor object that is stamped takes a serial number on first use, for as long as it lives, and
+# the serial is folded into the version (odd multiplier: serials that differ by less than 2^16 only collide for counters
+# that differ by more than 2^15).  A caller's explicit version (the folded inference weights' `_fold_gen`) is taken as it is.
+_WEIGHT_SERIALS = {}      # id(tensor object) -> (weak reference to it, serial)
+
+
+def _weight_serial(w):
+    k = id(w)
+    e = _WEIGHT_SERIALS.get(k)
+    if e is not None and e[0]() is w:
+        return e[1]
+
+    def forget(ref, k=k):
+        cur = _WEIGHT_SERIALS.get(k)
+        if cur is not None and cur[0] is ref:
+            del _WEIGHT_SERIALS[k]
+    _PACK['next_serial'] = s = _PACK.get('next_serial', 0) + 1
+    _WEIGHT_SERIALS[k] = (weakref.ref(w, forget), s)
+    return s
+
+
 class pack_stamp:
     """with pack_stamp(token, weight[, version]): <one C-ABI call that packs `weight`>"""
     __slots__ = ('token', 'version', 'device')
 
     def __init__(self, token, weight, version=None):
         self.token = 0 if _PACK['off'] else int(token)
-        v = weight._version if version is None else int(version)
+        if version is not None:
+            v = int(version)
+        elif self.token:
+            v = weight._version + _weight_serial(weight) * 0x9E3779B1
+        else:
+            v = 0
         self.version = ((_PARAM_EPOCH & 0xffffffff) << 32) | (v & 0xffffffff)
         self.device = weight.device
 

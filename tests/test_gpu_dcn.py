@@ -386,21 +386,33 @@ def test_a_forward_hook_on_the_offset_convolution_still_fires():
     assert torch.equal(got, want) and torch.equal(again, want)
 
 
+@pytest.mark.parametrize('stamped', [False, True], ids=['token0', 'pack_token'])
 @pytest.mark.parametrize('name', ['dg2', 'dg2_64ch', 'dg4_odd'])
-def test_deformable_groups_through_the_autograd_path_with_saved_columns(name):
+def test_deformable_groups_through_the_autograd_path_with_saved_columns(name, stamped):
     """deformable_group > 1 (round 6: composed of deformable_group = 1 calls per group) through the product's autograd
-    Function, which keeps the sampled columns of every group between forward and backward: values against the C oracle."""
+    Function, which keeps the sampled columns of every group between forward and backward: values against the C oracle.
+    Without a pack token, and with one as the `DCNv2` / `DCN` modules pass it (the groups' weights all go through one
+    workspace buffer: under a token they must not be taken for one another's, tests/test_gpu_pack_cache.py); each twice,
+    with an in-place update of the weights in between."""
+    import hip_runtime as hr
     from libs.DCNv2.dcn_v2 import dcn_v2_conv
     (x, w, b, off, m, go), geom = _case(zlib.crc32(name.encode()) % 1000, **CASES[name])
-    want = od.dcn_v2_forward(x, w, b, off, m, *geom)
-    wg = od.dcn_v2_backward(x, w, b, off, m, go, *geom)           # input, offset, mask, weight, bias
+    token = hr.PackToken() if stamped else 0
     leaves = [t.to(DEV).requires_grad_(True) for t in (x, off, m, w, b)]
     kh, kw, sh, sw, ph, pw, dh, dw, dg = geom
-    y = dcn_v2_conv(*leaves, (sh, sw), (ph, pw), (dh, dw), dg)
-    assert y.grad_fn.saved_tensors[5] is not None                 # the columns were kept
-    _close(y, want)
-    y.backward(go.to(DEV))
-    for got, ref, nm in zip([leaves[0].grad, leaves[1].grad, leaves[2].grad, leaves[3].grad, leaves[4].grad], wg,
-                            ['input', 'offset', 'mask', 'weight', 'bias']):
-        assert got.shape == ref.shape, nm
-        _close(got, ref)
+    for call in range(2):
+        want = od.dcn_v2_forward(x, w, b, off, m, *geom)
+        wg = od.dcn_v2_backward(x, w, b, off, m, go, *geom)           # input, offset, mask, weight, bias
+        for t in leaves:
+            t.grad = None
+        y = dcn_v2_conv(*leaves, (sh, sw), (ph, pw), (dh, dw), dg, token)
+        assert y.grad_fn.saved_tensors[5] is not None                 # the columns were kept
+        _close(y, want)
+        y.backward(go.to(DEV))
+        for got, ref, nm in zip([leaves[0].grad, leaves[1].grad, leaves[2].grad, leaves[3].grad, leaves[4].grad], wg,
+                                ['input', 'offset', 'mask', 'weight', 'bias']):
+            assert got.shape == ref.shape, nm
+            _close(got, ref)
+        w = w * -0.5
+        with torch.no_grad():
+            leaves[3].mul_(-0.5)
