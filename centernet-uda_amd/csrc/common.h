@@ -81,6 +81,9 @@ int matrix_mode();
 // Wave-specialised (producer / consumer, 8-wave) variants of the f32 implicit-GEMM kernels for the 64- and 128-row
 // tiles: on unless CNUDA_WS=0 (read once).  +3-8 % per launch where it applies, ~1.2 % of the benched step.
 bool wave_specialised();
+// Buffer-addressed (32-bit offset, hardware bounds check) loaders of the implicit GEMMs: on unless CNUDA_BUF=0 (read once;
+// A/B measurements).  Tensors of 2 GiB and more always take the pointer-addressed loaders.
+bool buffer_addressing();
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 

@@ -860,12 +860,6 @@ int fill_geom(ConvGeom& g, int B, int C, int H, int W, int Co, int kh, int kw, i
     return 0;
 }
 
-// CNUDA_BUF=0: the pointer-addressed loaders (A/B measurements; tensors of 2 GiB and more always take them)
-bool buffer_addressing() {
-    static const bool on = !(getenv("CNUDA_BUF") && getenv("CNUDA_BUF")[0] == '0');
-    return on;
-}
-
 // ConvWBufLoader: both tensors under 2 GiB (32-bit byte offsets, the sentinel above them) and planes under 2^23
 // elements (24-bit multiplies in the per-chunk address arithmetic)
 bool wgrad_buffer_ok(const ConvGeom& g) {
@@ -876,19 +870,21 @@ bool wgrad_buffer_ok(const ConvGeom& g) {
 
 // largest tile that still fills the chip (small feature maps: 16x16 / 32x32): the 128-row tile wants two workgroups
 // per CU, the 64-row tile is still the better choice with one (round 3: the 32-row tile this used to force on the
-// 512-channel level at batch 16 runs at 80 TFLOP/s; -1.5 % per inference batch)
-int pick_bm(int M, long long N) {
+// 512-channel level at batch 16 runs at 80 TFLOP/s; -1.5 % per inference batch).  dcn.hip's dcn_pick_bm keeps the flat
+// 512 for both tiles: the relaxation for the 64-row tile was measured on the dense convolutions only.
+constexpr int kConvMinTiles128 = 512, kConvMinTiles64 = 256;      // tiles a launch must have to keep the 128- / 64-row tile
+int conv_pick_bm(int M, long long N) {
     int bm = M > 64 ? 128 : (M > 32 ? 64 : 32);
     const long long n_tiles = (N + IG_BN - 1) / IG_BN;
-    while (bm > 32 && n_tiles * ((M + bm - 1) / bm) < (bm == 128 ? 512 : 256)) bm >>= 1;
+    while (bm > 32 && n_tiles * ((M + bm - 1) / bm) < (bm == 128 ? kConvMinTiles128 : kConvMinTiles64)) bm >>= 1;
     return bm;
 }
 
 // Split-K (round 6, igemm.cuh igemm_fwd_*splitk_kernel): a forward-type GEMM whose pixel x row tiles at the NATURAL row tile
 // cover less than half the chip but whose K is long keeps that tile and cuts K over grid.y -- partial slabs, a fixed-order
-// reduce that runs the loader's epilogue.  pick_bm's answer to the same problem is a smaller row tile (more, emptier
+// reduce that runs the loader's epilogue.  conv_pick_bm's answer to the same problem is a smaller row tile (more, emptier
 // workgroups: 12-20 TFLOP/s on the ADVENT discriminator's 4 x 4 convolutions and the 512 -> 27 offset convolution).
-// CNUDA_SPLITK=0 keeps pick_bm's plan (A/B measurements; tests/test_gpu_kernel_switches.py).
+// CNUDA_SPLITK=0 keeps conv_pick_bm's plan (A/B measurements; tests/test_gpu_kernel_switches.py).
 struct SplitK {
     int bm = 0, z = 1, split_k = 0;          // row tile, splits, K elements per split (a multiple of the chunk)
     bool on() const { return z > 1; }
@@ -934,7 +930,66 @@ bool hwgrad_s2_ok(const ConvGeom& g) {
            4 * (round_up(g.Wo, HS_BN) - g.Wo) <= g.Wo && wgrad_buffer_ok(g);
 }
 
+// Which layers take the halo-tile kernels (hconv.cuh; CNUDA_HCONV: 0 none, 1 every eligible layer, 2 = default: the 32-row GEMMs).  Measured in
+// round 4, A/B on one box, whole benched step: 32-row GEMMs only 84.0-84.3 ms, none 84.5-84.7, every eligible layer
+// 85.0-85.3 -- the 64- and 128-row tiles are matrix-pipe-bound either way (PMC: 0.72-0.81 of the cycles the chip
+// clocks under them, profiles/r4_pmc_conv.md) and the wave-specialised im2col kernels keep the edge there; the 27-row
+// DCN offset convolutions were bound by the texture-address unit and gain 9-14 % per launch.
+int g_hconv_level = getenv("CNUDA_HCONV") ? atoi(getenv("CNUDA_HCONV")) : 2;
+int g_hconv_min_tiles = 128;         // cnuda_conv_set_halo_policy (tests)
+int hconv_level() { return g_hconv_level; }
+// kc: channels of the gathered tensor (x for the forward, grad_y for the input gradient); bm: the GEMM's row tile.
+// Small problems (under 128 pixel tiles) keep the im2col kernels: nothing to gain, and their results stay bit for bit
+// what the golden step fixtures were calibrated on.
+// Any row width that is a multiple of 8 (round 6; rounds 4-5: 16 / 32 / 64 / 128 only): the tile is TR rows x TW columns,
+// TW = the largest power of two that divides W (hconv.cuh) -- 5 column tiles on the 160- / 80- / 40-wide maps of a 640 x 640
+// input.  A map whose height is no multiple of the tile's keeps the halo kernels while the overhang stays under a quarter.
+bool hconv_ok(const ConvGeom& g, int kc, int bm) {
+    const int lv = hconv_level();
+    if (!(lv != 0 && (lv == 1 || bm == 32) && matrix_mode() == 0 && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 &&
+          g.ph == 1 && g.pw == 1 && kc % 16 == 0 && halo_tile_width(g.W) != 0 &&
+          (long long)g.B * g.H * g.W >= (long long)g_hconv_min_tiles * IG_BN &&
+          (size_t)g.B * kc * g.H * g.W * sizeof(float) < IG_BUF_OOB))
+        return false;
+    const HaloGeom hg = make_halo_geom(kc, g.H, g.W, IG_BN);
+    return hg.cells <= HC_MAXCELLS * IG_THREADS && 4 * (hg.tiles_y * hg.TR - g.H) <= g.H;
+}
+
+// Which kernel family a call of this geometry takes -- decided once, in make_plan; the entry points switch on it, the
+// queries (cnuda_conv2d_stats_block, *_supported) compare it, the profiler names come from it.  A new kernel is a new
+// member here, its rule in make_plan, its arm in the entry point.
+enum class FwdPath { SmallC, Halo, BufSplitK, Buf, PtrFast, Ptr };
+enum class DgradPath { SmallC, S2C16, Classes, ClassLoop, Halo, BufSplitK, Buf, Ptr };
+enum class WgradPath { SmallC, HaloS2, Halo, BufC8, Buf, PtrFastWs, PtrFast, Ptr };
+// the loader a WgradPath's GEMM is instantiated with, as the profiler names it (the halo / LDS-tile paths name themselves)
+const char* wgrad_loader_name(WgradPath w) {
+    switch (w) {
+        case WgradPath::BufC8: return "ConvWBufLoaderC8";
+        case WgradPath::Buf: return "ConvWBufLoader";
+        case WgradPath::PtrFastWs: case WgradPath::PtrFast: return "ConvWLoader<2>";
+        default: return "ConvWLoader<0>";
+    }
+}
+
+// taps of a kh x kw / stride (sh, sw) kernel that reach the input pixels of parity (py, px): (iy + ph - r) must be a
+// multiple of sh for every iy = py + sh * qy -- decided by py alone (C++ % keeps the dividend's sign; zero is zero either way)
+bool class_tap(const ConvGeom& g, int py, int px, int r, int t) {
+    return (py + g.ph - r) % g.sh == 0 && (px + g.pw - t) % g.sw == 0;
+}
+// K of a parity class's GEMM (ntaps == 0, a class no tap reaches: K is all padding, the kernel writes zeros)
+int class_kp(int ntaps, int Co) { return round_up(ntaps > 0 ? ntaps * Co : IG_KC, IG_KC); }
+
 struct ConvPlan {
+    // fwd / dgrad: SmallC where the LDS-tile kernels take the call; fwd_gemm / dgrad_gemm: the implicit-GEMM path of the same
+    // geometry, for the calls those kernels have no form of (a residual; an addend that aliases grad_x) -- and never SmallC
+    FwdPath fwd, fwd_gemm;
+    DgradPath dgrad, dgrad_gemm;
+    WgradPath wgrad;
+    bool fwd_buf;             // x can be read through the buffer-addressed forward loaders (also what the row-sigmoid / row-quad
+                              // / statistics loaders need, whatever fwd_gemm says)
+    bool y_buf;               // y / grad_y lies under 2 GiB
+    bool dgrad_buf;           // ... and can be read through the buffer-addressed input-gradient loaders
+    bool wgrad_ws;            // the weight-gradient GEMM runs its wave-specialised instance
     int T;
     bool hw;                  // weight gradient on halo tiles (hwgrad_kernel): Z = pixel-tile splits per channel group
     bool hw_s2;               // ... the stride-2 form (hwgrad_s2_kernel: 128-pixel tiles)
@@ -945,18 +1000,20 @@ struct ConvPlan {
     int Mpw, Jp, Z, wbm, wbj; // wgrad slabs and tile shape
     long long Nf, Nd, pix_per_split;
     size_t fwd_bytes, dgrad_bytes, wgrad_bytes;
+    size_t max_bytes;         // cnuda_conv2d_workspace_bytes: enough for every call of this geometry
 };
 ConvPlan make_plan(const ConvGeom& g) {
     ConvPlan q;
     q.T = g.kh * g.kw;
     q.Nf = (long long)g.B * g.Ho * g.Wo;
     q.Nd = (long long)g.B * g.H * g.W;
-    q.Kf = q.T * g.C;   q.Kpf = round_up(q.Kf, IG_KC);  q.bmf = pick_bm(g.Co, q.Nf);
-    q.Kd = q.T * round_up(g.Co, IG_BK);  q.Kpd = round_up(q.Kd, IG_KC);  q.bmd = pick_bm(g.C, q.Nd);
+    q.Kf = q.T * g.C;   q.Kpf = round_up(q.Kf, IG_KC);  q.bmf = conv_pick_bm(g.Co, q.Nf);
+    q.Kd = q.T * round_up(g.Co, IG_BK);  q.Kpd = round_up(q.Kd, IG_KC);  q.bmd = conv_pick_bm(g.C, q.Nd);
+    q.fwd_buf = g.C % IG_BK == 0 && buffer_addressing() && q.T <= 32 && (size_t)g.B * g.C * g.H * g.W * sizeof(float) < IG_BUF_OOB;
+    q.y_buf = (size_t)g.B * g.Co * g.Ho * g.Wo * sizeof(float) < IG_BUF_OOB;
+    q.dgrad_buf = buffer_addressing() && q.T <= 32 && q.y_buf;
     // (split-K only for the buffer-addressed loaders of the plain stride-1 paths; the parity-class input gradient plans per class)
-    const bool sk_ok = buffer_addressing() && q.T <= 32 && g.C % IG_BK == 0 &&
-                       (size_t)g.B * g.C * g.H * g.W * sizeof(float) < IG_BUF_OOB &&
-                       (size_t)g.B * g.Co * g.Ho * g.Wo * sizeof(float) < IG_BUF_OOB;
+    const bool sk_ok = q.fwd_buf && q.y_buf;
     if (sk_ok) q.skf = pick_splitk(g.Co, q.Nf, q.Kpf);
     if (sk_ok && g.sh == 1 && g.sw == 1) q.skd = pick_splitk(g.C, q.Nd, q.Kpd);
     if (q.skf.on()) q.bmf = q.skf.bm;
@@ -1007,7 +1064,67 @@ ConvPlan make_plan(const ConvGeom& g) {
     // (slabs, then the bias row sums per split: [Z][Mpw] -- never less than the [Co][B] scratch of the channel-sum kernels)
     q.wgrad_bytes = carve_bytes((size_t)q.Z * q.Mpw * q.Jp, 4) +
                     carve_bytes(std::max((size_t)g.Co * g.B, (size_t)q.Z * q.Mpw), 4) + 256;
+
+    // ---- the paths.  Each list is in order of precedence: the first rule that holds names the kernel.
+    q.fwd_gemm = q.skf.on() ? FwdPath::BufSplitK
+               : hconv_ok(g, g.C, q.bmf) ? FwdPath::Halo
+               : q.fwd_buf ? FwdPath::Buf
+               : g.C % IG_BK == 0 ? FwdPath::PtrFast : FwdPath::Ptr;
+    q.fwd = smallc_supported(g.C, g.Co, g.kh, g.kw, g.sh, g.sw) ? FwdPath::SmallC : q.fwd_gemm;
+
+    if (g.C == 16 && g.kh == 3 && g.kw == 3 && g.sh == 2 && g.sw == 2 && g.ph == 1 && g.pw == 1 && g.Co <= 256 &&
+        matrix_mode() == 0 && (size_t)g.Co * 144 * sizeof(float) <= ig_a_bytes(q.Kpd, q.Mpd)) {
+        q.dgrad_gemm = DgradPath::S2C16;      // the 16-channel full-resolution level: one thread per 2 x 2 output block
+    } else if ((g.sh > 1 || g.sw > 1) && g.H % g.sh == 0 && g.W % g.sw == 0 && g.Co % IG_BK == 0 &&
+               ceil_div(g.kh, g.sh) * ceil_div(g.kw, g.sw) <= 9) {   // taps one class can see (tap_r/tap_s hold 9)
+        // K restricted to the taps a parity class can see; all classes in ONE launch (blockIdx.y = class) unless a class
+        // cuts K over the grid (split-K, small maps) or the tensors need the pointer loaders
+        const long long Nc = (long long)g.B * (g.H / g.sh) * (g.W / g.sw);
+        bool any_split = false;
+        for (int py = 0; py < g.sh && q.dgrad_buf && !any_split; ++py)
+            for (int px = 0; px < g.sw && !any_split; ++px) {
+                int ntaps = 0;
+                for (int r = 0; r < g.kh; ++r)
+                    for (int t = 0; t < g.kw; ++t) ntaps += class_tap(g, py, px, r, t);
+                any_split = pick_splitk(g.C, Nc, class_kp(ntaps, g.Co)).on();
+            }
+        q.dgrad_gemm = (q.dgrad_buf && !any_split && g.sh * g.sw <= MAX_CLASSES && matrix_mode() == 0) ? DgradPath::Classes
+                                                                                                    : DgradPath::ClassLoop;
+    } else {
+        q.dgrad_gemm = q.skd.on() ? DgradPath::BufSplitK
+                     : hconv_ok(g, g.Co, q.bmd) ? DgradPath::Halo         // (Co % 16 == 0: Kpd = 9 Co, no padded rows)
+                     : (q.dgrad_buf && g.sh == 1 && g.sw == 1) ? DgradPath::Buf : DgradPath::Ptr;
+    }
+    // (the input gradient of a stride-1 convolution is a convolution of grad_y: the LDS-tile kernels with the roles swapped)
+    q.dgrad = (g.sh == 1 && g.sw == 1 && smallc_supported(g.Co, g.C, g.kh, g.kw, 1, 1) && g.kh - 1 - g.ph >= 0 && g.kw - 1 - g.pw >= 0)
+                  ? DgradPath::SmallC : q.dgrad_gemm;
+
+    const bool fast = g.C % 64 == 0;           // ConvWLoader<2> / ConvWBufLoader: whole 64-channel column blocks
+    q.wgrad = smallc_supported(g.C, g.Co, g.kh, g.kw, g.sh, g.sw) ? WgradPath::SmallC
+            : q.hw_s2 ? WgradPath::HaloS2
+            : q.hw ? WgradPath::Halo
+            : (!fast && g.C % 8 == 0 && wbuf && (q.wbm == 32 || (q.wbm == 64 && q.wbj == 64))) ? WgradPath::BufC8
+            : (fast && wbuf) ? WgradPath::Buf
+            : (fast && wave_specialised() && q.wbm == 64) ? WgradPath::PtrFastWs
+            : fast ? WgradPath::PtrFast : WgradPath::Ptr;
+    q.wgrad_ws = wave_specialised() && q.wbm >= 64 && (q.wgrad == WgradPath::Buf || q.wgrad == WgradPath::PtrFastWs);
+    q.max_bytes = std::max(q.fwd_bytes, std::max(q.dgrad_bytes, q.wgrad_bytes));
+    if (q.fwd == FwdPath::SmallC || smallc_supported(g.Co, g.C, g.kh, g.kw, g.sh, g.sw))     // (either direction on the LDS-tile kernels)
+        q.max_bytes = std::max(q.max_bytes, smallc_workspace_bytes(g.B, g.C, g.H, g.W, g.Co, g.kh, g.kw, g.sh, g.ph, g.pw) +
+                                                carve_bytes((size_t)g.Co * g.B, 4));
     return q;
+}
+
+// cnuda_conv2d_stats_block on a plan: the statistics layout the forward of this geometry writes (0: none)
+int plan_stats_block(const ConvGeom& g, const ConvPlan& q, int* rows, int* blocks_per_image) {
+    if (blocks_per_image) *blocks_per_image = 0;
+    if (q.fwd == FwdPath::SmallC)
+        return smallc_stats_blocks(g.B, g.C, g.H, g.W, g.Co, g.kh, g.kw, g.sh, g.ph, g.pw, blocks_per_image, rows);
+    // (the statistics epilogue exists for the buffer-addressed loader without a K split -- every DLA-34 / ResNet layer behind
+    // the stem -- and stores four pixels at a time)
+    if (q.fwd != FwdPath::Buf || ((g.Ho * g.Wo) & 3) != 0 || matrix_mode() != 0) return 0;
+    if (rows) *rows = q.Mpf;
+    return q.bmf == 32 ? 32 : 64;
 }
 
 // ---------------------------------------------------------------------------
@@ -1029,30 +1146,6 @@ struct HconvDgrad {
     using Out = ConvDgradLoader::Out;
     static const char* name() { return "dgrad"; }
 };
-// Which layers take them (CNUDA_HCONV: 0 none, 1 every eligible layer, 2 = default: the 32-row GEMMs).  Measured in
-// round 4, A/B on one box, whole benched step: 32-row GEMMs only 84.0-84.3 ms, none 84.5-84.7, every eligible layer
-// 85.0-85.3 -- the 64- and 128-row tiles are matrix-pipe-bound either way (PMC: 0.72-0.81 of the cycles the chip
-// clocks under them, profiles/r4_pmc_conv.md) and the wave-specialised im2col kernels keep the edge there; the 27-row
-// DCN offset convolutions were bound by the texture-address unit and gain 9-14 % per launch.
-int g_hconv_level = getenv("CNUDA_HCONV") ? atoi(getenv("CNUDA_HCONV")) : 2;
-int g_hconv_min_tiles = 128;         // cnuda_conv_set_halo_policy (tests)
-int hconv_level() { return g_hconv_level; }
-// kc: channels of the gathered tensor (x for the forward, grad_y for the input gradient); bm: the GEMM's row tile.
-// Small problems (under 128 pixel tiles) keep the im2col kernels: nothing to gain, and their results stay bit for bit
-// what the golden step fixtures were calibrated on.
-// Any row width that is a multiple of 8 (round 6; rounds 4-5: 16 / 32 / 64 / 128 only): the tile is TR rows x TW columns,
-// TW = the largest power of two that divides W (hconv.cuh) -- 5 column tiles on the 160- / 80- / 40-wide maps of a 640 x 640
-// input.  A map whose height is no multiple of the tile's keeps the halo kernels while the overhang stays under a quarter.
-bool hconv_ok(const ConvGeom& g, int kc, int bm) {
-    const int lv = hconv_level();
-    if (!(lv != 0 && (lv == 1 || bm == 32) && matrix_mode() == 0 && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 &&
-          g.ph == 1 && g.pw == 1 && kc % 16 == 0 && halo_tile_width(g.W) != 0 &&
-          (long long)g.B * g.H * g.W >= (long long)g_hconv_min_tiles * IG_BN &&
-          (size_t)g.B * kc * g.H * g.W * sizeof(float) < IG_BUF_OOB))
-        return false;
-    const HaloGeom hg = make_halo_geom(kc, g.H, g.W, IG_BN);
-    return hg.cells <= HC_MAXCELLS * IG_THREADS && 4 * (hg.tiles_y * hg.TR - g.H) <= g.H;
-}
 template <int BM, int BN, class Ad>
 bool hconv_launch_one(const typename Ad::Params& p, const float* src, const float* A, int Mp, int Kp, int M, long long N,
                       int m_tiles, const HaloGeom& hg, hipStream_t st) {
@@ -1076,12 +1169,12 @@ int launch_hconv(int bm, const typename Ad::Params& p, const float* src, int kc,
     const HaloGeom hg = wide ? hg2 : make_halo_geom(kc, g.H, g.W, 128);
     ProfScope prof(st);
     prof.name("hconv_kernel<%d, %d, %s>", bm, wide ? 256 : 128, Ad::name());
-    bool ok;
-    if (bm == 128) ok = hconv_launch_one<128, 128, Ad>(p, src, A, Mp, Kp, M, N, m_tiles, hg, st);
-    else if (bm == 64 && wide) ok = hconv_launch_one<64, 256, Ad>(p, src, A, Mp, Kp, M, N, m_tiles, hg, st);
-    else if (bm == 64) ok = hconv_launch_one<64, 128, Ad>(p, src, A, Mp, Kp, M, N, m_tiles, hg, st);
-    else if (wide) ok = hconv_launch_one<32, 256, Ad>(p, src, A, Mp, Kp, M, N, m_tiles, hg, st);
-    else ok = hconv_launch_one<32, 128, Ad>(p, src, A, Mp, Kp, M, N, m_tiles, hg, st);
+    bool ok = false;
+    CNUDA_REQUIRE((with_tiles<Tile<128, 128>, Tile<64, 256>, Tile<64, 128>, Tile<32, 256>, Tile<32, 128>>(
+                      bm, wide ? 256 : 128, [&](auto BM, auto BN) {
+                          ok = hconv_launch_one<BM(), BN(), Ad>(p, src, A, Mp, Kp, M, N, m_tiles, hg, st);
+                      })),
+                  "%s: no hconv_kernel instance for a %d-row tile", who, bm);
     if (!ok) return CNUDA_ERR_INVALID_ARGUMENT;
     return check_launch(who);
 }
@@ -1180,25 +1273,27 @@ int launch_fwd(int bm, const typename Loader::Params& p, const float* A, int Mp,
                hipStream_t st, const char* who, const SplitK& sk = SplitK(), float* slab = nullptr) {
     CNUDA_REQUIRE(N < (1ll << 31) - IG_BN, "%s: more than 2^31 pixels per call", who);
     const int n_tiles = ceil_div(N, IG_BN), m_tiles = Mp / bm;
-    const dim3 grid(n_tiles * m_tiles), block(IG_THREADS);
+    const dim3 grid(n_tiles * m_tiles), block(IG_THREADS), block2(2 * IG_THREADS);
+    // wave-specialised variant (igemm.cuh): +4-8 % on the 64- and 128-row tiles of the 128..512-channel layers,
+    // neutral on the 64-channel ones, -2-4 % on the 32-row tile, which therefore keeps the 4-wave kernel (and has no instance)
+    const bool ws = matrix_mode() == 0 && wave_specialised() && bm >= 64;
+    bool found;
     ProfScope prof(st);
     if constexpr (SplitKLoader<Loader>::value) {
         if (sk.on()) {
             CNUDA_REQUIRE(slab && bm == sk.bm && matrix_mode() == 0, "%s: split-K plan without its slabs", who);
-            const bool ws = wave_specialised() && bm >= 64;
             prof.name(ws ? "igemm_fwd_ws_splitk_kernel<%d, %s> x %d + reduce" : "igemm_fwd_splitk_kernel<%d, %s> x %d + reduce",
                       bm, Loader::name(), sk.z);
             const dim3 gridz(n_tiles * m_tiles, sk.z);
-            if (bm == 128 && ws)
-                CNUDA_LAUNCH((igemm_fwd_ws_splitk_kernel<128, Loader>), gridz, dim3(2 * IG_THREADS), 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles, slab, sk.split_k);
-            else if (bm == 64 && ws)
-                CNUDA_LAUNCH((igemm_fwd_ws_splitk_kernel<64, Loader>), gridz, dim3(2 * IG_THREADS), 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles, slab, sk.split_k);
-            else if (bm == 128)
-                CNUDA_LAUNCH((igemm_fwd_splitk_kernel<128, Loader>), gridz, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles, slab, sk.split_k);
-            else if (bm == 64)
-                CNUDA_LAUNCH((igemm_fwd_splitk_kernel<64, Loader>), gridz, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles, slab, sk.split_k);
+            if (ws)
+                found = with_tile<64, 128>(bm, [&](auto BM) {
+                    CNUDA_LAUNCH((igemm_fwd_ws_splitk_kernel<BM(), Loader>), gridz, block2, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles, slab, sk.split_k);
+                });
             else
-                CNUDA_LAUNCH((igemm_fwd_splitk_kernel<32, Loader>), gridz, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles, slab, sk.split_k);
+                found = with_tile<32, 64, 128>(bm, [&](auto BM) {
+                    CNUDA_LAUNCH((igemm_fwd_splitk_kernel<BM(), Loader>), gridz, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles, slab, sk.split_k);
+                });
+            CNUDA_REQUIRE(found, "%s: no split-K kernel instance for a %d-row tile", who, bm);
             CNUDA_LAUNCH((splitk_reduce_kernel<Loader>), dim3(ceil_div(N, 256), ceil_div(M, SK_ROWS)), dim3(256), 0, st, p, slab, sk.z,
                          Mp, (long long)n_tiles * IG_BN, M, N);
             return check_launch(who);
@@ -1216,7 +1311,6 @@ int launch_fwd(int bm, const typename Loader::Params& p, const float* A, int Mp,
             return check_launch(who);
         }
     }
-    const bool ws = matrix_mode() == 0 && wave_specialised() && bm >= 64;
     prof.name(matrix_mode() == 1 ? "igemm_fwd_kernel<%d, %s> [split bf16 x3]"
                                  : (ws ? "igemm_fwd_ws_kernel<%d, %s>" : "igemm_fwd_kernel<%d, %s>"), bm, Loader::name());
     if (matrix_mode() == 1) {
@@ -1224,66 +1318,39 @@ int launch_fwd(int bm, const typename Loader::Params& p, const float* A, int Mp,
         float* A3 = const_cast<float*>(A) + (size_t)Kp * Mp;
         CNUDA_LAUNCH(split_a_kernel, dim3(stream_grid((long long)(Kp / 16) * 2 * Mp, 256)), dim3(256), 0, st, A,
                            reinterpret_cast<u32x4*>(A3), Kp, Mp);
-        A = A3;
-        if (bm == 128)
-            CNUDA_LAUNCH((igemm_fwd_kernel<128, Loader, true>), grid, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles);
-        else if (bm == 64)
-            CNUDA_LAUNCH((igemm_fwd_kernel<64, Loader, true>), grid, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles);
-        else
-            CNUDA_LAUNCH((igemm_fwd_kernel<32, Loader, true>), grid, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles);
-        return check_launch(who);
+        found = with_tile<32, 64, 128>(bm, [&](auto BM) {
+            CNUDA_LAUNCH((igemm_fwd_kernel<BM(), Loader, true>), grid, block, 0, st, p, A3, Mp, Kp, M, N, n_tiles, m_tiles);
+        });
+    } else if (ws) {
+        found = with_tile<64, 128>(bm, [&](auto BM) {
+            CNUDA_LAUNCH((igemm_fwd_ws_kernel<BM(), Loader>), grid, block2, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles);
+        });
+    } else {
+        found = with_tile<32, 64, 128>(bm, [&](auto BM) {
+            CNUDA_LAUNCH((igemm_fwd_kernel<BM(), Loader>), grid, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles);
+        });
     }
-    // wave-specialised variant (igemm.cuh): +4-8 % on the 64- and 128-row tiles of the 128..512-channel layers,
-    // neutral on the 64-channel ones, -2-4 % on the 32-row tile, which therefore keeps the 4-wave kernel
-    if (wave_specialised() && bm >= 64) {
-        const dim3 block2(2 * IG_THREADS);
-        if (bm == 128)
-            CNUDA_LAUNCH((igemm_fwd_ws_kernel<128, Loader>), grid, block2, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles);
-        else
-            CNUDA_LAUNCH((igemm_fwd_ws_kernel<64, Loader>), grid, block2, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles);
-        return check_launch(who);
-    }
-    if (bm == 128)
-        CNUDA_LAUNCH((igemm_fwd_kernel<128, Loader>), grid, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles);
-    else if (bm == 64)
-        CNUDA_LAUNCH((igemm_fwd_kernel<64, Loader>), grid, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles);
-    else
-        CNUDA_LAUNCH((igemm_fwd_kernel<32, Loader>), grid, block, 0, st, p, A, Mp, Kp, M, N, n_tiles, m_tiles);
+    CNUDA_REQUIRE(found, "%s: no igemm_fwd kernel instance for a %d-row tile", who, bm);
     return check_launch(who);
 }
 
+// The weight-gradient GEMM of one loader: `Tiles` lists the (row, column) tile shapes compiled for it, WS picks the
+// wave-specialised kernel.  false: the plan's tile is not among them.
+template <class Loader, bool WS, class... Tiles, class P>
+bool launch_wgrad(const ConvPlan& q, const P& p, float* slabs, float* bsl, hipStream_t st) {
+    const dim3 grid(q.Jp / q.wbj, q.Mpw / q.wbm, q.Z), blk((WS ? 2 : 1) * IG_THREADS);
+    return with_tiles<Tiles...>(q.wbm, q.wbj, [&](auto BM, auto BJ) {
+        if constexpr (WS)
+            CNUDA_LAUNCH((igemm_wgrad_ws_kernel<Loader, BM(), BJ()>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp, q.Nf, q.pix_per_split, bsl);
+        else
+            CNUDA_LAUNCH((igemm_wgrad_kernel<Loader, BM(), BJ()>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp, q.Nf, q.pix_per_split, bsl);
+    });
+}
 // the tile variants of the buffer-addressed weight-gradient GEMM (ConvWBufLoader; ConvWCatLoader)
 template <class Loader>
-void launch_wgrad_buf(const ConvPlan& q, const typename Loader::Params& p, dim3 grid, float* slabs, float* bsl, hipStream_t st) {
-    const dim3 blk(IG_THREADS);
-    const dim3 blk2(2 * IG_THREADS);
-    if (q.wbm == 128 && q.wbj == 128 && wave_specialised())
-        CNUDA_LAUNCH((igemm_wgrad_ws_kernel<Loader, 128, 128>), grid, blk2, 0, st, p, slabs, q.Mpw,
-                           q.Jp, q.Nf, q.pix_per_split, bsl);
-    else if (q.wbm == 128 && q.wbj == 128)
-        CNUDA_LAUNCH((igemm_wgrad_kernel<Loader, 128, 128>), grid, blk, 0, st, p, slabs, q.Mpw,
-                           q.Jp, q.Nf, q.pix_per_split, bsl);
-    else if (q.wbm == 128 && wave_specialised())
-        CNUDA_LAUNCH((igemm_wgrad_ws_kernel<Loader, 128, 64>), grid, blk2, 0, st, p, slabs, q.Mpw,
-                           q.Jp, q.Nf, q.pix_per_split, bsl);
-    else if (q.wbm == 128)
-        CNUDA_LAUNCH((igemm_wgrad_kernel<Loader, 128, 64>), grid, blk, 0, st, p, slabs, q.Mpw,
-                           q.Jp, q.Nf, q.pix_per_split, bsl);
-    else if (wave_specialised() && q.wbm == 64 && q.wbj == 128)
-        CNUDA_LAUNCH((igemm_wgrad_ws_kernel<Loader, 64, 128>), grid, blk2, 0, st, p, slabs, q.Mpw,
-                           q.Jp, q.Nf, q.pix_per_split, bsl);
-    else if (wave_specialised() && q.wbm == 64)
-        CNUDA_LAUNCH((igemm_wgrad_ws_kernel<Loader, 64, 64>), grid, blk2, 0, st, p, slabs, q.Mpw,
-                           q.Jp, q.Nf, q.pix_per_split, bsl);
-    else if (q.wbm == 64 && q.wbj == 128)
-        CNUDA_LAUNCH((igemm_wgrad_kernel<Loader, 64, 128>), grid, blk, 0, st, p, slabs, q.Mpw,
-                           q.Jp, q.Nf, q.pix_per_split, bsl);
-    else if (q.wbm == 64)
-        CNUDA_LAUNCH((igemm_wgrad_kernel<Loader, 64, 64>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp,
-                           q.Nf, q.pix_per_split, bsl);
-    else
-        CNUDA_LAUNCH((igemm_wgrad_kernel<Loader, 32, 128>), grid, blk, 0, st, p, slabs, q.Mpw,
-                           q.Jp, q.Nf, q.pix_per_split, bsl);
+bool launch_wgrad_buf(const ConvPlan& q, const typename Loader::Params& p, float* slabs, float* bsl, hipStream_t st) {
+    return q.wgrad_ws ? launch_wgrad<Loader, true, Tile<128, 128>, Tile<128, 64>, Tile<64, 128>, Tile<64, 64>>(q, p, slabs, bsl, st)
+                      : launch_wgrad<Loader, false, Tile<128, 128>, Tile<128, 64>, Tile<64, 128>, Tile<64, 64>, Tile<32, 128>>(q, p, slabs, bsl, st);
 }
 
 }  // namespace
@@ -1308,15 +1375,7 @@ extern "C" size_t cnuda_conv2d_workspace_bytes(int B, int C, int H, int W, int C
                                                int ph, int pw) {
     ConvGeom g;
     if (fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_workspace_bytes")) return 0;
-    const ConvPlan q = make_plan(g);
-    size_t m = q.fwd_bytes;
-    if (q.dgrad_bytes > m) m = q.dgrad_bytes;
-    if (q.wgrad_bytes > m) m = q.wgrad_bytes;
-    if (smallc_supported(C, Cout, kh, kw, sh, sw) || smallc_supported(Cout, C, kh, kw, sh, sw)) {
-        const size_t sm = smallc_workspace_bytes(B, C, H, W, Cout, kh, kw, sh, ph, pw) + carve_bytes((size_t)Cout * B, 4);
-        if (sm > m) m = sm;
-    }
-    return m;
+    return make_plan(g).max_bytes;
 }
 
 extern "C" int cnuda_conv2d_forward(const float* x, const float* weight, const float* bias, float* y, int B, int C,
@@ -1335,16 +1394,7 @@ extern "C" int cnuda_conv2d_stats_block(int B, int C, int H, int W, int Cout, in
                                         int pw, int* rows, int* blocks_per_image) {
     ConvGeom g;
     if (fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_stats_block")) return 0;
-    if (blocks_per_image) *blocks_per_image = 0;
-    if (smallc_supported(C, Cout, kh, kw, sh, sw)) return smallc_stats_blocks(B, C, H, W, Cout, kh, kw, sh, ph, pw, blocks_per_image, rows);
-    if (((g.Ho * g.Wo) & 3) != 0) return 0;
-    const ConvPlan q = make_plan(g);
-    if (q.skf.on() || hconv_ok(g, C, q.bmf)) return 0;
-    // (the statistics kernels exist for the buffer-addressed loader: every DLA-34 / ResNet layer behind the stem)
-    if (!(C % IG_BK == 0 && buffer_addressing() && q.T <= 32 && (size_t)B * C * H * W * sizeof(float) < IG_BUF_OOB) || matrix_mode() != 0)
-        return 0;
-    if (rows) *rows = q.Mpf;
-    return q.bmf == 32 ? 32 : 64;
+    return plan_stats_block(g, make_plan(g), rows, blocks_per_image);
 }
 
 extern "C" int cnuda_conv2d_forward_res(const float* x, const float* weight, const float* bias, const float* residual,
@@ -1362,42 +1412,41 @@ extern "C" int cnuda_conv2d_forward_stats(const float* x, const float* weight, c
     CNUDA_REQUIRE(x && weight && y, "cnuda_conv2d_forward: null pointer");
     ConvGeom g;
     if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_forward")) return rc;
-    if (stats) {
-        int rows = 0;
-        CNUDA_REQUIRE(!residual && act_slope < 0.0f &&
-                          cnuda_conv2d_stats_block(B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, &rows, nullptr) != 0,
-                      "cnuda_conv2d_forward_stats: no statistics for this call (cnuda_conv2d_stats_block says which)");
-    }
-    if (!residual && smallc_supported(C, Cout, kh, kw, sh, sw))
+    const ConvPlan q = make_plan(g);
+    CNUDA_REQUIRE(!stats || (!residual && act_slope < 0.0f && plan_stats_block(g, q, nullptr, nullptr) != 0),
+                  "cnuda_conv2d_forward_stats: no statistics for this call (cnuda_conv2d_stats_block says which)");
+    const FwdPath path = residual ? q.fwd_gemm : q.fwd;       // (the LDS-tile kernels have no residual)
+    if (path == FwdPath::SmallC)
         return smallc_forward(x, weight, bias, y, B, C, H, W, Cout, kh, kw, sh, ph, pw, act_slope, 0, workspace,
                               workspace_bytes, (hipStream_t)stream, stats);
-    const ConvPlan q = make_plan(g);
     CNUDA_REQUIRE(workspace && workspace_bytes >= q.fwd_bytes, "cnuda_conv2d_forward: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     Carver cv(workspace, workspace_bytes);
     ConvFwdParams p{g, x, bias, y, act_slope, residual};
-    if (!q.skf.on() && hconv_ok(g, C, q.bmf)) {      // (K = 9 C is already a multiple of the chunk: the same packed size, another K order)
-        const float* Ah = launch_pack(weight, reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpf, q.Mpf))),
-                                      ig_a_bytes(q.Kpf, q.Mpf), Cout, C, q.T, PACK_HALO_FWD, q.Kpf, q.Mpf, 0, st);
-        return launch_hconv<HconvFwd>(q.bmf, p, x, C, g, Ah, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
+    // (halo tiles: K = 9 C is already a multiple of the chunk -- the same packed size, another K order)
+    const float* A = launch_pack(weight, reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpf, q.Mpf))), ig_a_bytes(q.Kpf, q.Mpf),
+                                 Cout, C, q.T, path == FwdPath::Halo ? PACK_HALO_FWD : PACK_FWD, q.Kpf, q.Mpf, 0, st);
+    switch (path) {
+        case FwdPath::Halo:
+            return launch_hconv<HconvFwd>(q.bmf, p, x, C, g, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
+        case FwdPath::BufSplitK: {
+            float* slab = reinterpret_cast<float*>(cv.take<char>(splitk_slab_bytes(q.skf, Cout, q.Nf)));
+            return launch_fwd<ConvFwdBufLoader>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward", q.skf, slab);
+        }
+        case FwdPath::Buf:
+            if (stats) {            // (plan_stats_block vouched for this path)
+                ConvFwdStatsParams ps;
+                static_cast<ConvFwdParams&>(ps) = p;
+                ps.stats = stats;
+                ps.stats_mp = q.Mpf;
+                return launch_fwd<ConvFwdBufStatsLoader>(q.bmf, ps, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward_stats");
+            }
+            return launch_fwd<ConvFwdBufLoader>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
+        case FwdPath::PtrFast:
+            return launch_fwd<ConvFwdLoader<true>>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
+        default:
+            return launch_fwd<ConvFwdLoader<false>>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
     }
-    const float* A = launch_pack(weight, reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpf, q.Mpf))),
-                                 ig_a_bytes(q.Kpf, q.Mpf), Cout, C, q.T, PACK_FWD, q.Kpf, q.Mpf, 0, st);
-    if (stats) {            // (cnuda_conv2d_stats_block vouched for the buffer-addressed loader)
-        ConvFwdStatsParams ps;
-        static_cast<ConvFwdParams&>(ps) = p;
-        ps.stats = stats;
-        ps.stats_mp = q.Mpf;
-        return launch_fwd<ConvFwdBufStatsLoader>(q.bmf, ps, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward_stats");
-    }
-    if (C % IG_BK == 0 && buffer_addressing() && q.T <= 32 && (size_t)B * C * H * W * sizeof(float) < IG_BUF_OOB) {
-        float* slab = q.skf.on() ? reinterpret_cast<float*>(cv.take<char>(splitk_slab_bytes(q.skf, Cout, q.Nf))) : nullptr;
-        return launch_fwd<ConvFwdBufLoader>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward", q.skf, slab);
-    }
-    CNUDA_REQUIRE(!q.skf.on(), "cnuda_conv2d_forward: split-K plan off the buffer-addressed path");
-    if (C % IG_BK == 0)
-        return launch_fwd<ConvFwdLoader<true>>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
-    return launch_fwd<ConvFwdLoader<false>>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
 }
 
 // ---- the 1x1 convolution over a channel concatenation (ConvCat; DLA's Root) ------------------------------------------------
@@ -1433,10 +1482,10 @@ extern "C" int cnuda_conv2d_cat_supported(const int* cs, int n, int B, int H, in
     const int C = cat_channels(cs, n);
     ConvGeom g;
     if (fill_geom(g, B, C, H, W, Cout, 1, 1, 1, 1, 0, 0, "cnuda_conv2d_cat_supported")) return 0;
-    int rows = 0;
-    if (!cnuda_conv2d_stats_block(B, C, H, W, Cout, 1, 1, 1, 1, 0, 0, &rows, nullptr)) return 0;   // (buffer-addressed, no K split, H*W % 4 == 0)
+    // the concatenating loaders are forms of the buffer-addressed GEMMs without a K split, in all three directions; their
+    // forward epilogue stores four pixels at a time
     const ConvPlan q = make_plan(g);
-    return !q.skd.on() && !q.hw && !q.hw_s2 && wgrad_buffer_ok(g) && (size_t)B * Cout * H * W * sizeof(float) < IG_BUF_OOB;
+    return q.fwd == FwdPath::Buf && q.dgrad == DgradPath::Buf && q.wgrad == WgradPath::Buf && ((H * W) & 3) == 0;
 }
 
 extern "C" int cnuda_conv2d_cat_forward(const float* const* xs, const int* cs, int n, const float* weight, const float* bias,
@@ -1512,9 +1561,10 @@ extern "C" int cnuda_conv2d_cat_backward_weight(const float* const* xs, const in
     static_cast<ConvWParams&>(p) = ConvWParams{g, nullptr, grad_y};
     {
         ProfScope prof(st);
-        prof.name((wave_specialised() && q.wbm >= 64) ? "igemm_wgrad_ws_kernel<ConvWCatLoader, %d, %d>" : "igemm_wgrad_kernel<ConvWCatLoader, %d, %d>",
+        prof.name(q.wgrad_ws ? "igemm_wgrad_ws_kernel<ConvWCatLoader, %d, %d>" : "igemm_wgrad_kernel<ConvWCatLoader, %d, %d>",
                   q.wbm, q.wbj);
-        launch_wgrad_buf<ConvWCatLoader>(q, p, dim3(q.Jp / q.wbj, q.Mpw / q.wbm, q.Z), slabs, nullptr, st);
+        CNUDA_REQUIRE(launch_wgrad_buf<ConvWCatLoader>(q, p, slabs, nullptr, st),
+                      "cnuda_conv2d_cat_backward_weight: no kernel instance for a %d x %d tile", q.wbm, q.wbj);
     }
     if (int rc = check_launch("cnuda_conv2d_cat_backward_weight")) return rc;
     launch_slab_reduce(slabs, grad_weight, q.Z, q.Mpw, q.Jp, Cout, C, q.T, st, nullptr, nullptr);
@@ -1528,10 +1578,9 @@ extern "C" int cnuda_conv2d_rowquads_supported(int B, int C, int H, int W, int C
                                                int pw) {
     ConvGeom g;
     if (fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_rowquads_supported")) return 0;
-    if (Cout % 4 != 0 || smallc_supported(C, Cout, kh, kw, sh, sw)) return 0;
+    // (a form of the buffer-addressed GEMM, also where the plain forward would take halo tiles)
     const ConvPlan q = make_plan(g);
-    return !q.skf.on() && C % IG_BK == 0 && buffer_addressing() && q.T <= 32 &&
-           (size_t)B * C * H * W * sizeof(float) < IG_BUF_OOB;
+    return Cout % 4 == 0 && q.fwd != FwdPath::SmallC && q.fwd != FwdPath::BufSplitK && q.fwd_buf;
 }
 
 extern "C" int cnuda_conv2d_forward_rowquads(const float* x, const float* weight, float* y, int B, int C, int H, int W,
@@ -1559,9 +1608,8 @@ extern "C" int cnuda_conv2d_rowsig_supported(int B, int C, int H, int W, int Cou
                                              int pw) {
     ConvGeom g;
     if (fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_rowsig_supported")) return 0;
-    return (Cout <= 32 && C % IG_BK == 0 && buffer_addressing() && kh * kw <= 32 && matrix_mode() == 0 &&
-            (size_t)B * C * H * W * sizeof(float) < IG_BUF_OOB && (size_t)B * Cout * g.Ho * g.Wo * sizeof(float) < IG_BUF_OOB &&
-            !smallc_supported(C, Cout, kh, kw, sh, sw)) ? 1 : 0;
+    const ConvPlan q = make_plan(g);
+    return (Cout <= 32 && matrix_mode() == 0 && q.fwd != FwdPath::SmallC && q.fwd_buf && q.y_buf) ? 1 : 0;
 }
 extern "C" int cnuda_conv2d_forward_rowsig(const float* x, const float* weight, const float* bias, float* y, int sig_from,
                                            int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
@@ -1578,13 +1626,10 @@ extern "C" int cnuda_conv2d_forward_rowsig(const float* x, const float* weight, 
     ConvFwdSigParams p;
     static_cast<ConvFwdParams&>(p) = ConvFwdParams{g, x, bias, y, -1.0f, nullptr};
     p.sig_from = sig_from;
-    if (!q.skf.on() && hconv_ok(g, C, q.bmf)) {
-        const float* Ah = launch_pack(weight, reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpf, q.Mpf))),
-                                      ig_a_bytes(q.Kpf, q.Mpf), Cout, C, q.T, PACK_HALO_FWD, q.Kpf, q.Mpf, 0, st);
-        return launch_hconv<HconvFwdSig>(q.bmf, p, x, C, g, Ah, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward_rowsig");
-    }
-    const float* A = launch_pack(weight, reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpf, q.Mpf))),
-                                 ig_a_bytes(q.Kpf, q.Mpf), Cout, C, q.T, PACK_FWD, q.Kpf, q.Mpf, 0, st);
+    const bool halo = q.fwd == FwdPath::Halo;
+    const float* A = launch_pack(weight, reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpf, q.Mpf))), ig_a_bytes(q.Kpf, q.Mpf),
+                                 Cout, C, q.T, halo ? PACK_HALO_FWD : PACK_FWD, q.Kpf, q.Mpf, 0, st);
+    if (halo) return launch_hconv<HconvFwdSig>(q.bmf, p, x, C, g, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward_rowsig");
     float* slab = q.skf.on() ? reinterpret_cast<float*>(cv.take<char>(splitk_slab_bytes(q.skf, Cout, q.Nf))) : nullptr;
     return launch_fwd<ConvFwdBufSigLoader>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward_rowsig", q.skf, slab);
 }
@@ -1658,7 +1703,9 @@ extern "C" int cnuda_conv2d_backward_data_add(const float* grad_y, const float* 
     // in a second pass, which would double the new gradient and lose the old content -> they take the call only when
     // no addend aliases the output.
     const bool aliased = (addend && addend == grad_x) || (addend2 && addend2 == grad_x);
-    if (!aliased && sh == 1 && sw == 1 && smallc_supported(Cout, C, kh, kw, 1, 1) && kh - 1 - ph >= 0 && kw - 1 - pw >= 0) {
+    const ConvPlan q = make_plan(g);
+    const DgradPath path = aliased ? q.dgrad_gemm : q.dgrad;
+    if (path == DgradPath::SmallC) {
         // (the LDS-tile kernels of the 3- / 16-channel layers have no addend: one elementwise pass behind them)
         if (int rc = smallc_forward(grad_y, weight, nullptr, grad_x, B, Cout, g.Ho, g.Wo, C, kh, kw, 1, kh - 1 - ph,
                                     kw - 1 - pw, -1.0f, 1, workspace, workspace_bytes, (hipStream_t)stream))
@@ -1666,14 +1713,11 @@ extern "C" int cnuda_conv2d_backward_data_add(const float* grad_y, const float* 
         if (addend) if (int rc = cnuda_add(grad_x, addend, grad_x, (long long)B * C * H * W, stream)) return rc;
         return addend2 ? cnuda_add(grad_x, addend2, grad_x, (long long)B * C * H * W, stream) : 0;
     }
-    const ConvPlan q = make_plan(g);
     CNUDA_REQUIRE(workspace && workspace_bytes >= q.dgrad_bytes, "cnuda_conv2d_backward_data: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     Carver cv(workspace, workspace_bytes);
     float* Aws = reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpd, q.Mpd)));
-    if (C == 16 && kh == 3 && kw == 3 && sh == 2 && sw == 2 && ph == 1 && pw == 1 && Cout <= 256 && matrix_mode() == 0 &&
-        (size_t)Cout * 144 * sizeof(float) <= ig_a_bytes(q.Kpd, q.Mpd)) {
-        // the 16-channel full-resolution level: one thread per 2 x 2 output block (dgrad_s2_c16_kernel)
+    if (path == DgradPath::S2C16) {
         CNUDA_LAUNCH(dgrad_s2_c16_pack_kernel, dim3((Cout * 144 + 255) / 256), dim3(256), 0, st, weight, Aws, Cout);
         DgradS2Params dp{grad_y, Aws, grad_x, addend, addend2, B, Cout, H, W, g.Ho, g.Wo, (H + 1) / 2, (W + 1) / 2};
         ProfScope prof(st);
@@ -1681,17 +1725,14 @@ extern "C" int cnuda_conv2d_backward_data_add(const float* grad_y, const float* 
         CNUDA_LAUNCH(dgrad_s2_c16_kernel, dim3((dp.QW + 63) / 64, (dp.QH + 3) / 4, B), dim3(256), 0, st, dp);
         return check_launch("cnuda_conv2d_backward_data(stride 2, 16 channels)");
     }
-    const bool buf_ok = buffer_addressing() && q.T <= 32 && (size_t)B * Cout * g.Ho * g.Wo * sizeof(float) < IG_BUF_OOB;
-    if ((sh > 1 || sw > 1) && H % sh == 0 && W % sw == 0 && Cout % IG_BK == 0 &&
-        ceil_div(kh, sh) * ceil_div(kw, sw) <= 9) {   // taps one class can see (tap_r/tap_s hold 9)
-        // K restricted to the taps a parity class can see; all classes in ONE launch (blockIdx.y = class) unless a class
-        // cuts K over the grid (split-K, small maps) or the tensors need the pointer loaders
+    if (path == DgradPath::Classes || path == DgradPath::ClassLoop) {
+        // (ClassLoop: one launch per class -- buffer-addressed, each with its own split-K plan, or the pointer loader)
+        const bool buf_ok = q.dgrad_buf;
         ProfScope prof(st);   // brackets the whole class group (inner scopes find nothing armed)
         prof.name("igemm_fwd*_kernel<*, ConvDgradClassLoader> x %d parity classes", sh * sw);
         const long long Nc = (long long)B * (H / sh) * (W / sw);
         ConvDgradClassParams cps[16];
         int Kpcs[16], taps_all[16][9], ncls = 0;
-        bool any_split = false;
         for (int py = 0; py < sh; ++py)
             for (int px = 0; px < sw; ++px) {
                 CNUDA_REQUIRE(ncls < 16, "cnuda_conv2d_backward_data: more than 16 parity classes");
@@ -1701,21 +1742,16 @@ extern "C" int cnuda_conv2d_backward_data_add(const float* grad_y, const float* 
                 cp.ntaps = 0;
                 for (int r = 0; r < kh; ++r)
                     for (int t = 0; t < kw; ++t)
-                        // (iy + ph - r) must be a multiple of sh for every iy = py + sh*qy: decided by py alone
-                        // (C++ % keeps the dividend's sign; zero is zero either way)
-                        if ((py + ph - r) % sh == 0 && (px + pw - t) % sw == 0) {
+                        if (class_tap(g, py, px, r, t)) {
                             cp.tap_r[cp.ntaps] = r; cp.tap_s[cp.ntaps] = t; taps_all[ncls][cp.ntaps] = r * kw + t;
                             cp.tap_dy[cp.ntaps] = (py + ph - r) / sh; cp.tap_dx[cp.ntaps] = (px + pw - t) / sw;
                             ++cp.ntaps;
                         }
-                // ntaps == 0 (a class no tap reaches): K is all padding, the kernel writes zeros
-                const int Kc = cp.ntaps * Cout;
-                Kpcs[ncls] = round_up(Kc > 0 ? Kc : IG_KC, IG_KC);
-                any_split = any_split || (buf_ok && pick_splitk(C, Nc, Kpcs[ncls]).on());
+                Kpcs[ncls] = class_kp(cp.ntaps, Cout);
                 ++ncls;
             }
-        if (buf_ok && !any_split && ncls <= MAX_CLASSES && matrix_mode() == 0) {
-            const int bm = pick_bm(C, Nc * ncls), Mp = round_up(C, bm);      // (the grid is ncls times one class's)
+        if (path == DgradPath::Classes) {
+            const int bm = conv_pick_bm(C, Nc * ncls), Mp = round_up(C, bm);      // (the grid is ncls times one class's)
             // classes in order of decreasing K: the long ones start first
             int order[MAX_CLASSES];
             for (int i = 0; i < ncls; ++i) order[i] = i;
@@ -1736,16 +1772,14 @@ extern "C" int cnuda_conv2d_backward_data_add(const float* grad_y, const float* 
             CNUDA_REQUIRE(Nc < (1ll << 31) - IG_BN, "cnuda_conv2d_backward_data: more than 2^31 pixels per call");
             const int n_tiles = ceil_div(Nc, IG_BN), m_tiles = Mp / bm;
             const dim3 grid(n_tiles * m_tiles, ncls);
-            if (wave_specialised() && bm == 128)
-                CNUDA_LAUNCH((igemm_fwd_ws_classes_kernel<128>), grid, dim3(2 * IG_THREADS), 0, st, set, Mp, C, Nc, n_tiles, m_tiles);
-            else if (wave_specialised() && bm == 64)
-                CNUDA_LAUNCH((igemm_fwd_ws_classes_kernel<64>), grid, dim3(2 * IG_THREADS), 0, st, set, Mp, C, Nc, n_tiles, m_tiles);
-            else if (bm == 128)
-                CNUDA_LAUNCH((igemm_fwd_classes_kernel<128>), grid, dim3(IG_THREADS), 0, st, set, Mp, C, Nc, n_tiles, m_tiles);
-            else if (bm == 64)
-                CNUDA_LAUNCH((igemm_fwd_classes_kernel<64>), grid, dim3(IG_THREADS), 0, st, set, Mp, C, Nc, n_tiles, m_tiles);
-            else
-                CNUDA_LAUNCH((igemm_fwd_classes_kernel<32>), grid, dim3(IG_THREADS), 0, st, set, Mp, C, Nc, n_tiles, m_tiles);
+            const bool found = (wave_specialised() && bm >= 64)
+                ? with_tile<64, 128>(bm, [&](auto BM) {
+                      CNUDA_LAUNCH((igemm_fwd_ws_classes_kernel<BM()>), grid, dim3(2 * IG_THREADS), 0, st, set, Mp, C, Nc, n_tiles, m_tiles);
+                  })
+                : with_tile<32, 64, 128>(bm, [&](auto BM) {
+                      CNUDA_LAUNCH((igemm_fwd_classes_kernel<BM()>), grid, dim3(IG_THREADS), 0, st, set, Mp, C, Nc, n_tiles, m_tiles);
+                  });
+            CNUDA_REQUIRE(found, "cnuda_conv2d_backward_data: no parity-class kernel instance for a %d-row tile", bm);
             return check_launch("cnuda_conv2d_backward_data(classes)");
         }
         for (int ci = 0; ci < ncls; ++ci) {
@@ -1753,7 +1787,7 @@ extern "C" int cnuda_conv2d_backward_data_add(const float* grad_y, const float* 
                 const int Kpc = Kpcs[ci];
                 const int* taps = taps_all[ci];
                 const SplitK sc = buf_ok ? pick_splitk(C, Nc, Kpc) : SplitK();
-                const int bm = sc.on() ? sc.bm : pick_bm(C, Nc), Mp = round_up(C, bm);
+                const int bm = sc.on() ? sc.bm : conv_pick_bm(C, Nc), Mp = round_up(C, bm);
                 const size_t slab_bytes = splitk_slab_bytes(sc, C, Nc);
                 CNUDA_REQUIRE(carve_bytes(ig_a_bytes(Kpc, Mp), 1) + carve_bytes(slab_bytes, 1) + 256 <= workspace_bytes,
                               "cnuda_conv2d_backward_data: workspace");
@@ -1766,7 +1800,7 @@ extern "C" int cnuda_conv2d_backward_data_add(const float* grad_y, const float* 
         }
         return 0;
     }
-    if (!q.skd.on() && hconv_ok(g, Cout, q.bmd)) {   // (Co % 16 == 0: Kpd = 9 Co, no padded rows)
+    if (path == DgradPath::Halo) {
         const float* Ah = launch_pack(weight, Aws, ig_a_bytes(q.Kpd, q.Mpd), Cout, C, q.T, PACK_HALO_DGRAD, q.Kpd, q.Mpd, 0, st);
         ConvDgradParams ph{g, grad_y, grad_x, Cout, addend, addend2};
         return launch_hconv<HconvDgrad>(q.bmd, ph, grad_y, Cout, g, Ah, q.Mpd, q.Kpd, C, q.Nd, st, "cnuda_conv2d_backward_data");
@@ -1774,11 +1808,10 @@ extern "C" int cnuda_conv2d_backward_data_add(const float* grad_y, const float* 
     const float* A = launch_pack(weight, Aws, ig_a_bytes(q.Kpd, q.Mpd), Cout, C, q.T, PACK_DGRAD, q.Kpd, q.Mpd,
                                  round_up(Cout, IG_BK), st);
     ConvDgradParams p{g, grad_y, grad_x, round_up(Cout, IG_BK), addend, addend2};
-    if (buf_ok && sh == 1 && sw == 1) {
+    if (path == DgradPath::BufSplitK || path == DgradPath::Buf) {
         float* slab = q.skd.on() ? reinterpret_cast<float*>(cv.take<char>(splitk_slab_bytes(q.skd, C, q.Nd))) : nullptr;
         return launch_fwd<ConvDgradBufLoader>(q.bmd, p, A, q.Mpd, q.Kpd, C, q.Nd, st, "cnuda_conv2d_backward_data", q.skd, slab);
     }
-    CNUDA_REQUIRE(!q.skd.on(), "cnuda_conv2d_backward_data: split-K plan off the buffer-addressed path");
     return launch_fwd<ConvDgradLoader>(q.bmd, p, A, q.Mpd, q.Kpd, C, q.Nd, st, "cnuda_conv2d_backward_data");
 }
 
@@ -1789,95 +1822,66 @@ extern "C" int cnuda_conv2d_backward_weight(const float* x, const float* grad_y,
     CNUDA_REQUIRE(x && grad_y && grad_weight, "cnuda_conv2d_backward_weight: null pointer");
     ConvGeom g;
     if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_backward_weight")) return rc;
-    if (smallc_supported(C, Cout, kh, kw, sh, sw)) {
-        hipStream_t st0 = (hipStream_t)stream;
+    const ConvPlan q = make_plan(g);
+    hipStream_t st = (hipStream_t)stream;
+    if (q.wgrad == WgradPath::SmallC) {
         if (int rc = smallc_backward_weight(x, grad_y, grad_weight, B, C, H, W, Cout, kh, kw, sh, ph, pw, workspace,
-                                            workspace_bytes, st0))
+                                            workspace_bytes, st))
             return rc;
-        if (grad_bias) launch_channel_sum(grad_y, grad_bias, B, Cout, (long long)g.Ho * g.Wo, st0);
+        if (grad_bias) launch_channel_sum(grad_y, grad_bias, B, Cout, (long long)g.Ho * g.Wo, st);
         return check_launch("cnuda_conv2d_backward_weight(small)");
     }
-    const ConvPlan q = make_plan(g);
     CNUDA_REQUIRE(workspace && workspace_bytes >= q.wgrad_bytes, "cnuda_conv2d_backward_weight: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     Carver cv(workspace, workspace_bytes);
     float* slabs = cv.take<float>((size_t)q.Z * q.Mpw * q.Jp);
     // bias gradient: row sums of grad_y per split from the GEMM's own staging registers, summed with the slabs
     float* bsl = grad_bias ? cv.take<float>((size_t)q.Z * q.Mpw) : nullptr;
     ConvWParams p{g, x, grad_y};
-    if (q.hw_s2) {
-        ProfScope prof(st);
-        prof.name("hwgrad_s2_kernel");
-        const HwS2Params hp{x, grad_y, B, C, H, W, Cout, g.Ho, g.Wo, q.hw_tiles, q.hw_tiles_per_split};
-        const size_t lds = HS_LDS_FLOATS * sizeof(float);
-        CNUDA_REQUIRE(raise_dynamic_lds(reinterpret_cast<const void*>(&hwgrad_s2_kernel), lds),
-                      "cnuda_conv2d_backward_weight: dynamic LDS");
-        CNUDA_LAUNCH(hwgrad_s2_kernel, dim3(C / 16, q.Z, (Cout + 31) / 32), dim3(IG_THREADS), lds, st, hp, slabs, q.Mpw, q.Jp, bsl);
-    } else if (q.hw) {
-        ProfScope prof(st);
-        const int tw = halo_tile_width(W);
-        const bool side = tw < W;
-        prof.name(side ? "hwgrad_kernel<%d, side>" : "hwgrad_kernel<%d>", tw);
-        const HwParams hp{x, grad_y, B, C, H, W, Cout, W / tw, hwgrad_tiles_y(g), q.hw_tiles, q.hw_tiles_per_split};
-        const dim3 grid(C / 16, q.Z), blk(IG_THREADS);
-#define CNUDA_HWGRAD(TWV, SIDEV) do {                                                                                \
-        const size_t lds = HwShape<TWV, SIDEV>::lds_floats * sizeof(float);                                           \
-        CNUDA_REQUIRE(raise_dynamic_lds(reinterpret_cast<const void*>(&hwgrad_kernel<TWV, SIDEV>), lds),              \
-                      "cnuda_conv2d_backward_weight: dynamic LDS");                                                   \
-        CNUDA_LAUNCH((hwgrad_kernel<TWV, SIDEV>), grid, blk, lds, st, hp, slabs, q.Mpw, q.Jp, bsl);                   \
-    } while (0)
-        if (!side) {
-            if (tw == 128) CNUDA_HWGRAD(128, false); else if (tw == 64) CNUDA_HWGRAD(64, false);
-            else if (tw == 32) CNUDA_HWGRAD(32, false); else if (tw == 16) CNUDA_HWGRAD(16, false); else CNUDA_HWGRAD(8, false);
+    bool found = true, lds_ok = true;
+    {
+        ProfScope prof(st);       // (the main kernel alone: closed before the slab reduce)
+        if (q.wgrad == WgradPath::HaloS2) {
+            prof.name("hwgrad_s2_kernel");
+            const HwS2Params hp{x, grad_y, B, C, H, W, Cout, g.Ho, g.Wo, q.hw_tiles, q.hw_tiles_per_split};
+            const size_t lds = HS_LDS_FLOATS * sizeof(float);
+            lds_ok = raise_dynamic_lds(reinterpret_cast<const void*>(&hwgrad_s2_kernel), lds);
+            if (lds_ok)
+                CNUDA_LAUNCH(hwgrad_s2_kernel, dim3(C / 16, q.Z, (Cout + 31) / 32), dim3(IG_THREADS), lds, st, hp, slabs, q.Mpw, q.Jp, bsl);
+        } else if (q.wgrad == WgradPath::Halo) {
+            const int tw = halo_tile_width(W);
+            const bool side = tw < W;           // (tiles with neighbours in their row)
+            prof.name(side ? "hwgrad_kernel<%d, side>" : "hwgrad_kernel<%d>", tw);
+            const HwParams hp{x, grad_y, B, C, H, W, Cout, W / tw, hwgrad_tiles_y(g), q.hw_tiles, q.hw_tiles_per_split};
+            found = with_tiles<Tile<128, 0>, Tile<64, 0>, Tile<32, 0>, Tile<16, 0>, Tile<8, 0>,
+                               Tile<128, 1>, Tile<64, 1>, Tile<32, 1>, Tile<16, 1>, Tile<8, 1>>(tw, side ? 1 : 0, [&](auto TW, auto SIDE) {
+                constexpr bool kSide = SIDE() != 0;
+                const size_t lds = HwShape<TW(), kSide>::lds_floats * sizeof(float);
+                lds_ok = raise_dynamic_lds(reinterpret_cast<const void*>(&hwgrad_kernel<TW(), kSide>), lds);
+                if (lds_ok) CNUDA_LAUNCH((hwgrad_kernel<TW(), kSide>), dim3(C / 16, q.Z), dim3(IG_THREADS), lds, st, hp, slabs, q.Mpw, q.Jp, bsl);
+            });
         } else {
-            if (tw == 128) CNUDA_HWGRAD(128, true); else if (tw == 64) CNUDA_HWGRAD(64, true);
-            else if (tw == 32) CNUDA_HWGRAD(32, true); else if (tw == 16) CNUDA_HWGRAD(16, true); else CNUDA_HWGRAD(8, true);
-        }
-#undef CNUDA_HWGRAD
-    } else {
-        ProfScope prof(st);
-        const dim3 grid(q.Jp / q.wbj, q.Mpw / q.wbm, q.Z), blk(IG_THREADS);
-        const bool fast = C % 64 == 0;
-        const bool buf = fast && wgrad_buffer_ok(g);
-        const bool buf8 = !fast && C % 8 == 0 && wgrad_buffer_ok(g) && (q.wbm == 32 || (q.wbm == 64 && q.wbj == 64));
-        prof.name((wave_specialised() && fast && q.wbm >= 64) ? "igemm_wgrad_ws_kernel<%s, %d, %d>" : "igemm_wgrad_kernel<%s, %d, %d>",
-                  buf ? "ConvWBufLoader" : (buf8 ? "ConvWBufLoaderC8" : (fast ? "ConvWLoader<2>" : "ConvWLoader<0>")), q.wbm, q.wbj);
-        if (buf8) {
-            if (q.wbm == 32)
-                CNUDA_LAUNCH((igemm_wgrad_kernel<ConvWBufLoaderC8, 32, 128>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp,
-                                   q.Nf, q.pix_per_split, bsl);
-            else
-                CNUDA_LAUNCH((igemm_wgrad_kernel<ConvWBufLoaderC8, 64, 64>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp,
-                                   q.Nf, q.pix_per_split, bsl);
-        } else if (buf) {
-            launch_wgrad_buf<ConvWBufLoader>(q, p, grid, slabs, bsl, st);
-        } else if (wave_specialised() && fast && q.wbm == 64) {
-            const dim3 blk2(2 * IG_THREADS);
-            if (q.wbj == 128)
-                CNUDA_LAUNCH((igemm_wgrad_ws_kernel<ConvWLoader<2>, 64, 128>), grid, blk2, 0, st, p, slabs, q.Mpw,
-                                   q.Jp, q.Nf, q.pix_per_split, bsl);
-            else
-                CNUDA_LAUNCH((igemm_wgrad_ws_kernel<ConvWLoader<2>, 64, 64>), grid, blk2, 0, st, p, slabs, q.Mpw,
-                                   q.Jp, q.Nf, q.pix_per_split, bsl);
-        } else if (q.wbm == 64) {
-            if (fast && q.wbj == 128)
-                CNUDA_LAUNCH((igemm_wgrad_kernel<ConvWLoader<2>, 64, 128>), grid, blk, 0, st, p, slabs, q.Mpw,
-                                   q.Jp, q.Nf, q.pix_per_split, bsl);
-            else if (fast)
-                CNUDA_LAUNCH((igemm_wgrad_kernel<ConvWLoader<2>, 64, 64>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp,
-                                   q.Nf, q.pix_per_split, bsl);
-            else
-                CNUDA_LAUNCH((igemm_wgrad_kernel<ConvWLoader<0>, 64, 64>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp,
-                                   q.Nf, q.pix_per_split, bsl);
-        } else {
-            if (fast)
-                CNUDA_LAUNCH((igemm_wgrad_kernel<ConvWLoader<2>, 32, 128>), grid, blk, 0, st, p, slabs, q.Mpw,
-                                   q.Jp, q.Nf, q.pix_per_split, bsl);
-            else
-                CNUDA_LAUNCH((igemm_wgrad_kernel<ConvWLoader<0>, 32, 128>), grid, blk, 0, st, p, slabs, q.Mpw,
-                                   q.Jp, q.Nf, q.pix_per_split, bsl);
+            prof.name(q.wgrad_ws ? "igemm_wgrad_ws_kernel<%s, %d, %d>" : "igemm_wgrad_kernel<%s, %d, %d>", wgrad_loader_name(q.wgrad),
+                      q.wbm, q.wbj);
+            switch (q.wgrad) {
+                case WgradPath::BufC8:
+                    found = launch_wgrad<ConvWBufLoaderC8, false, Tile<32, 128>, Tile<64, 64>>(q, p, slabs, bsl, st);
+                    break;
+                case WgradPath::Buf:
+                    found = launch_wgrad_buf<ConvWBufLoader>(q, p, slabs, bsl, st);
+                    break;
+                case WgradPath::PtrFastWs:
+                    found = launch_wgrad<ConvWLoader<2>, true, Tile<64, 128>, Tile<64, 64>>(q, p, slabs, bsl, st);
+                    break;
+                case WgradPath::PtrFast:
+                    found = launch_wgrad<ConvWLoader<2>, false, Tile<64, 128>, Tile<64, 64>, Tile<32, 128>>(q, p, slabs, bsl, st);
+                    break;
+                default:
+                    found = launch_wgrad<ConvWLoader<0>, false, Tile<64, 64>, Tile<32, 128>>(q, p, slabs, bsl, st);
+            }
         }
     }
+    CNUDA_REQUIRE(lds_ok, "cnuda_conv2d_backward_weight: dynamic LDS");
+    CNUDA_REQUIRE(found, "cnuda_conv2d_backward_weight: no kernel instance for this tile (%d x %d)", q.wbm, q.wbj);
     if (int rc = check_launch("cnuda_conv2d_backward_weight")) return rc;
     launch_slab_reduce(slabs, grad_weight, q.Z, q.Mpw, q.Jp, Cout, C, q.T, st, bsl, grad_bias);
     return check_launch("cnuda_conv2d_backward_weight(reduce)");

@@ -1553,10 +1553,13 @@ int fill_geom(DcnGeom& g, int B, int C, int H, int W, int Co, int kh, int kw, in
     return 0;
 }
 
-int pick_bm(int M, long long N) {
+// largest row tile that still leaves two workgroups per CU.  (conv.hip's conv_pick_bm lets the 64-row tile stay with one:
+// that relaxation was measured on the dense convolutions only, the sampling loaders keep the flat threshold)
+constexpr int kDcnMinTiles = 512;
+int dcn_pick_bm(int M, long long N) {
     int bm = M > 64 ? 128 : (M > 32 ? 64 : 32);
     const long long n_tiles = (N + IG_BN - 1) / IG_BN;
-    while (bm > 32 && n_tiles * ((M + bm - 1) / bm) < 512) bm >>= 1;
+    while (bm > 32 && n_tiles * ((M + bm - 1) / bm) < kDcnMinTiles) bm >>= 1;
     return bm;
 }
 
@@ -1575,7 +1578,39 @@ int g_walk_tc = 0;                                  // cnuda_dcn_set_walk_tile (
 int g_offset_regime = 0;
 
 
+// the LDS-window kernel's layers: 3x3 / stride 1 / padding 1 / dilation 1, row width a multiple of 16, one M tile.  CNUDA_DCNW=0
+// keeps the gathering loader (A/B measurements; tests/test_gpu_kernel_switches.py).
+// (round 6: any row width that is a multiple of 16 -- 160 / 80 / 96 -- in whole tiles of 4 x 32 or 8 x 16 pixels; rounds 4-5:
+// 16 / 32 / 64 / 128 only)
+int dcnw_tile_cols(int W) { return W % 32 == 0 ? 32 : 16; }
+bool dcnw_takes(const DcnGeom& g) {
+    static const bool dcnw_on = !(getenv("CNUDA_DCNW") && getenv("CNUDA_DCNW")[0] == '0');
+    return dcnw_on && (g_offset_regime & 2) == 0 && matrix_mode() == 0 && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 &&
+           g.dh == 1 && g.dw == 1 && g.dg == 1 && g.C % 16 == 0 && g.Co <= 64 &&
+           g.W % 16 == 0 && g.H % (IG_BN / dcnw_tile_cols(g.W)) == 0 &&
+           (size_t)g.B * g.C * g.H * g.W * sizeof(float) < IG_BUF_OOB;
+}
+
+#ifndef DCN_COLS_WS
+#define DCN_COLS_WS 1
+#endif
+#ifndef DCN_COLW_WS
+#define DCN_COLW_WS 1
+#endif
+// Which kernels a call of this geometry takes -- decided once, in make_plan (as ConvPlan's paths, conv.hip):
+//   Naive           one thread per output element (width 1)
+//   Composed        deformable_group > 1: a deformable_group = 1 call per group (which plans for itself)
+//   Window          dcnw_fwd_kernel: the LDS-window kernel
+//   SampleThenGemm  several row tiles: dcn_sample_kernel writes the columns once, a plain GEMM reads them
+//   Gather          the implicit GEMM whose loader samples
+enum class DcnFwdPath { Naive, Composed, Window, SampleThenGemm, Gather };
 struct DcnPlan {
+    DcnFwdPath fwd;
+    bool fwd_buf;                   // SampleThenGemm / Gather: the buffer-addressed loader
+    bool fwd_ws;                    // SampleThenGemm: the GEMM's wave-specialised instance
+    bool colw_buf, colw_ws;         // weight gradient from saved columns: buffer-addressed loader, wave-specialised instance
+    int wbj;                        // ... and its column tile (rows: WG_BM)
+    bool dcol_quads;                // column gradient with its rows interleaved in quads (both consumers read 16 bytes)
     int T, K, Kp, bm, Mp;           // forward pack [Kp][Mp]
     int Mpw, Jp, Z;                 // wgrad slabs [Z][Mpw][Jp]
     long long N, pix_per_split;
@@ -1594,15 +1629,15 @@ DcnPlan make_plan(const DcnGeom& g) {
     q.K = q.T * g.C;
     q.Kp = round_up(q.K, IG_KC);
     q.N = (long long)g.B * g.Ho * g.Wo;
-    q.bm = pick_bm(g.Co, q.N);
+    q.bm = dcn_pick_bm(g.Co, q.N);
     q.Mp = round_up(g.Co, q.bm);
     q.Mpw = round_up(g.Co, WG_BM);
     q.Jp = round_up(q.K, WG_BJ);
     q.N = (long long)g.B * g.Ho * g.Wo;
     // enough pixel splits to fill the chip (>= ~1024 workgroups), each a multiple of the chunk
-    const int wbj = q.Jp % 128 == 0 ? 128 : WG_BJ;     // (the launch below picks the 64 x 128 tile the same way)
-    const long long tiles = (long long)(q.Mpw / WG_BM) * (q.Jp / wbj);
-    const long long z = wgrad_splits(tiles, WG_BM, wbj, (q.N + WG_BP - 1) / WG_BP);
+    q.wbj = q.Jp % 128 == 0 ? 128 : WG_BJ;             // (of the saved-columns loaders; the sampling loader has 64 x 64 alone)
+    const long long tiles = (long long)(q.Mpw / WG_BM) * (q.Jp / q.wbj);
+    const long long z = wgrad_splits(tiles, WG_BM, q.wbj, (q.N + WG_BP - 1) / WG_BP);
     q.pix_per_split = ((q.N + z - 1) / z + WG_BP - 1) / WG_BP * WG_BP;
     q.Z = (int)((q.N + q.pix_per_split - 1) / q.pix_per_split);
     q.fwd_two_kernels = q.Mp / q.bm > 1;
@@ -1644,7 +1679,53 @@ DcnPlan make_plan(const DcnGeom& g) {
     q.fused_consumers = q.WSZmax > 0 && g.W >= 2 && (long long)g.B * q.tiles_y * q.tiles_x >= g_fused_min_tiles;
     q.fused_split = 4;     // measured 1..4 on the 128 x 128 / 64 x 64 layers: 1116/1077/1093/1064 and 716/645/611/584 us
     if (q.fused_split > q.ncg) q.fused_split = q.ncg;
+
+    const size_t HoWo = (size_t)g.Ho * g.Wo;
+    q.fwd = (g.dg > 1 && g.W >= 2) ? DcnFwdPath::Composed
+          : (g.dg != 1 || g.W < 2) ? DcnFwdPath::Naive          // (the MFMA paths sample horizontally adjacent pairs)
+          : dcnw_takes(g) ? DcnFwdPath::Window
+          : q.fwd_two_kernels ? DcnFwdPath::SampleThenGemm : DcnFwdPath::Gather;
+    q.fwd_buf = buffer_addressing() && g.C % IG_BK == 0 && (size_t)g.B * g.C * g.H * g.W * sizeof(float) < IG_BUF_OOB &&
+                (size_t)g.B * q.K * HoWo * sizeof(float) < IG_BUF_OOB;
+    // (a plain GEMM over coalesced rows: the 8-wave producer / consumer kernel of the dense convolutions takes it)
+    q.fwd_ws = DCN_COLS_WS && q.fwd_buf && q.bm >= 64 && wave_specialised() && matrix_mode() == 0;
+    q.colw_buf = buffer_addressing() && (size_t)g.B * q.K * HoWo * sizeof(float) < IG_BUF_OOB &&
+                 (size_t)g.B * g.Co * HoWo * sizeof(float) < IG_BUF_OOB && HoWo < (1 << 23);
+    // (plain row reads of the saved columns: the same 8-wave kernel)
+    q.colw_ws = DCN_COLW_WS && q.colw_buf && wave_specialised() && matrix_mode() == 0;
+    // (round 6) rows interleaved in quads where the GEMM has that epilogue: one 16-byte load per (pixel, tap, 4 channels)
+    // in both consumers
+    static const bool quads_on = !(getenv("CNUDA_DCOL_QUADS") && getenv("CNUDA_DCOL_QUADS")[0] == '0');
+    q.dcol_quads = quads_on && g.C % 4 == 0 && HoWo < (1 << 26) &&
+                   cnuda_conv2d_rowquads_supported(g.B, g.Co, g.Ho, g.Wo, q.T * g.C, 1, 1, 1, 1, 0, 0);
     return q;
+}
+
+// the GEMM behind a sampling / column loader: row tiles 32 / 64 / 128; WS (DcnColsBufLoader alone has such instances)
+// the wave-specialised kernel of the 64- and 128-row tiles.  false: no instance for q.bm
+template <class Loader, bool WS = false, class P>
+bool launch_dcn_fwd(const DcnPlan& q, const P& p, const float* A, int Cout, hipStream_t st) {
+    const int n_tiles = ceil_div(q.N, IG_BN), m_tiles = q.Mp / q.bm;
+    const dim3 grid(n_tiles * m_tiles);
+    if constexpr (WS)
+        return with_tile<64, 128>(q.bm, [&](auto BM) {
+            CNUDA_LAUNCH((igemm_fwd_ws_kernel<BM(), Loader>), grid, dim3(2 * IG_THREADS), 0, st, p, A, q.Mp, q.Kp, Cout, q.N, n_tiles, m_tiles);
+        });
+    else
+        return with_tile<32, 64, 128>(q.bm, [&](auto BM) {
+            CNUDA_LAUNCH((igemm_fwd_kernel<BM(), Loader>), grid, dim3(IG_THREADS), 0, st, p, A, q.Mp, q.Kp, Cout, q.N, n_tiles, m_tiles);
+        });
+}
+// the weight-gradient GEMM of one loader on the 64-row tile: BJS lists its column tiles
+template <class Loader, bool WS, int... BJS, class P>
+bool launch_dcn_wgrad(const DcnPlan& q, int bj, const P& p, float* slabs, float* bsl, hipStream_t st) {
+    const dim3 grid(q.Jp / bj, q.Mpw / WG_BM, q.Z), blk((WS ? 2 : 1) * IG_THREADS);
+    return with_tile<BJS...>(bj, [&](auto BJ) {
+        if constexpr (WS)
+            CNUDA_LAUNCH((igemm_wgrad_ws_kernel<Loader, 64, BJ()>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
+        else
+            CNUDA_LAUNCH((igemm_wgrad_kernel<Loader, 64, BJ()>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
+    });
 }
 
 }  // namespace
@@ -1713,13 +1794,13 @@ extern "C" size_t cnuda_dcn_v2_workspace_bytes(int B, int C, int H, int W, int C
                                                int ph, int pw, int dh, int dw, int dg) {
     DcnGeom g;
     if (fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_workspace_bytes")) return 0;
-    if (dg > 1 && W >= 2) {     // the composed path: group copies of input / weights and their gradients, one output, the inner call's
+    const DcnPlan q = make_plan(g);
+    if (q.fwd == DcnFwdPath::Composed) {     // group copies of input / weights and their gradients, one output, the inner call's
         const int Cg = C / dg, T = kh * kw;
         const size_t inner = cnuda_dcn_v2_workspace_bytes(B, Cg, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, 1);
         return 2 * carve_bytes((size_t)B * Cg * H * W, 4) + 2 * carve_bytes((size_t)Cout * Cg * T, 4) +
                carve_bytes((size_t)B * Cout * g.Ho * g.Wo, 4) + 2 * carve_bytes((size_t)Cout, 4) + carve_bytes(inner, 1) + 512;
     }
-    const DcnPlan q = make_plan(g);
     return q.fwd_bytes > q.bwd_bytes ? q.fwd_bytes : q.bwd_bytes;
 }
 
@@ -1740,30 +1821,15 @@ extern "C" int cnuda_dcn_v2_forward_cols(const float* input, const float* weight
                                     sh, sw, ph, pw, dh, dw, dg, workspace, workspace_bytes, stream);
 }
 
-namespace {
-// the LDS-window kernel's layers: 3x3 / stride 1 / padding 1 / dilation 1, row width a multiple of 16, one M tile.  CNUDA_DCNW=0
-// keeps the gathering loader (A/B measurements; tests/test_gpu_kernel_switches.py).
-// (round 6: any row width that is a multiple of 16 -- 160 / 80 / 96 -- in whole tiles of 4 x 32 or 8 x 16 pixels; rounds 4-5:
-// 16 / 32 / 64 / 128 only)
-int dcnw_tile_cols(int W) { return W % 32 == 0 ? 32 : 16; }
-bool dcnw_takes(const DcnGeom& g) {
-    static const bool dcnw_on = !(getenv("CNUDA_DCNW") && getenv("CNUDA_DCNW")[0] == '0');
-    return dcnw_on && (g_offset_regime & 2) == 0 && matrix_mode() == 0 && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 &&
-           g.dh == 1 && g.dw == 1 && g.dg == 1 && g.C % 16 == 0 && g.Co <= 64 &&
-           g.W % 16 == 0 && g.H % (IG_BN / dcnw_tile_cols(g.W)) == 0 &&
-           (size_t)g.B * g.C * g.H * g.W * sizeof(float) < IG_BUF_OOB;
-}
-}  // namespace
-
 // Pixel blocks of the BatchNorm statistics a forward call of this geometry can leave (cnuda_dcn_v2_forward_stats): 0 none
 // (deformable_group > 1, width 1, planes that are no multiple of four pixels), else pixels per block; *rows = rows per block.
 extern "C" int cnuda_dcn_v2_stats_block(int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                                         int dh, int dw, int dg, int* rows) {
     DcnGeom g;
     if (fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_stats_block")) return 0;
-    if (dg != 1 || W < 2 || ((g.Ho * g.Wo) & 3) != 0) return 0;
-    if (dcnw_takes(g)) { if (rows) *rows = 64; return 32; }
     const DcnPlan q = make_plan(g);
+    if (q.fwd == DcnFwdPath::Naive || q.fwd == DcnFwdPath::Composed || ((g.Ho * g.Wo) & 3) != 0) return 0;
+    if (q.fwd == DcnFwdPath::Window) { if (rows) *rows = 64; return 32; }
     if (rows) *rows = q.Mp;
     return q.bm == 32 ? 32 : 64;
 }
@@ -1823,7 +1889,8 @@ static int dcn_forward_impl(const float* input, const float* weight, const float
     if (strides && strides->mask_bs) g.mask_bs = strides->mask_bs;
     hipStream_t st = (hipStream_t)stream;
     CNUDA_REQUIRE(act_slope < 0.0f || (dg == 1 && W >= 2), "cnuda_dcn_v2_forward_act: fused activation needs deformable_group == 1 and width >= 2");
-    if (dg > 1 && W >= 2) {
+    const DcnPlan q = make_plan(g);
+    if (q.fwd == DcnFwdPath::Composed) {
         // deformable_group > 1 (libs/DCNv2/dcn_v2.py:54-94 accepts any; testcpu.py:169-180 uses 2), round 6: the output is the sum
         // over the groups of a deformable_group = 1 convolution of the group's C / dg input channels with its own offsets and
         // mask -- the fast kernels run per group on a contiguous copy of the group's channels and weights, offsets / mask are
@@ -1858,47 +1925,39 @@ static int dcn_forward_impl(const float* input, const float* weight, const float
         }
         return check_launch("cnuda_dcn_v2_forward(dg>1)");
     }
-    if (dg != 1 || W < 2) {   // the MFMA path samples horizontally adjacent pairs
+    if (q.fwd == DcnFwdPath::Naive) {
         DcnNaiveParams p{g, input, weight, bias, offset, mask, nullptr, output, nullptr, nullptr, nullptr, nullptr};
         CNUDA_LAUNCH(dcn_naive_fwd_kernel, dim3(stream_grid((long long)B * Cout * g.Ho * g.Wo, 256)), dim3(256),
                            0, st, p);
         return check_launch("cnuda_dcn_v2_forward(dg>1)");
     }
-    const DcnPlan q = make_plan(g);
     CNUDA_REQUIRE(q.N < (1ll << 31) - IG_BN, "cnuda_dcn_v2_forward: more than 2^31 pixels per call");
     CNUDA_REQUIRE(workspace && workspace_bytes >= q.fwd_bytes, "cnuda_dcn_v2_forward: workspace too small");
     Carver cv(workspace, workspace_bytes);
-    if (dcnw_takes(g)) {
+    if (q.fwd == DcnFwdPath::Window) {
         const int bm = 64;
         const float* Aw = launch_pack(weight, cv.take<float>((size_t)q.Kp * bm), (size_t)q.Kp * bm * sizeof(float), Cout, C,
                                       q.T, PACK_HALO_FWD, q.Kp, bm, 0, st);
         DcnFwdParams p{g, input, offset, mask, bias, act_slope, output, columns, stats, 64};
         ProfScope prof(st);
         prof.name("dcnw_fwd_kernel<%d>%s", bm, columns ? " (+ column side output)" : "");
-        const int tc = dcnw_tile_cols(W), tiles_x = W / tc, n_tiles = (int)(q.N / IG_BN);
-#define CNUDA_DCNW_LAUNCH(BMV, TCV)                                                                                    \
-    do {                                                                                                               \
-        const size_t fl = dcnw_lds_floats<TCV>(BMV);                                                                   \
-        const size_t lds = (fl < (size_t)4 * IG_EPI_WAVE ? (size_t)4 * IG_EPI_WAVE : fl) * sizeof(float);             \
-        CNUDA_REQUIRE(raise_dynamic_lds(reinterpret_cast<const void*>(&dcnw_fwd_kernel<BMV, TCV>), lds),               \
-                      "cnuda_dcn_v2_forward: dynamic LDS");                                                            \
-        CNUDA_LAUNCH((dcnw_fwd_kernel<BMV, TCV>), dim3(n_tiles), dim3(IG_THREADS), lds, st, p, Aw, bm, q.Kp, n_tiles,  \
-                     tiles_x);                                                                                         \
-    } while (0)
+        const int tiles_x = W / dcnw_tile_cols(W), n_tiles = (int)(q.N / IG_BN);
         // (a 128-row variant -- four accumulator tiles per wave -- spills and measured slower than the gathering
         // loader's 128-row tile, 571 vs 452 us at 128 -> 128, 64 x 64, B = 32: layers with more than 64 outputs stay there)
-        if (tc == 32) CNUDA_DCNW_LAUNCH(64, 32); else CNUDA_DCNW_LAUNCH(64, 16);
-#undef CNUDA_DCNW_LAUNCH
+        bool lds_ok = true;
+        const bool found = with_tiles<Tile<64, 32>, Tile<64, 16>>(bm, dcnw_tile_cols(W), [&](auto BM, auto TC) {
+            const size_t fl = dcnw_lds_floats<TC()>(BM());
+            const size_t lds = (fl < (size_t)4 * IG_EPI_WAVE ? (size_t)4 * IG_EPI_WAVE : fl) * sizeof(float);
+            lds_ok = raise_dynamic_lds(reinterpret_cast<const void*>(&dcnw_fwd_kernel<BM(), TC()>), lds);
+            if (lds_ok) CNUDA_LAUNCH((dcnw_fwd_kernel<BM(), TC()>), dim3(n_tiles), dim3(IG_THREADS), lds, st, p, Aw, bm, q.Kp, n_tiles, tiles_x);
+        });
+        CNUDA_REQUIRE(lds_ok, "cnuda_dcn_v2_forward: dynamic LDS");
+        CNUDA_REQUIRE(found, "cnuda_dcn_v2_forward: no dcnw_fwd_kernel instance for %d-column tiles", dcnw_tile_cols(W));
         return check_launch("cnuda_dcn_v2_forward(window)");
     }
     const float* A = launch_pack(weight, cv.take<float>((size_t)q.Kp * q.Mp), (size_t)q.Kp * q.Mp * sizeof(float), Cout,
                                  C, q.T, PACK_FWD, q.Kp, q.Mp, 0, st);
-    const int n_tiles = ceil_div(q.N, IG_BN), m_tiles = q.Mp / q.bm;
-    const dim3 grid(n_tiles * m_tiles), block(IG_THREADS);
-    static const bool buf_on = !(getenv("CNUDA_BUF") && getenv("CNUDA_BUF")[0] == '0');
-    const bool buf = buf_on && C % IG_BK == 0 && (size_t)B * C * H * W * sizeof(float) < IG_BUF_OOB &&
-                     (size_t)B * q.K * g.Ho * g.Wo * sizeof(float) < IG_BUF_OOB;
-    if (q.fwd_two_kernels) {
+    if (q.fwd == DcnFwdPath::SampleThenGemm) {
         float* cols = columns ? columns : cv.take<float>((size_t)B * q.K * g.Ho * g.Wo);
         ProfScope prof(st);   // brackets both kernels
         prof.name("dcn_sample_kernel + igemm_fwd_kernel<%d, DcnColsLoader>", q.bm);
@@ -1908,57 +1967,17 @@ static int dcn_forward_impl(const float* input, const float* weight, const float
             CNUDA_LAUNCH(dcn_sample_kernel, dim3(B * tiles), dim3(64, tw), 0, st, sp, tiles);
         }
         DcnColsParams p{g, cols, bias, act_slope, output, stats, q.Mp};
-#ifndef DCN_COLS_WS
-#define DCN_COLS_WS 1
-#endif
-        // (a plain GEMM over coalesced rows: the 8-wave producer / consumer kernel of the dense convolutions takes it)
-        if (DCN_COLS_WS && buf && q.bm == 128 && wave_specialised() && matrix_mode() == 0)
-            CNUDA_LAUNCH((igemm_fwd_ws_kernel<128, DcnColsBufLoader>), grid, dim3(2 * IG_THREADS), 0, st, p, A, q.Mp, q.Kp, Cout,
-                               q.N, n_tiles, m_tiles);
-        else if (DCN_COLS_WS && buf && q.bm == 64 && wave_specialised() && matrix_mode() == 0)
-            CNUDA_LAUNCH((igemm_fwd_ws_kernel<64, DcnColsBufLoader>), grid, dim3(2 * IG_THREADS), 0, st, p, A, q.Mp, q.Kp, Cout,
-                               q.N, n_tiles, m_tiles);
-        else if (buf && q.bm == 128)
-            CNUDA_LAUNCH((igemm_fwd_kernel<128, DcnColsBufLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                               n_tiles, m_tiles);
-        else if (buf && q.bm == 64)
-            CNUDA_LAUNCH((igemm_fwd_kernel<64, DcnColsBufLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                               n_tiles, m_tiles);
-        else if (buf)
-            CNUDA_LAUNCH((igemm_fwd_kernel<32, DcnColsBufLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                               n_tiles, m_tiles);
-        else if (q.bm == 128)
-            CNUDA_LAUNCH((igemm_fwd_kernel<128, DcnColsLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                               n_tiles, m_tiles);
-        else if (q.bm == 64)
-            CNUDA_LAUNCH((igemm_fwd_kernel<64, DcnColsLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                               n_tiles, m_tiles);
-        else
-            CNUDA_LAUNCH((igemm_fwd_kernel<32, DcnColsLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                               n_tiles, m_tiles);
+        const bool found = q.fwd_ws    ? launch_dcn_fwd<DcnColsBufLoader, true>(q, p, A, Cout, st)
+                           : q.fwd_buf ? launch_dcn_fwd<DcnColsBufLoader>(q, p, A, Cout, st)
+                                       : launch_dcn_fwd<DcnColsLoader>(q, p, A, Cout, st);
+        CNUDA_REQUIRE(found, "cnuda_dcn_v2_forward: no GEMM instance for a %d-row tile", q.bm);
         return check_launch("cnuda_dcn_v2_forward(columns + GEMM)");
     }
     DcnFwdParams p{g, input, offset, mask, bias, act_slope, output, columns, stats, q.Mp};
     ProfScope prof(st);
     prof.name("igemm_fwd_kernel<%d, DcnFwdLoader>%s", q.bm, columns ? " (+ column side output)" : "");
-    if (buf && q.bm == 128)
-        CNUDA_LAUNCH((igemm_fwd_kernel<128, DcnFwdBufLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                           n_tiles, m_tiles);
-    else if (buf && q.bm == 64)
-        CNUDA_LAUNCH((igemm_fwd_kernel<64, DcnFwdBufLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                           n_tiles, m_tiles);
-    else if (buf)
-        CNUDA_LAUNCH((igemm_fwd_kernel<32, DcnFwdBufLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                           n_tiles, m_tiles);
-    else if (q.bm == 128)
-        CNUDA_LAUNCH((igemm_fwd_kernel<128, DcnFwdLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                           n_tiles, m_tiles);
-    else if (q.bm == 64)
-        CNUDA_LAUNCH((igemm_fwd_kernel<64, DcnFwdLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                           n_tiles, m_tiles);
-    else
-        CNUDA_LAUNCH((igemm_fwd_kernel<32, DcnFwdLoader>), grid, block, 0, st, p, A, q.Mp, q.Kp, Cout, q.N,
-                           n_tiles, m_tiles);
+    const bool found = q.fwd_buf ? launch_dcn_fwd<DcnFwdBufLoader>(q, p, A, Cout, st) : launch_dcn_fwd<DcnFwdLoader>(q, p, A, Cout, st);
+    CNUDA_REQUIRE(found, "cnuda_dcn_v2_forward: no GEMM instance for a %d-row tile", q.bm);
     return check_launch("cnuda_dcn_v2_forward");
 }
 
@@ -2070,7 +2089,8 @@ static int dcn_backward_impl(const float* input, const float* weight, const floa
     }
     hipStream_t st = (hipStream_t)stream;
     const int T = kh * kw, HoWo = g.Ho * g.Wo;
-    if (dg > 1 && W >= 2) {
+    const DcnPlan q = make_plan(g);
+    if (q.fwd == DcnFwdPath::Composed) {
         // deformable_group > 1, composed from the deformable_group = 1 kernels (see dcn_forward_impl): per group the data
         // gradient of its C / dg input channels, its rows of grad_offset / grad_mask (written in place through the batch strides
         // of the dg-group tensors) and its slice of grad_weight; grad_bias by the first group's call
@@ -2124,7 +2144,6 @@ static int dcn_backward_impl(const float* input, const float* weight, const floa
                            p);
         return check_launch("cnuda_dcn_v2_backward(dg>1)");
     }
-    const DcnPlan q = make_plan(g);
     CNUDA_REQUIRE(workspace && workspace_bytes >= q.bwd_bytes, "cnuda_dcn_v2_backward: workspace too small");
     Carver cv(workspace, workspace_bytes);
     float* slabs = cv.take<float>((size_t)q.Z * q.Mpw * q.Jp);
@@ -2141,48 +2160,23 @@ static int dcn_backward_impl(const float* input, const float* weight, const floa
     ProfGroup prof;
     // (2) weight gradient (and, from the same staging registers, the bias gradient: bsl -> slab reduce)
     {
+      bool found;
       {
         ProfScope wscope(st, 4);
         if (columns) {
             DcnColWParams p{g, columns, grad_output};
-            static const bool buf_on = !(getenv("CNUDA_BUF") && getenv("CNUDA_BUF")[0] == '0');
-            const bool buf = buf_on && (size_t)B * q.T * C * HoWo * sizeof(float) < IG_BUF_OOB &&
-                             (size_t)B * Cout * HoWo * sizeof(float) < IG_BUF_OOB && HoWo < (1 << 23);
-#ifndef DCN_COLW_WS
-#define DCN_COLW_WS 1
-#endif
-            // (plain row reads of the saved columns: the 8-wave producer / consumer kernel of the dense convolutions takes them)
-            const bool ws = DCN_COLW_WS && wave_specialised() && matrix_mode() == 0;
-            wscope.name(ws && buf ? "igemm_wgrad_ws_kernel<%s, 64, %d>" : "igemm_wgrad_kernel<%s, 64, %d>",
-                        buf ? "DcnColWBufLoader" : "DcnColWLoader", q.Jp % 128 == 0 ? 128 : 64);
-            if (buf && q.Jp % 128 == 0) {
-                if (ws)
-                    CNUDA_LAUNCH((igemm_wgrad_ws_kernel<DcnColWBufLoader, 64, 128>), dim3(q.Jp / 128, q.Mpw / WG_BM, q.Z),
-                                       dim3(2 * IG_THREADS), 0, wst, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
-                else
-                    CNUDA_LAUNCH((igemm_wgrad_kernel<DcnColWBufLoader, 64, 128>), dim3(q.Jp / 128, q.Mpw / WG_BM, q.Z),
-                                       dim3(IG_THREADS), 0, wst, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
-            } else if (buf) {
-                if (ws)
-                    CNUDA_LAUNCH((igemm_wgrad_ws_kernel<DcnColWBufLoader, 64, 64>), dim3(q.Jp / WG_BJ, q.Mpw / WG_BM, q.Z),
-                                       dim3(2 * IG_THREADS), 0, wst, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
-                else
-                    CNUDA_LAUNCH((igemm_wgrad_kernel<DcnColWBufLoader, 64, 64>), dim3(q.Jp / WG_BJ, q.Mpw / WG_BM, q.Z),
-                                       dim3(IG_THREADS), 0, wst, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
-            }
-            else if (q.Jp % 128 == 0)
-                CNUDA_LAUNCH((igemm_wgrad_kernel<DcnColWLoader, 64, 128>), dim3(q.Jp / 128, q.Mpw / WG_BM, q.Z),
-                                   dim3(IG_THREADS), 0, wst, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
-            else
-                CNUDA_LAUNCH((igemm_wgrad_kernel<DcnColWLoader, 64, 64>), dim3(q.Jp / WG_BJ, q.Mpw / WG_BM, q.Z),
-                                   dim3(IG_THREADS), 0, wst, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
+            wscope.name(q.colw_ws ? "igemm_wgrad_ws_kernel<%s, 64, %d>" : "igemm_wgrad_kernel<%s, 64, %d>",
+                        q.colw_buf ? "DcnColWBufLoader" : "DcnColWLoader", q.wbj);
+            found = q.colw_ws    ? launch_dcn_wgrad<DcnColWBufLoader, true, 64, 128>(q, q.wbj, p, slabs, bsl, wst)
+                    : q.colw_buf ? launch_dcn_wgrad<DcnColWBufLoader, false, 64, 128>(q, q.wbj, p, slabs, bsl, wst)
+                                 : launch_dcn_wgrad<DcnColWLoader, false, 64, 128>(q, q.wbj, p, slabs, bsl, wst);
         } else {
             DcnWParams p{g, input, offset, mask, grad_output};
             wscope.name("igemm_wgrad_kernel<DcnWLoader, 64, 64>");
-            CNUDA_LAUNCH((igemm_wgrad_kernel<DcnWLoader, 64, 64>), dim3(q.Jp / WG_BJ, q.Mpw / WG_BM, q.Z),
-                               dim3(IG_THREADS), 0, wst, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
+            found = launch_dcn_wgrad<DcnWLoader, false, 64>(q, WG_BJ, p, slabs, bsl, wst);
         }
       }
+        CNUDA_REQUIRE(found, "cnuda_dcn_v2_backward: no weight-gradient instance for %d-column tiles", q.wbj);
         if (int rc = check_launch("cnuda_dcn_v2_backward(weight)")) return rc;
         launch_slab_reduce(slabs, grad_weight, q.Z, q.Mpw, q.Jp, Cout, C, q.T, wst, bsl, grad_bias);
     }
@@ -2197,11 +2191,7 @@ static int dcn_backward_impl(const float* input, const float* weight, const floa
                              zero_in_prep ? grad_input : nullptr, gin_elems / 4, wt_blocks + geo_blocks};
             CNUDA_LAUNCH(dcn_prep_kernel, dim3(wt_blocks + geo_blocks + zero_blocks), dim3(256), 0, st, pp);
         }
-        // (round 6) rows interleaved in quads where the GEMM has that epilogue: one 16-byte load per (pixel, tap, 4 channels)
-        // in both consumers
-        static const bool quads_on = !(getenv("CNUDA_DCOL_QUADS") && getenv("CNUDA_DCOL_QUADS")[0] == '0');
-        const bool quads = quads_on && C % 4 == 0 && HoWo < (1 << 26) &&
-                           cnuda_conv2d_rowquads_supported(B, Cout, g.Ho, g.Wo, q.T * C, 1, 1, 1, 1, 0, 0);
+        const bool quads = q.dcol_quads;
         if (int rc = quads ? cnuda_conv2d_forward_rowquads(grad_output, wt, dcol, B, Cout, g.Ho, g.Wo, q.T * C, 1, 1, 1, 1, 0, 0,
                                                            gemm_ws, q.gemm_bytes, stream)
                            : cnuda_conv2d_forward(grad_output, wt, nullptr, dcol, B, Cout, g.Ho, g.Wo, q.T * C, 1, 1, 1, 1, 0,

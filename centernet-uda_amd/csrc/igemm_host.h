@@ -3,6 +3,8 @@
 #pragma once
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace cnuda {
@@ -19,6 +21,27 @@ enum PackMode {
 };
 
 inline int round_up(int v, int q) { return (v + q - 1) / q * q; }
+
+// A runtime tile size as a compile-time one: with_tile<32, 64, 128>(bm, [&](auto BM) { ... kernel<BM()> ... }) calls the
+// lambda with std::integral_constant<int, V> for the listed V that equals `v`.  Only the listed values are instantiated --
+// the list IS the set of compiled kernel instances -- and a value outside it calls nothing: false, the caller's error.
+template <int... Vs, class F>
+bool with_tile(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// ... and a pair of them (row x column tile of the weight gradient, tile width x neighbours of hwgrad_kernel):
+// with_tiles<Tile<64, 64>, Tile<64, 128>>(bm, bj, [&](auto BM, auto BJ) { ... })
+template <int A, int B> struct Tile {};
+template <int A, int B, class F>
+bool tile_case(Tile<A, B>, int a, int b, F& f) {
+    if (a != A || b != B) return false;
+    f(std::integral_constant<int, A>{}, std::integral_constant<int, B>{});
+    return true;
+}
+template <class... Tiles, class F>
+bool with_tiles(int a, int b, F&& f) {
+    return (tile_case(Tiles{}, a, b, f) || ...);
+}
 
 // Pixel splits of a weight-gradient launch: the workgroup count (tiles x splits) should fill the chip's resident
 // slots a whole number of times -- 256 CUs x the workgroups of that tile shape one CU holds (set by the tile's LDS

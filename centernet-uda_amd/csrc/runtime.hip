@@ -130,6 +130,10 @@ bool wave_specialised() {
     static const bool on = !(getenv("CNUDA_WS") && getenv("CNUDA_WS")[0] == '0');
     return on;
 }
+bool buffer_addressing() {
+    static const bool on = !(getenv("CNUDA_BUF") && getenv("CNUDA_BUF")[0] == '0');
+    return on;
+}
 }  // namespace cnuda
 extern "C" int cnuda_set_matrix_mode(int mode) {
     if (mode != 0 && mode != 1) {
