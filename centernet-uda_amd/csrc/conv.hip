@@ -641,49 +641,28 @@ struct ConvWLoader {
     using Params = ConvWParams;
     static const char* name() { return MODE == 2 ? "ConvWLoader<2>" : (MODE == 1 ? "ConvWLoader<1>" : "ConvWLoader<0>"); }
     const Params& p;
-    // pixel cursor: image index, pixel index inside the image, output row / column
-    long long n_, n_end_;
-    int b_, pp_, oy_, ox_;
-    bool valid_;
-    __device__ __forceinline__ void cursor_init(long long n, long long n_end, int HoWo, int Wo) {
-        n_ = n;
-        n_end_ = n_end;
-        valid_ = n < n_end;
-        const long long nn = valid_ ? n : 0;
-        b_ = (int)(nn / HoWo);
-        pp_ = (int)(nn - (long long)b_ * HoWo);
-        oy_ = pp_ / Wo;
-        ox_ = pp_ - oy_ * Wo;
-    }
-    __device__ __forceinline__ void cursor_advance(int HoWo, int Wo) {
-        n_ += WG_BP;
-        valid_ = n_ < n_end_;
-        pp_ += WG_BP;
-        ox_ += WG_BP;
-        while (ox_ >= Wo) { ox_ -= Wo; ++oy_; }
-        while (pp_ >= HoWo) { pp_ -= HoWo; ++b_; oy_ = pp_ / Wo; ox_ = pp_ - oy_ * Wo; }
-    }
+    IgPixelCursor c;
     __device__ ConvWLoader(const Params& pp, long long n, long long n_end) : p(pp) {
-        cursor_init(n, n_end, p.g.Ho * p.g.Wo, p.g.Wo);
+        c.init(n, n_end, p.g.Ho * p.g.Wo, p.g.Wo);
     }
-    __device__ __forceinline__ void advance() { cursor_advance(p.g.Ho * p.g.Wo, p.g.Wo); }
+    __device__ __forceinline__ void advance() { c.advance(p.g.Ho * p.g.Wo, p.g.Wo); }
     template <int NV, int STEP>
     __device__ __forceinline__ void load_g(int m0, int msub, float (&v)[NV]) {
         const ConvGeom& g = p.g;
         const int HoWo = g.Ho * g.Wo;
-        const float* base = p.gy + (size_t)b_ * g.Co * HoWo + pp_;
+        const float* base = p.gy + (size_t)c.b_ * g.Co * HoWo + c.pp_;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int m = m0 + msub + STEP * i;
-            v[i] = (valid_ && m < g.Co) ? base[(size_t)m * HoWo] : 0.0f;
+            v[i] = (c.valid_ && m < g.Co) ? base[(size_t)m * HoWo] : 0.0f;
         }
     }
     template <int NV, int STEP>
     __device__ __forceinline__ void load_b(int j0, int jsub, float (&v)[NV]) {
         const ConvGeom& g = p.g;
         const int HW = g.H * g.W, K = g.kh * g.kw * g.C;
-        const int iy0 = oy_ * g.sh - g.ph, ix0 = ox_ * g.sw - g.pw;
-        const float* x_b = p.x + (size_t)b_ * g.C * HW;
+        const int iy0 = c.oy_ * g.sh - g.ph, ix0 = c.ox_ * g.sw - g.pw;
+        const float* x_b = p.x + (size_t)c.b_ * g.C * HW;
         if (MODE == 2) {
             // every aligned group of 64 columns has one tap (C % 64 == 0): NV/16 bounds tests, no index math
             constexpr int PER = 64 / STEP;     // values of this thread inside one 64-column group
@@ -693,7 +672,7 @@ struct ConvWLoader {
                 const int tap = jg / g.C, c0 = jg - tap * g.C + jsub;
                 const int r = tap / g.kw, s = tap - r * g.kw;
                 const int iy = iy0 + r, ix = ix0 + s;
-                const bool ok1 = valid_ && jg < K && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W;
+                const bool ok1 = c.valid_ && jg < K && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W;
                 const float* ptr = x_b + (size_t)c0 * HW + (ok1 ? iy * g.W + ix : 0);
 #pragma unroll
                 for (int i = 0; i < PER; ++i) v[PER * h + i] = ok1 ? ptr[(size_t)(STEP * i) * HW] : 0.0f;
@@ -706,8 +685,8 @@ struct ConvWLoader {
         for (int i = 0; i < NV; ++i) {
             const int k = j0 + jsub + STEP * i;
             float val = 0.0f;
-            if (valid_ && k < K) {
-                const int tap = k / g.C, c = k - tap * g.C;
+            if (c.valid_ && k < K) {
+                const int tap = k / g.C, ch = k - tap * g.C;
                 if (tap != cur) {
                     const int r = tap / g.kw, s = tap - r * g.kw;
                     const int iy = iy0 + r, ix = ix0 + s;
@@ -715,7 +694,7 @@ struct ConvWLoader {
                     off = iy * g.W + ix;
                     cur = tap;
                 }
-                if (ok) val = x_b[(size_t)c * HW + off];
+                if (ok) val = x_b[(size_t)ch * HW + off];
             }
             v[i] = val;
         }

@@ -101,6 +101,8 @@ __device__ __forceinline__ void tap_corners(const Tap& t, const float* __restric
 __device__ __forceinline__ float tap_sample(const Tap& t, float v00, float v01, float v10, float v11) {
     return t.hh * t.hw * v00 + t.hh * t.lw * v01 + t.lh * t.hw * v10 + t.lh * t.lw * v11;
 }
+// the two corners of a plane row as one 8-byte load (W >= 2; 4-byte aligned)
+struct __attribute__((packed, aligned(4))) Pair { float l, r; };
 
 // ---------------------------------------------------------------------------
 // forward: igemm_fwd_kernel loader (deformable_group == 1)
@@ -163,7 +165,6 @@ struct DcnFwdLoaderT {
             col_voff = (p.col && n_valid) ? (unsigned)(b * K * HoWo + pp) * (unsigned)sizeof(float) : IG_BUF_OOB;
         }
     }
-    struct __attribute__((packed, aligned(4))) Pair { float l, r; };
     __device__ __forceinline__ void set_tap(int tap) {
         const Tap t = make_tap(g, off_b, mask_b, 0, tap, oy, ox);
         const float mk = (valid && t.inside) ? t.mask : 0.0f;
@@ -674,7 +675,6 @@ __global__ __launch_bounds__(1024) void dcn_sample_kernel(DcnSampleParams p, int
         const int wa = ledge ? 0 : (redge ? g.W - 2 : t.w0);
         const int ht = t.h0 < 0 ? 0 : t.h0, hb = t.h0 + 1 > g.H - 1 ? g.H - 1 : t.h0 + 1;
         const int qT = t.inside ? ht * g.W + wa : 0, qB = t.inside ? hb * g.W + wa : 0;
-        struct __attribute__((packed, aligned(4))) Pair { float l, r; };
         for (int c0 = 0; c0 < g.C; c0 += 8) {
             float e00[8], e01[8], e10[8], e11[8];
             if (paired) {
@@ -798,8 +798,21 @@ struct DcnColsBufLoader {
 //   dcn_col2im_kernel     : bilinear scatter of dcol*mask into grad_input through an LDS
 //                           window; every wave owns four channel planes.
 // ---------------------------------------------------------------------------
-struct DcnGeo { int cell; float lh, lw, mask; };   // cell = h0 << 16 | (w0 & 0xffff); h0 = -32768: tap outside
+// The 16-byte geometry record of a (pixel, tap): packed from a Tap by dcn_coord_grad_kernel and dcn_prep_kernel, unpacked by
+// the gather role of dcn_bwd_data_kernel and by dcn_scatter_group.
+struct DcnGeo { int cell; float lh, lw, mask; };   // cell = h0 << 16 | (w0 & 0xffff), or DCN_GEO_OUTSIDE
 static_assert(sizeof(DcnGeo) == 16, "geometry record is one dwordx4");
+constexpr int DCN_GEO_OUTSIDE = (int)0x80000000u;  // h0 = -32768: the tap samples outside the plane (its mask is stored as 0)
+struct DcnGeoTap { int h0, w0; float lh, lw, mask; bool inside; };
+__device__ __forceinline__ DcnGeo dcn_geo_pack(const Tap& t) {
+    DcnGeo r;
+    r.cell = t.inside ? (int)(((unsigned)t.h0 << 16) | ((unsigned)t.w0 & 0xffffu)) : DCN_GEO_OUTSIDE;
+    r.lh = t.lh; r.lw = t.lw; r.mask = t.inside ? t.mask : 0.f;
+    return r;
+}
+__device__ __forceinline__ DcnGeoTap dcn_geo_unpack(const DcnGeo& r) {
+    return {r.cell >> 16, (int)(short)(r.cell & 0xffff), r.lh, r.lw, r.mask, r.cell != DCN_GEO_OUTSIDE};
+}
 
 // channels c0 .. c0+7 of one (pixel, tap) out of the quad-interleaved column gradient: dq = its pixel's cell in row quad 0 of
 // the tap, row quads HoWo cells apart.  C % 4 == 0; a second quad past C is read clamped and the caller drops it.
@@ -809,6 +822,80 @@ __device__ __forceinline__ void dcn_load_dcol_quads(const float* __restrict__ dq
     const float4 b = *reinterpret_cast<const float4*>(dq + (size_t)q1 * HoWo * 4);
     d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
     d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+}
+
+// The coordinate gradient of one (pixel, tap) -- the ONE copy of this arithmetic: dcn_coord_grad_kernel (geometry from
+// make_tap) and the gather role of dcn_bwd_data_kernel (geometry from the record) both call it, then dcn_coord_store.
+// t: an inside tap of a plane with W >= 2; in_b: the image's input planes; dc: the pixel's cell in the first row (row quad)
+// of the tap's column gradient.
+struct DcnCoordSums { float sm, sh, sw; };      // d/d mask, d/d offset_h, d/d offset_w
+template <bool QUADS>
+__device__ __forceinline__ DcnCoordSums dcn_coord_tap(const DcnGeom& g, const DcnGeoTap& t, const float* in_b, const float* dc,
+                                                      int HoWo) {
+    const int HW = g.H * g.W, h0 = t.h0, w0 = t.w0;
+    const float lh = t.lh, lw = t.lw, hh = 1.0f - lh, hw = 1.0f - lw, mask = t.mask;
+    // The two corners of a row are ONE 8-byte load starting at column clamp(w0, 0, W-2) (halves the L1/TA
+    // requests, which bound this kernel); s*l / s*r say which element of the pair each corner is -- at the
+    // left edge the existing right corner is the pair's left element, at the right edge the existing left
+    // corner is its right element.  The three sums are linear in the corners, so the per-tap coefficients
+    // of (top.l, top.r, bottom.l, bottom.r) are folded once per tap.
+    const bool ledge = w0 < 0, redge = w0 > g.W - 2;
+    const int wa = ledge ? 0 : (redge ? g.W - 2 : w0);
+    const int ht = h0 < 0 ? 0 : h0, hb = h0 + 1 > g.H - 1 ? g.H - 1 : h0 + 1;
+    const int qT = ht * g.W + wa, qB = hb * g.W + wa;
+    // corner value e_xy = pair.l * L + pair.r * R with (L, R) in {(1,0), (0,1), (0,0)}
+    const float l0 = (!ledge && !redge) ? 1.f : 0.f, r0 = redge ? 1.f : 0.f;     // left corner  (column w0)
+    const float l1 = ledge ? 1.f : 0.f, r1 = (!ledge && !redge) ? 1.f : 0.f;     // right corner (column w0+1)
+    // which corners exist, from (h0, w0): Tap::c00 .. c11 as tap_from_raw spells them.  Both callers pass inside taps only, so
+    // t.inside is true here; it is written out because dcn_coord_grad_kernel then shares the flags with its Tap's (its
+    // width-1 branch reads those) instead of holding a second set in registers -- 96 instead of 98 VGPRs, a wave per SIMD.
+    const bool top = h0 >= 0, bot = h0 + 1 <= g.H - 1, lef = w0 >= 0, rig = w0 + 1 <= g.W - 1;
+    const bool c00 = t.inside && top && lef, c01 = t.inside && top && rig, c10 = t.inside && bot && lef, c11 = t.inside && bot && rig;
+    const float f00 = c00 ? 1.f : 0.f, f01 = c01 ? 1.f : 0.f, f10 = c10 ? 1.f : 0.f, f11 = c11 ? 1.f : 0.f;
+    // coefficient of e00, e01, e10, e11 in: sample (A), d/dh (Bh), d/dw (Bw)
+    const float A00 = hh * hw * f00, A01 = hh * lw * f01, A10 = lh * hw * f10, A11 = lh * lw * f11;
+    const float H00 = -hw * f00, H01 = -lw * f01, H10 = hw * f10, H11 = lw * f11;
+    const float W00 = -hh * f00, W01 = hh * f01, W10 = -lh * f10, W11 = lh * f11;
+    const float aTl = A00 * l0 + A01 * l1, aTr = A00 * r0 + A01 * r1, aBl = A10 * l0 + A11 * l1, aBr = A10 * r0 + A11 * r1;
+    const float hTl = H00 * l0 + H01 * l1, hTr = H00 * r0 + H01 * r1, hBl = H10 * l0 + H11 * l1, hBr = H10 * r0 + H11 * r1;
+    const float wTl = W00 * l0 + W01 * l1, wTr = W00 * r0 + W01 * r1, wBl = W10 * l0 + W11 * l1, wBr = W10 * r0 + W11 * r1;
+    // All three sums are linear in u = sum_c dcol_c * (top.l, top.r, bottom.l, bottom.r)_c: the channel loop
+    // accumulates the four components of u only (4 multiply-adds per channel instead of 14) and the per-tap
+    // coefficient rows are applied once at the end.  (Measured: no change in run time -- the kernel is bound
+    // by its corner gathers, not by the VALU; kept because it is the simpler arithmetic.)
+    float uTl = 0.f, uTr = 0.f, uBl = 0.f, uBr = 0.f;
+    for (int c0 = 0; c0 < g.C; c0 += 8) {
+        float d[8];
+        Pair pt[8], pb[8];
+        if constexpr (QUADS) dcn_load_dcol_quads(dc, c0, g.C, HoWo, d);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int c = c0 + u < g.C ? c0 + u : g.C - 1;
+            const float* plane = in_b + (size_t)c * HW;
+            if constexpr (!QUADS) d[u] = dc[(size_t)c * HoWo];
+            pt[u] = *reinterpret_cast<const Pair*>(plane + qT);
+            pb[u] = *reinterpret_cast<const Pair*>(plane + qB);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const float dd = c0 + u < g.C ? d[u] : 0.f;
+            uTl = fmaf(dd, pt[u].l, uTl); uTr = fmaf(dd, pt[u].r, uTr);      // (-ffp-contract=off: explicit)
+            uBl = fmaf(dd, pb[u].l, uBl); uBr = fmaf(dd, pb[u].r, uBr);
+        }
+    }
+    DcnCoordSums s;
+    s.sm = aTl * uTl + aTr * uTr + aBl * uBl + aBr * uBr;
+    s.sh = (hTl * uTl + hTr * uTr + hBl * uBl + hBr * uBr) * mask;
+    s.sw = (wTl * uTl + wTr * uTr + wBl * uBl + wBr * uBr) * mask;
+    return s;
+}
+// ... and its tail: the mask gradient (of the mask's logit where the geometry asks for it) and the offset gradients, stored once
+__device__ __forceinline__ void dcn_coord_store(const DcnGeom& g, float* gmask, float* goff, int b, int tap, int px, int HoWo,
+                                                float mask, DcnCoordSums s) {
+    if (g.gmask_logit) s.sm = s.sm * mask * (1.0f - mask);        // (cnuda_split_offset_mask_backward's own expression)
+    gmask[(size_t)b * g.gmask_bs + (size_t)tap * HoWo + px] = s.sm;
+    goff[(size_t)b * g.goff_bs + (size_t)(2 * tap) * HoWo + px] = s.sh;
+    goff[(size_t)b * g.goff_bs + (size_t)(2 * tap + 1) * HoWo + px] = s.sw;
 }
 
 struct DcnCoordParams {
@@ -831,57 +918,9 @@ __global__ __launch_bounds__(1024) void dcn_coord_grad_kernel(DcnCoordParams p, 
     for (int tap = threadIdx.y; tap < T; tap += blockDim.y) {
         const Tap t = make_tap(g, p.off + (size_t)b * g.off_bs, p.mask + (size_t)b * g.mask_bs, 0, tap, oy, ox);
         const float* dc = p.dcol + ((size_t)b * T + tap) * g.C * HoWo + (QUADS ? (size_t)px * 4 : (size_t)px);
-        float sm = 0.f, sh_ = 0.f, sw_ = 0.f;
+        DcnCoordSums s{0.f, 0.f, 0.f};
         if (t.inside && g.W >= 2) {
-            // The two corners of a row are ONE 8-byte load starting at column clamp(w0, 0, W-2) (halves the L1/TA
-            // requests, which bound this kernel); s*l / s*r say which element of the pair each corner is -- at the
-            // left edge the existing right corner is the pair's left element, at the right edge the existing left
-            // corner is its right element.  The three sums are linear in the corners, so the per-tap coefficients
-            // of (top.l, top.r, bottom.l, bottom.r) are folded once per tap.
-            struct __attribute__((packed, aligned(4))) Pair { float l, r; };
-            const bool ledge = t.w0 < 0, redge = t.w0 > g.W - 2;
-            const int wa = ledge ? 0 : (redge ? g.W - 2 : t.w0);
-            const int ht = t.h0 < 0 ? 0 : t.h0, hb = t.h0 + 1 > g.H - 1 ? g.H - 1 : t.h0 + 1;
-            const int qT = ht * g.W + wa, qB = hb * g.W + wa;
-            // corner value e_xy = pair.l * L + pair.r * R with (L, R) in {(1,0), (0,1), (0,0)}
-            const float l0 = (!ledge && !redge) ? 1.f : 0.f, r0 = redge ? 1.f : 0.f;     // left corner  (column w0)
-            const float l1 = ledge ? 1.f : 0.f, r1 = (!ledge && !redge) ? 1.f : 0.f;     // right corner (column w0+1)
-            const float f00 = t.c00 ? 1.f : 0.f, f01 = t.c01 ? 1.f : 0.f, f10 = t.c10 ? 1.f : 0.f,
-                        f11 = t.c11 ? 1.f : 0.f;
-            // coefficient of e00, e01, e10, e11 in: sample (A), d/dh (Bh), d/dw (Bw)
-            const float A00 = t.hh * t.hw * f00, A01 = t.hh * t.lw * f01, A10 = t.lh * t.hw * f10, A11 = t.lh * t.lw * f11;
-            const float H00 = -t.hw * f00, H01 = -t.lw * f01, H10 = t.hw * f10, H11 = t.lw * f11;
-            const float W00 = -t.hh * f00, W01 = t.hh * f01, W10 = -t.lh * f10, W11 = t.lh * f11;
-            const float aTl = A00 * l0 + A01 * l1, aTr = A00 * r0 + A01 * r1, aBl = A10 * l0 + A11 * l1, aBr = A10 * r0 + A11 * r1;
-            const float hTl = H00 * l0 + H01 * l1, hTr = H00 * r0 + H01 * r1, hBl = H10 * l0 + H11 * l1, hBr = H10 * r0 + H11 * r1;
-            const float wTl = W00 * l0 + W01 * l1, wTr = W00 * r0 + W01 * r1, wBl = W10 * l0 + W11 * l1, wBr = W10 * r0 + W11 * r1;
-            // All three sums are linear in u = sum_c dcol_c * (top.l, top.r, bottom.l, bottom.r)_c: the channel loop
-            // accumulates the four components of u only (4 multiply-adds per channel instead of 14) and the per-tap
-            // coefficient rows are applied once at the end.  (Measured: no change in run time -- the kernel is bound
-            // by its corner gathers, not by the VALU; kept because it is the simpler arithmetic.)
-            float uTl = 0.f, uTr = 0.f, uBl = 0.f, uBr = 0.f;
-            for (int c0 = 0; c0 < g.C; c0 += 8) {
-                float d[8];
-                Pair pt[8], pb[8];
-                if constexpr (QUADS) dcn_load_dcol_quads(dc, c0, g.C, HoWo, d);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int c = c0 + u < g.C ? c0 + u : g.C - 1;
-                    const float* plane = in_b + (size_t)c * HW;
-                    if constexpr (!QUADS) d[u] = dc[(size_t)c * HoWo];
-                    pt[u] = *reinterpret_cast<const Pair*>(plane + qT);
-                    pb[u] = *reinterpret_cast<const Pair*>(plane + qB);
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const float dd = c0 + u < g.C ? d[u] : 0.f;
-                    uTl = fmaf(dd, pt[u].l, uTl); uTr = fmaf(dd, pt[u].r, uTr);      // (-ffp-contract=off: explicit)
-                    uBl = fmaf(dd, pb[u].l, uBl); uBr = fmaf(dd, pb[u].r, uBr);
-                }
-            }
-            sm = aTl * uTl + aTr * uTr + aBl * uBl + aBr * uBr;
-            sh_ = (hTl * uTl + hTr * uTr + hBl * uBl + hBr * uBr) * t.mask;
-            sw_ = (wTl * uTl + wTr * uTr + wBl * uBl + wBr * uBr) * t.mask;
+            s = dcn_coord_tap<QUADS>(g, DcnGeoTap{t.h0, t.w0, t.lh, t.lw, t.mask, t.inside}, in_b, dc, HoWo);
         } else if (t.inside) {     // width 1: no horizontal neighbour to pair with
             const float f00 = t.c00 ? 1.f : 0.f, f01 = t.c01 ? 1.f : 0.f, f10 = t.c10 ? 1.f : 0.f,
                         f11 = t.c11 ? 1.f : 0.f;
@@ -890,31 +929,29 @@ __global__ __launch_bounds__(1024) void dcn_coord_grad_kernel(DcnCoordParams p, 
                 const float dd = QUADS ? dc[(size_t)(c >> 2) * HoWo * 4 + (c & 3)] : dc[(size_t)c * HoWo];
                 const float a00 = plane[t.o00] * f00, a01 = plane[t.o01] * f01, a10 = plane[t.o10] * f10,
                             a11 = plane[t.o11] * f11;
-                sm += dd * tap_sample(t, a00, a01, a10, a11);
+                s.sm += dd * tap_sample(t, a00, a01, a10, a11);
                 const float dm = dd * t.mask;
-                sh_ += (-t.hw * a00 - t.lw * a01 + t.hw * a10 + t.lw * a11) * dm;
-                sw_ += (-t.hh * a00 + t.hh * a01 - t.lh * a10 + t.lh * a11) * dm;
+                s.sh += (-t.hw * a00 - t.lw * a01 + t.hw * a10 + t.lw * a11) * dm;
+                s.sw += (-t.hh * a00 + t.hh * a01 - t.lh * a10 + t.lh * a11) * dm;
             }
         }
-        if (g.gmask_logit) sm = sm * t.mask * (1.0f - t.mask);        // (cnuda_split_offset_mask_backward's own expression)
-        p.gmask[(size_t)b * g.gmask_bs + (size_t)tap * HoWo + px] = sm;
-        p.goff[(size_t)b * g.goff_bs + (size_t)(2 * tap) * HoWo + px] = sh_;
-        p.goff[(size_t)b * g.goff_bs + (size_t)(2 * tap + 1) * HoWo + px] = sw_;
-        DcnGeo r;
-        r.cell = t.inside ? (int)(((unsigned)t.h0 << 16) | ((unsigned)t.w0 & 0xffffu)) : (int)0x80000000u;
-        r.lh = t.lh; r.lw = t.lw; r.mask = t.inside ? t.mask : 0.f;
-        p.geo[((size_t)b * T + tap) * HoWo + px] = r;
+        dcn_coord_store(g, p.gmask, p.goff, b, tap, px, HoWo, t.mask, s);
+        p.geo[((size_t)b * T + tap) * HoWo + px] = dcn_geo_pack(t);
     }
 }
 
 constexpr int CI_CG = 16;        // channels per workgroup (4 per wave)
 constexpr int CI_MARGIN = 2;     // window rows / columns beyond the undeformed footprint (default; DcnPlan::margin is what runs)
+// The pixel tiling and LDS window of the scatter walk (make_plan fills it; both walk forms take it as it stands):
+// TR x TC = 256 output pixels per tile, TC = 1 << tc_shift; ncg 16-channel groups; a window of WSZmax cells (0: windowless) with
+// `margin` rows / columns around the undeformed footprint; claim_sz bytes of claim map per wave.
+struct DcnWalkTile { int TR, TC, tc_shift, tiles_y, tiles_x, ncg, WSZmax, claim_sz, margin; };
 struct DcnCol2imParams {
     DcnGeom g;
     const float* dcol;
     const DcnGeo* geo;
     float* gin;
-    int TR, TC, tc_shift, tiles_y, tiles_x, ncg, WSZmax, claim_sz, margin;
+    DcnWalkTile tile;
 };
 // The col2im walk of ONE wave over ONE 16-channel group of a TR x TC pixel tile (256 pixels): the wave owns
 // channel planes c_w..c_w+3 of the LDS window ([cell][4 channels]: the four channels of a cell are ONE 16-byte
@@ -942,12 +979,22 @@ struct DcnScatterCtx {
     float4* dump;                             // a private cell for inactive lanes
     lds_vu8* claim;                           // this wave's claim map [WSZ]
 };
-__device__ __forceinline__ void dcn_scatter_window(DcnScatterCtx& x, const DcnGeom& g, int TR, int WSZmax, int margin) {
-    x.wy0 = x.y0 * g.sh - g.ph - margin;
-    x.wx0 = x.x0 * g.sw - g.pw - margin;
-    x.WR = WSZmax ? (TR - 1) * g.sh + (g.kh - 1) * g.dh + 2 * margin + 1 : 0;
-    x.WC = WSZmax ? (x.TC - 1) * g.sw + (g.kw - 1) * g.dw + 2 * margin + 1 : 0;
+// The context of wave `wid` (thread `tid` of the role's 256) for the tile at (y0, x0), carved out of the workgroup's dynamic LDS
+// `win`: 4 waves x [WSZ cells][4 channels], 256 dump cells x 4, the claim maps.  Clears the thread's dump cell.
+__device__ __forceinline__ DcnScatterCtx dcn_scatter_ctx(float* win, const DcnWalkTile& t, const DcnGeom& g, int y0, int x0,
+                                                         int wid, int tid) {
+    DcnScatterCtx x;
+    x.y0 = y0; x.x0 = x0; x.TC = t.TC; x.tc_shift = t.tc_shift;
+    x.wy0 = y0 * g.sh - g.ph - t.margin;
+    x.wx0 = x0 * g.sw - g.pw - t.margin;
+    x.WR = t.WSZmax ? (t.TR - 1) * g.sh + (g.kh - 1) * g.dh + 2 * t.margin + 1 : 0;
+    x.WC = t.WSZmax ? (t.TC - 1) * g.sw + (g.kw - 1) * g.dw + 2 * t.margin + 1 : 0;
     x.WSZ = x.WR * x.WC;                       // == WSZmax (or 0: the window does not fit the LDS)
+    x.wp = reinterpret_cast<float4*>(win) + (size_t)wid * x.WSZ;
+    x.dump = reinterpret_cast<float4*>(win + CI_CG * t.WSZmax) + tid;
+    x.claim = (lds_vu8*)(reinterpret_cast<unsigned char*>(win + CI_CG * t.WSZmax + 4 * 256) + wid * t.claim_sz);
+    *x.dump = make_float4(0.f, 0.f, 0.f, 0.f);
+    return x;
 }
 template <bool QUADS>
 __device__ __forceinline__ void dcn_scatter_group(const DcnScatterCtx& x, const DcnGeom& g, const DcnGeo* __restrict__ geo_b,
@@ -1007,12 +1054,13 @@ __device__ __forceinline__ void dcn_scatter_group(const DcnScatterCtx& x, const 
         if (it + 2 < items) fetch(slot);
         const int tapx = c_tapx;
         if (++c_tapx == g.kw) c_tapx = 0;             // (T = kh * kw taps per group: the column counter wraps with it)
-        const int h0 = rec.cell >> 16, w0 = (int)(short)(rec.cell & 0xffff);
-        const bool live = valid && rec.cell != (int)0x80000000u;
-        const float lh = rec.lh, lw = rec.lw, hh = 1.0f - lh, hw = 1.0f - lw;
+        const DcnGeoTap gt = dcn_geo_unpack(rec);
+        const int h0 = gt.h0, w0 = gt.w0;
+        const bool live = valid && gt.inside;
+        const float lh = gt.lh, lw = gt.lw, hh = 1.0f - lh, hw = 1.0f - lw;
         const float k00 = hh * hw, k01 = hh * lw, k10 = lh * hw, k11 = lh * lw;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) d[r] *= rec.mask * cvf[r];
+        for (int r = 0; r < 4; ++r) d[r] *= gt.mask * cvf[r];
         const int rh = h0 - wy0, rw = w0 - wx0;
         // wholly inside the window (both rows, both columns)?  else a stray
         const bool near = WSZ > 0 && live && (unsigned)rh < (unsigned)(WR - 1) && (unsigned)rw < (unsigned)(WC - 1);
@@ -1107,24 +1155,19 @@ __device__ __forceinline__ void dcn_scatter_group(const DcnScatterCtx& x, const 
 // Workgroup = (image, TR x TC tile of output pixels (256), 16 channels); the four waves never synchronise.
 template <bool QUADS>
 __global__ __launch_bounds__(256) void dcn_col2im_kernel(DcnCol2imParams p, int n_wg) {
-    extern __shared__ __align__(16) float win[];     // 4 waves x [WSZ cells][4 channels] + 256 dump cells x 4 + claim maps
+    extern __shared__ __align__(16) float win[];     // (dcn_scatter_ctx)
     const DcnGeom& g = p.g;
     const int T = g.kh * g.kw, HoWo = g.Ho * g.Wo, HW = g.H * g.W;
     // (wid through readfirstlane: the compiler then KNOWS it is wave-uniform, and everything derived from it -- channel
     // planes, row bases of the dcol loads, the window base -- is scalar arithmetic instead of per-lane 64-bit math)
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     int id = xcd_remap(blockIdx.x, n_wg);
-    const int cg = id % p.ncg; id /= p.ncg;
-    const int tx = id % p.tiles_x; id /= p.tiles_x;
-    const int ty = id % p.tiles_y;
-    const int b = id / p.tiles_y;
-    DcnScatterCtx x;
-    x.y0 = ty * p.TR; x.x0 = tx * p.TC; x.TC = p.TC; x.tc_shift = p.tc_shift;
-    dcn_scatter_window(x, g, p.TR, p.WSZmax, p.margin);
-    x.wp = reinterpret_cast<float4*>(win) + (size_t)wid * x.WSZ;
-    x.dump = reinterpret_cast<float4*>(win + CI_CG * p.WSZmax) + tid;
-    x.claim = (lds_vu8*)(reinterpret_cast<unsigned char*>(win + CI_CG * p.WSZmax + 4 * 256) + wid * p.claim_sz);
-    *x.dump = make_float4(0.f, 0.f, 0.f, 0.f);
+    const DcnWalkTile& tile = p.tile;
+    const int cg = id % tile.ncg; id /= tile.ncg;
+    const int tx = id % tile.tiles_x; id /= tile.tiles_x;
+    const int ty = id % tile.tiles_y;
+    const int b = id / tile.tiles_y;
+    const DcnScatterCtx x = dcn_scatter_ctx(win, tile, g, ty * tile.TR, tx * tile.TC, wid, tid);
     dcn_scatter_group<QUADS>(x, g, p.geo + (size_t)b * T * HoWo, p.dcol + (size_t)b * T * g.C * HoWo,
                              p.gin + (size_t)b * g.C * HW, cg * CI_CG + wid * 4, lane);
 }
@@ -1182,11 +1225,7 @@ __global__ __launch_bounds__(256) void dcn_prep_kernel(DcnPrepParams p) {
         const long long r = i / HoWo;
         const int tap = (int)(r % T), b = (int)(r / T);
         const int oy = px / g.Wo, ox = px - oy * g.Wo;
-        const Tap t = make_tap(g, p.off + (size_t)b * g.off_bs, p.mask + (size_t)b * g.mask_bs, 0, tap, oy, ox);
-        DcnGeo rec;
-        rec.cell = t.inside ? (int)(((unsigned)t.h0 << 16) | ((unsigned)t.w0 & 0xffffu)) : (int)0x80000000u;
-        rec.lh = t.lh; rec.lw = t.lw; rec.mask = t.inside ? t.mask : 0.f;
-        p.geo[i] = rec;
+        p.geo[i] = dcn_geo_pack(make_tap(g, p.off + (size_t)b * g.off_bs, p.mask + (size_t)b * g.mask_bs, 0, tap, oy, ox));
     }
 }
 
@@ -1195,26 +1234,27 @@ struct DcnBwdDataParams {
     const float *in, *dcol;
     const DcnGeo* geo;
     float *gin, *goff, *gmask;
-    int TR, TC, tc_shift, tiles_y, tiles_x, ncg, WSZmax, claim_sz, margin;
+    DcnWalkTile tile;
     int nsplit;      // workgroups per tile: workgroup s takes the channel groups [s*ncg/nsplit, (s+1)*ncg/nsplit) and the taps = s (mod nsplit)
 };
 template <bool QUADS>
 __global__ __launch_bounds__(512, 6) void dcn_bwd_data_kernel(DcnBwdDataParams p, int n_wg) {
-    extern __shared__ __align__(16) float win[];     // as dcn_col2im_kernel: 4 waves x [WSZ][4] + dump cells + claim maps
+    extern __shared__ __align__(16) float win[];     // (dcn_scatter_ctx)
     const DcnGeom& g = p.g;
     const int T = g.kh * g.kw, HoWo = g.Ho * g.Wo, HW = g.H * g.W;
     const int tid = threadIdx.x & 255, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform: see col2im
     int id = xcd_remap(blockIdx.x, n_wg);
     const int part = id % p.nsplit; id /= p.nsplit;
-    const int tx = id % p.tiles_x; id /= p.tiles_x;
-    const int ty = id % p.tiles_y;
-    const int b = id / p.tiles_y;
-    const int y0 = ty * p.TR, x0 = tx * p.TC;
+    const DcnWalkTile& tile = p.tile;
+    const int tx = id % tile.tiles_x; id /= tile.tiles_x;
+    const int ty = id % tile.tiles_y;
+    const int b = id / tile.tiles_y;
+    const int y0 = ty * tile.TR, x0 = tx * tile.TC;
     const DcnGeo* geo_b = p.geo + (size_t)b * T * HoWo;
     const float* dcol_b = p.dcol + (size_t)b * T * g.C * HoWo;
     auto pixel_of = [&](int grp, bool& valid) {
-        const int t = grp * 64 + lane;
-        const int oy = y0 + (t >> p.tc_shift), ox = x0 + (t & (p.TC - 1));
+        const int i = grp * 64 + lane;
+        const int oy = y0 + (i >> tile.tc_shift), ox = x0 + (i & (tile.TC - 1));
         valid = oy < g.Ho && ox < g.Wo;
         return valid ? oy * g.Wo + ox : 0;
     };
@@ -1222,78 +1262,27 @@ __global__ __launch_bounds__(512, 6) void dcn_bwd_data_kernel(DcnBwdDataParams p
     if ((DCN_ABLATE == 1) == (threadIdx.x >= 256)) return;
 #endif
     if (threadIdx.x >= 256) {
-        // ---- gather role: grad_offset / grad_mask of pixel group `wid` (dcn_coord_grad_kernel's arithmetic) ----
+        // ---- gather role: grad_offset / grad_mask of pixel group `wid` (dcn_coord_tap, as dcn_coord_grad_kernel) ----
         bool valid;
         const int px = pixel_of(wid, valid);
         if (!valid) return;
         const float* in_b = p.in + (size_t)b * g.C * HW;
-        struct __attribute__((packed, aligned(4))) Pair { float l, r; };
 #pragma unroll 1
         for (int tap = part; tap < T; tap += p.nsplit) {
-            const DcnGeo rec = geo_b[(size_t)tap * HoWo + px];
+            const DcnGeoTap t = dcn_geo_unpack(geo_b[(size_t)tap * HoWo + px]);
             const float* dc = dcol_b + (size_t)tap * g.C * HoWo + (QUADS ? (size_t)px * 4 : (size_t)px);
-            float sm = 0.f, sh_ = 0.f, sw_ = 0.f;
-            if (rec.cell != (int)0x80000000u) {
-                const int h0 = rec.cell >> 16, w0 = (int)(short)(rec.cell & 0xffff);
-                const float lh = rec.lh, lw = rec.lw, hh = 1.0f - lh, hw = 1.0f - lw;
-                const bool ledge = w0 < 0, redge = w0 > g.W - 2;
-                const int wa = ledge ? 0 : (redge ? g.W - 2 : w0);
-                const int ht = h0 < 0 ? 0 : h0, hb = h0 + 1 > g.H - 1 ? g.H - 1 : h0 + 1;
-                const int qT = ht * g.W + wa, qB = hb * g.W + wa;
-                const float l0 = (!ledge && !redge) ? 1.f : 0.f, r0 = redge ? 1.f : 0.f;
-                const float l1 = ledge ? 1.f : 0.f, r1 = (!ledge && !redge) ? 1.f : 0.f;
-                const bool top = h0 >= 0, bot = h0 + 1 <= g.H - 1, lef = w0 >= 0, rig = w0 + 1 <= g.W - 1;
-                const float f00 = (top && lef) ? 1.f : 0.f, f01 = (top && rig) ? 1.f : 0.f, f10 = (bot && lef) ? 1.f : 0.f,
-                            f11 = (bot && rig) ? 1.f : 0.f;
-                const float A00 = hh * hw * f00, A01 = hh * lw * f01, A10 = lh * hw * f10, A11 = lh * lw * f11;
-                const float H00 = -hw * f00, H01 = -lw * f01, H10 = hw * f10, H11 = lw * f11;
-                const float W00 = -hh * f00, W01 = hh * f01, W10 = -lh * f10, W11 = lh * f11;
-                const float aTl = A00 * l0 + A01 * l1, aTr = A00 * r0 + A01 * r1, aBl = A10 * l0 + A11 * l1, aBr = A10 * r0 + A11 * r1;
-                const float hTl = H00 * l0 + H01 * l1, hTr = H00 * r0 + H01 * r1, hBl = H10 * l0 + H11 * l1, hBr = H10 * r0 + H11 * r1;
-                const float wTl = W00 * l0 + W01 * l1, wTr = W00 * r0 + W01 * r1, wBl = W10 * l0 + W11 * l1, wBr = W10 * r0 + W11 * r1;
-                float uTl = 0.f, uTr = 0.f, uBl = 0.f, uBr = 0.f;
-                for (int c0 = 0; c0 < g.C; c0 += 8) {
-                    float d[8];
-                    Pair pt[8], pb[8];
-                    if constexpr (QUADS) dcn_load_dcol_quads(dc, c0, g.C, HoWo, d);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int c = c0 + u < g.C ? c0 + u : g.C - 1;
-                        const float* plane = in_b + (size_t)c * HW;
-                        if constexpr (!QUADS) d[u] = dc[(size_t)c * HoWo];
-                        pt[u] = *reinterpret_cast<const Pair*>(plane + qT);
-                        pb[u] = *reinterpret_cast<const Pair*>(plane + qB);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const float dd = c0 + u < g.C ? d[u] : 0.f;
-                        uTl = fmaf(dd, pt[u].l, uTl); uTr = fmaf(dd, pt[u].r, uTr);
-                        uBl = fmaf(dd, pb[u].l, uBl); uBr = fmaf(dd, pb[u].r, uBr);
-                    }
-                }
-                sm = aTl * uTl + aTr * uTr + aBl * uBl + aBr * uBr;
-                sh_ = (hTl * uTl + hTr * uTr + hBl * uBl + hBr * uBr) * rec.mask;
-                sw_ = (wTl * uTl + wTr * uTr + wBl * uBl + wBr * uBr) * rec.mask;
-            }
-            if (g.gmask_logit) sm = sm * rec.mask * (1.0f - rec.mask);    // (sm == 0 where the record's mask was zeroed: outside taps)
-            p.gmask[(size_t)b * g.gmask_bs + (size_t)tap * HoWo + px] = sm;
-            p.goff[(size_t)b * g.goff_bs + (size_t)(2 * tap) * HoWo + px] = sh_;
-            p.goff[(size_t)b * g.goff_bs + (size_t)(2 * tap + 1) * HoWo + px] = sw_;
+            DcnCoordSums s{0.f, 0.f, 0.f};            // (what an outside tap stores; its record's mask is zero as well)
+            if (t.inside) s = dcn_coord_tap<QUADS>(g, t, in_b, dc, HoWo);
+            dcn_coord_store(g, p.gmask, p.goff, b, tap, px, HoWo, t.mask, s);
         }
         return;
     }
     // ---- scatter role: dcn_col2im_kernel's walk, channel groups serial ----
-    DcnScatterCtx x;
-    x.y0 = y0; x.x0 = x0; x.TC = p.TC; x.tc_shift = p.tc_shift;
-    dcn_scatter_window(x, g, p.TR, p.WSZmax, p.margin);
-    x.wp = reinterpret_cast<float4*>(win) + (size_t)wid * x.WSZ;
-    x.dump = reinterpret_cast<float4*>(win + CI_CG * p.WSZmax) + tid;
-    x.claim = (lds_vu8*)(reinterpret_cast<unsigned char*>(win + CI_CG * p.WSZmax + 4 * 256) + wid * p.claim_sz);
-    *x.dump = make_float4(0.f, 0.f, 0.f, 0.f);
+    const DcnScatterCtx x = dcn_scatter_ctx(win, tile, g, y0, x0, wid, tid);
     float* gin_b = p.gin + (size_t)b * g.C * HW;
-    const int cg_end = (part + 1) * p.ncg / p.nsplit;
+    const int cg_end = (part + 1) * tile.ncg / p.nsplit;
 #pragma unroll 1
-    for (int cg = part * p.ncg / p.nsplit; cg < cg_end; ++cg)
+    for (int cg = part * tile.ncg / p.nsplit; cg < cg_end; ++cg)
         dcn_scatter_group<QUADS>(x, g, geo_b, dcol_b, gin_b, cg * CI_CG + wid * 4, lane);
 }
 
@@ -1307,62 +1296,41 @@ struct DcnWParams {
 struct DcnWLoader {
     using Params = DcnWParams;
     const Params& p;
-    // pixel cursor: image index, pixel index inside the image, output row / column
-    long long n_, n_end_;
-    int b_, pp_, oy_, ox_;
-    bool valid_;
-    __device__ __forceinline__ void cursor_init(long long n, long long n_end, int HoWo, int Wo) {
-        n_ = n;
-        n_end_ = n_end;
-        valid_ = n < n_end;
-        const long long nn = valid_ ? n : 0;
-        b_ = (int)(nn / HoWo);
-        pp_ = (int)(nn - (long long)b_ * HoWo);
-        oy_ = pp_ / Wo;
-        ox_ = pp_ - oy_ * Wo;
-    }
-    __device__ __forceinline__ void cursor_advance(int HoWo, int Wo) {
-        n_ += WG_BP;
-        valid_ = n_ < n_end_;
-        pp_ += WG_BP;
-        ox_ += WG_BP;
-        while (ox_ >= Wo) { ox_ -= Wo; ++oy_; }
-        while (pp_ >= HoWo) { pp_ -= HoWo; ++b_; oy_ = pp_ / Wo; ox_ = pp_ - oy_ * Wo; }
-    }
+    IgPixelCursor c;
     __device__ DcnWLoader(const Params& pp, long long n, long long n_end) : p(pp) {
-        cursor_init(n, n_end, p.g.Ho * p.g.Wo, p.g.Wo);
+        c.init(n, n_end, p.g.Ho * p.g.Wo, p.g.Wo);
     }
-    __device__ __forceinline__ void advance() { cursor_advance(p.g.Ho * p.g.Wo, p.g.Wo); }
+    __device__ __forceinline__ void advance() { c.advance(p.g.Ho * p.g.Wo, p.g.Wo); }
     template <int NV, int STEP>
     __device__ __forceinline__ void load_g(int m0, int msub, float (&v)[NV]) {
         const DcnGeom& g = p.g;
         const int HoWo = g.Ho * g.Wo;
-        const float* base = p.gout + (size_t)b_ * g.Co * HoWo + pp_;
+        const float* base = p.gout + (size_t)c.b_ * g.Co * HoWo + c.pp_;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int m = m0 + msub + STEP * i;
-            v[i] = (valid_ && m < g.Co) ? base[(size_t)m * HoWo] : 0.0f;
+            v[i] = (c.valid_ && m < g.Co) ? base[(size_t)m * HoWo] : 0.0f;
         }
     }
     template <int NV, int STEP>
     __device__ __forceinline__ void load_b(int j0, int jsub, float (&v)[NV]) {
         const DcnGeom& g = p.g;
         const int HW = g.H * g.W, T = g.kh * g.kw, K = T * g.C;
-        const float* in_b = p.in + (size_t)b_ * g.C * HW;
-        const float* off_b = p.off + (size_t)b_ * g.off_bs;
-        const float* mask_b = p.mask + (size_t)b_ * g.mask_bs;
+        const float* in_b = p.in + (size_t)c.b_ * g.C * HW;
+        const float* off_b = p.off + (size_t)c.b_ * g.off_bs;
+        const float* mask_b = p.mask + (size_t)c.b_ * g.mask_bs;
         int cur = -1;
         Tap t;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int k = j0 + jsub + STEP * i;
             float r = 0.0f;
-            if (valid_ && k < K) {
-                const int tap = k / g.C, c = k - tap * g.C;
-                if (tap != cur) { t = make_tap(g, off_b, mask_b, 0, tap, oy_, ox_); cur = tap; }
+            if (c.valid_ && k < K) {
+                const int tap = k / g.C, ch = k - tap * g.C;
+                if (tap != cur) { t = make_tap(g, off_b, mask_b, 0, tap, c.oy_, c.ox_); cur = tap; }
                 if (t.inside) {
                     float v00, v01, v10, v11;
-                    tap_corners(t, in_b + (size_t)c * HW, v00, v01, v10, v11);
+                    tap_corners(t, in_b + (size_t)ch * HW, v00, v01, v10, v11);
                     r = tap_sample(t, v00, v01, v10, v11) * t.mask;
                 }
             }
@@ -1380,52 +1348,31 @@ struct DcnColWParams {
 struct DcnColWLoader {
     using Params = DcnColWParams;
     const Params& p;
-    // pixel cursor: image index, pixel index inside the image, output row / column
-    long long n_, n_end_;
-    int b_, pp_, oy_, ox_;
-    bool valid_;
-    __device__ __forceinline__ void cursor_init(long long n, long long n_end, int HoWo, int Wo) {
-        n_ = n;
-        n_end_ = n_end;
-        valid_ = n < n_end;
-        const long long nn = valid_ ? n : 0;
-        b_ = (int)(nn / HoWo);
-        pp_ = (int)(nn - (long long)b_ * HoWo);
-        oy_ = pp_ / Wo;
-        ox_ = pp_ - oy_ * Wo;
-    }
-    __device__ __forceinline__ void cursor_advance(int HoWo, int Wo) {
-        n_ += WG_BP;
-        valid_ = n_ < n_end_;
-        pp_ += WG_BP;
-        ox_ += WG_BP;
-        while (ox_ >= Wo) { ox_ -= Wo; ++oy_; }
-        while (pp_ >= HoWo) { pp_ -= HoWo; ++b_; oy_ = pp_ / Wo; ox_ = pp_ - oy_ * Wo; }
-    }
+    IgPixelCursor c;
     __device__ DcnColWLoader(const Params& pp, long long n, long long n_end) : p(pp) {
-        cursor_init(n, n_end, p.g.Ho * p.g.Wo, p.g.Wo);
+        c.init(n, n_end, p.g.Ho * p.g.Wo, p.g.Wo);
     }
-    __device__ __forceinline__ void advance() { cursor_advance(p.g.Ho * p.g.Wo, p.g.Wo); }
+    __device__ __forceinline__ void advance() { c.advance(p.g.Ho * p.g.Wo, p.g.Wo); }
     template <int NV, int STEP>
     __device__ __forceinline__ void load_g(int m0, int msub, float (&v)[NV]) {
         const DcnGeom& g = p.g;
         const int HoWo = g.Ho * g.Wo;
-        const float* base = p.gout + (size_t)b_ * g.Co * HoWo + pp_;
+        const float* base = p.gout + (size_t)c.b_ * g.Co * HoWo + c.pp_;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int m = m0 + msub + STEP * i;
-            v[i] = (valid_ && m < g.Co) ? base[(size_t)m * HoWo] : 0.0f;
+            v[i] = (c.valid_ && m < g.Co) ? base[(size_t)m * HoWo] : 0.0f;
         }
     }
     template <int NV, int STEP>
     __device__ __forceinline__ void load_b(int j0, int jsub, float (&v)[NV]) {
         const DcnGeom& g = p.g;
         const int HoWo = g.Ho * g.Wo, K = g.kh * g.kw * g.C;
-        const float* base = p.col + (size_t)b_ * K * HoWo + pp_;
+        const float* base = p.col + (size_t)c.b_ * K * HoWo + c.pp_;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int k = j0 + jsub + STEP * i;
-            v[i] = (valid_ && k < K) ? base[(size_t)k * HoWo] : 0.0f;
+            v[i] = (c.valid_ && k < K) ? base[(size_t)k * HoWo] : 0.0f;
         }
     }
 };
@@ -1618,7 +1565,7 @@ struct DcnPlan {
     bool fwd_two_kernels;           // several M tiles: sample the columns once, then a plain GEMM
     // split backward: 1x1 GEMM workspace, transposed weights, dcol, geometry records; col2im tiling
     size_t gemm_bytes;
-    int TR, TC, tc_shift, tiles_y, tiles_x, ncg, WSZmax, claim_sz, margin;
+    DcnWalkTile tile;
     size_t col2im_lds;
     bool fused_consumers;           // dcn_bwd_data_kernel (large maps) instead of coord_grad + col2im
     int fused_split;                // its workgroups per tile
@@ -1654,31 +1601,32 @@ DcnPlan make_plan(const DcnGeom& g) {
                   carve_bytes((size_t)g.B * q.T * g.C * g.Ho * g.Wo, 4) +
                   carve_bytes((size_t)g.B * q.T * g.Ho * g.Wo, sizeof(DcnGeo)) + carve_bytes(q.gemm_bytes, 1) + 256;
     // col2im tile: 256 output pixels, lanes along x
-    q.TC = 64;
-    while (q.TC > 16 && q.TC / 2 >= g.Wo) q.TC >>= 1;
+    DcnWalkTile& w = q.tile;
+    w.TC = 64;
+    while (w.TC > 16 && w.TC / 2 >= g.Wo) w.TC >>= 1;
     // (round 6) a row width that 64-column tiles cover with a half-empty last tile -- 160 = 2.5 x 64, 80 = 1.25 x 64: the maps of
     // a 640 x 640 input -- takes 32-column tiles when those pad less: idle lanes cost the walk whole steps.  Measured, B = 32:
     // 64 -> 64 at 160 x 160 1861 -> 1702 us, 128 -> 64 at 80 x 80 1177 -> 1071 us (profiles/r6_dcn_walk_tile.txt), although the
     // 32-column tile ranks colliding lanes through the claim map instead of three DPP shifts (two rows per wave step).
-    if (q.TC == 64 && round_up(g.Wo, 32) < round_up(g.Wo, 64)) q.TC = 32;
-    if (g_walk_tc == 16 || g_walk_tc == 32 || g_walk_tc == 64) q.TC = g_walk_tc;     // (measurements: cnuda_dcn_set_walk_tile)
-    q.TR = 256 / q.TC;
-    q.tc_shift = q.TC == 64 ? 6 : (q.TC == 32 ? 5 : 4);
-    q.tiles_y = ceil_div(g.Ho, q.TR);
-    q.tiles_x = ceil_div(g.Wo, q.TC);
-    q.ncg = ceil_div(g.C, CI_CG);
-    q.margin = g_scatter_margin > 0 ? g_scatter_margin : ((g_offset_regime & 1) ? 4 : CI_MARGIN);
-    const int wr = (q.TR - 1) * g.sh + (g.kh - 1) * g.dh + 2 * q.margin + 1;
-    const int wc = (q.TC - 1) * g.sw + (g.kw - 1) * g.dw + 2 * q.margin + 1;
-    q.WSZmax = wr * wc;
-    q.claim_sz = ((wr + 1) * (wc + 1) + 15) / 16 * 16;
+    if (w.TC == 64 && round_up(g.Wo, 32) < round_up(g.Wo, 64)) w.TC = 32;
+    if (g_walk_tc == 16 || g_walk_tc == 32 || g_walk_tc == 64) w.TC = g_walk_tc;     // (measurements: cnuda_dcn_set_walk_tile)
+    w.TR = 256 / w.TC;
+    w.tc_shift = w.TC == 64 ? 6 : (w.TC == 32 ? 5 : 4);
+    w.tiles_y = ceil_div(g.Ho, w.TR);
+    w.tiles_x = ceil_div(g.Wo, w.TC);
+    w.ncg = ceil_div(g.C, CI_CG);
+    w.margin = g_scatter_margin > 0 ? g_scatter_margin : ((g_offset_regime & 1) ? 4 : CI_MARGIN);
+    const int wr = (w.TR - 1) * g.sh + (g.kh - 1) * g.dh + 2 * w.margin + 1;
+    const int wc = (w.TC - 1) * g.sw + (g.kw - 1) * g.dw + 2 * w.margin + 1;
+    w.WSZmax = wr * wc;
+    w.claim_sz = ((wr + 1) * (wc + 1) + 15) / 16 * 16;
     // three workgroups per CU need <= 53 KiB each; larger windows (strides, dilations, big kernels) run windowless
-    if ((size_t)CI_CG * q.WSZmax * 4 + 4096 + 4 * (size_t)q.claim_sz > (q.margin > CI_MARGIN ? 80 : 53) * 1024) { q.WSZmax = 0; q.claim_sz = 16; }
-    q.col2im_lds = ((size_t)CI_CG * q.WSZmax + 4 * 256) * sizeof(float) + 4 * (size_t)q.claim_sz;
+    if ((size_t)CI_CG * w.WSZmax * 4 + 4096 + 4 * (size_t)w.claim_sz > (w.margin > CI_MARGIN ? 80 : 53) * 1024) { w.WSZmax = 0; w.claim_sz = 16; }
+    q.col2im_lds = ((size_t)CI_CG * w.WSZmax + 4 * 256) * sizeof(float) + 4 * (size_t)w.claim_sz;
     // one workgroup per (image, tile) must still fill the chip (three resident per CU): the 128 x 128 and 64 x 64 maps
-    q.fused_consumers = q.WSZmax > 0 && g.W >= 2 && (long long)g.B * q.tiles_y * q.tiles_x >= g_fused_min_tiles;
+    q.fused_consumers = w.WSZmax > 0 && g.W >= 2 && (long long)g.B * w.tiles_y * w.tiles_x >= g_fused_min_tiles;
     q.fused_split = 4;     // measured 1..4 on the 128 x 128 / 64 x 64 layers: 1116/1077/1093/1064 and 716/645/611/584 us
-    if (q.fused_split > q.ncg) q.fused_split = q.ncg;
+    if (q.fused_split > w.ncg) q.fused_split = w.ncg;
 
     const size_t HoWo = (size_t)g.Ho * g.Wo;
     q.fwd = (g.dg > 1 && g.W >= 2) ? DcnFwdPath::Composed
@@ -1699,6 +1647,13 @@ DcnPlan make_plan(const DcnGeom& g) {
     q.dcol_quads = quads_on && g.C % 4 == 0 && HoWo < (1 << 26) &&
                    cnuda_conv2d_rowquads_supported(g.B, g.Co, g.Ho, g.Wo, q.T * g.C, 1, 1, 1, 1, 0, 0);
     return q;
+}
+
+// The <true> or <false> instance of a kernel templated on QUADS (DcnPlan::dcol_quads), as with_tile picks a tile:
+// with_quads(q.dcol_quads, [&](auto Q) { ... kernel<Q()> ... }) returns what the lambda returns.
+template <class F>
+auto with_quads(bool quads, F&& f) {
+    return quads ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // the GEMM behind a sampling / column loader: row tiles 32 / 64 / 128; WS (DcnColsBufLoader alone has such instances)
@@ -2198,37 +2153,40 @@ static int dcn_backward_impl(const float* input, const float* weight, const floa
                                                   0, -1.0f, gemm_ws, q.gemm_bytes, stream))
             return rc;
         if (q.fused_consumers) {
-            DcnBwdDataParams p{g, input, dcol, geo, grad_input, grad_offset, grad_mask, q.TR, q.TC, q.tc_shift,
-                               q.tiles_y, q.tiles_x, q.ncg, q.WSZmax, q.claim_sz, q.margin, q.fused_split};
-            const int n_wg = B * q.tiles_y * q.tiles_x * q.fused_split;
+            DcnBwdDataParams p{g, input, dcol, geo, grad_input, grad_offset, grad_mask, q.tile, q.fused_split};
+            const int n_wg = B * q.tile.tiles_y * q.tile.tiles_x * q.fused_split;
             ProfScope scope(st, 3);
             scope.name("dcn_bwd_data_kernel");
-            // (a wide-margin window: dynamic LDS beyond 64 KiB is opt-in)
-            CNUDA_REQUIRE(raise_dynamic_lds(quads ? reinterpret_cast<const void*>(&dcn_bwd_data_kernel<true>)
-                                                  : reinterpret_cast<const void*>(&dcn_bwd_data_kernel<false>), q.col2im_lds),
-                          "cnuda_dcn_v2_backward: dynamic LDS");
-            if (quads) CNUDA_LAUNCH((dcn_bwd_data_kernel<true>), dim3(n_wg), dim3(512), q.col2im_lds, st, p, n_wg);
-            else CNUDA_LAUNCH((dcn_bwd_data_kernel<false>), dim3(n_wg), dim3(512), q.col2im_lds, st, p, n_wg);
+            if (int rc = with_quads(quads, [&](auto Q) -> int {
+                    // (a wide-margin window: dynamic LDS beyond 64 KiB is opt-in)
+                    CNUDA_REQUIRE(raise_dynamic_lds(reinterpret_cast<const void*>(&dcn_bwd_data_kernel<Q()>), q.col2im_lds),
+                                  "cnuda_dcn_v2_backward: dynamic LDS");
+                    CNUDA_LAUNCH((dcn_bwd_data_kernel<Q()>), dim3(n_wg), dim3(512), q.col2im_lds, st, p, n_wg);
+                    return 0;
+                }))
+                return rc;
         } else {
             {
                 DcnCoordParams p{g, input, offset, mask, dcol, grad_offset, grad_mask, geo};
                 const int tiles = ceil_div(HoWo, 64), tw = q.T < 16 ? q.T : 16;
                 ProfScope scope(st, 1);
                 scope.name("dcn_coord_grad_kernel");
-                if (quads) CNUDA_LAUNCH((dcn_coord_grad_kernel<true>), dim3(B * tiles), dim3(64, tw), 0, st, p, tiles);
-                else CNUDA_LAUNCH((dcn_coord_grad_kernel<false>), dim3(B * tiles), dim3(64, tw), 0, st, p, tiles);
+                with_quads(quads, [&](auto Q) {
+                    CNUDA_LAUNCH((dcn_coord_grad_kernel<Q()>), dim3(B * tiles), dim3(64, tw), 0, st, p, tiles);
+                });
             }
             {
-                DcnCol2imParams p{g, dcol, geo, grad_input, q.TR, q.TC, q.tc_shift, q.tiles_y, q.tiles_x,
-                                  q.ncg, q.WSZmax, q.claim_sz, q.margin};
-                const int n_wg = B * q.tiles_y * q.tiles_x * q.ncg;
+                DcnCol2imParams p{g, dcol, geo, grad_input, q.tile};
+                const int n_wg = B * q.tile.tiles_y * q.tile.tiles_x * q.tile.ncg;
                 ProfScope scope(st, 2);
                 scope.name("dcn_col2im_kernel");
-                CNUDA_REQUIRE(raise_dynamic_lds(quads ? reinterpret_cast<const void*>(&dcn_col2im_kernel<true>)
-                                                      : reinterpret_cast<const void*>(&dcn_col2im_kernel<false>), q.col2im_lds),
-                              "cnuda_dcn_v2_backward: dynamic LDS");
-                if (quads) CNUDA_LAUNCH((dcn_col2im_kernel<true>), dim3(n_wg), dim3(256), q.col2im_lds, st, p, n_wg);
-                else CNUDA_LAUNCH((dcn_col2im_kernel<false>), dim3(n_wg), dim3(256), q.col2im_lds, st, p, n_wg);
+                if (int rc = with_quads(quads, [&](auto Q) -> int {
+                        CNUDA_REQUIRE(raise_dynamic_lds(reinterpret_cast<const void*>(&dcn_col2im_kernel<Q()>), q.col2im_lds),
+                                      "cnuda_dcn_v2_backward: dynamic LDS");
+                        CNUDA_LAUNCH((dcn_col2im_kernel<Q()>), dim3(n_wg), dim3(256), q.col2im_lds, st, p, n_wg);
+                        return 0;
+                    }))
+                    return rc;
             }
         }
         if (int rc = check_launch("cnuda_dcn_v2_backward(data)")) return rc;

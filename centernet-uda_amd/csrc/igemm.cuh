@@ -945,9 +945,12 @@ __global__ __launch_bounds__(IG_THREADS, 2) void igemm_fwd_shortk_kernel(
 // ---------------------------------------------------------------------------
 constexpr int WG_BM = 64, WG_BJ = 64, WG_BP = 32;   // pixels per chunk (2 LDS stages of 32 instead of 1 of 64)
 
-// Pixel cursor of the buffer-addressed weight-gradient loaders: (image, pixel inside the image, output row, column)
-// of the thread's pixel in the current 32-pixel chunk, advanced without divisions or 64-bit arithmetic (these run on
-// the staging waves between MFMAs: every vector instruction here is a matrix-pipe cycle lost).
+// Pixel cursor of every weight-gradient loader: (image, pixel inside the image, output row, column) of the thread's
+// pixel in the current 32-pixel chunk, advanced without divisions or 64-bit arithmetic (these run on the staging waves
+// between MFMAs: every vector instruction here is a matrix-pipe cycle lost).  valid_ is exactly `n < n_end` for the
+// cursor's pixel n while a split holds fewer than 2^31 pixels (left_ saturates there): the kernels pass
+// n = n_begin + (0 .. 31) and n_end <= n_begin + pix_per_split, and 2^31 pixels in ONE split are 8 GiB of grad_output per
+// output channel in that split alone -- with the splits the hosts make (wgrad_splits) terabytes of operands, no device's.
 struct IgPixelCursor {
     int left_;                 // pixels from the thread's pixel to the end of the split (> 0: the pixel is valid)
     int b_, pp_, oy_, ox_;
