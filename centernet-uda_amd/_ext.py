@@ -28,6 +28,65 @@ def _out_hw(H, W, kh, kw, sh, sw, ph, pw, dh, dw):
     return ((H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1, (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1)
 
 
+def _forward(who, input, weight, bias, offset, mask, om, geom, Ho, Wo, want_columns, act_slope, pack_token, pack_version,
+             stats_box):
+    """The one forward call behind dcn_v2_forward (offset, mask; om None) and dcn_v2_forward_om (om; offset, mask None), which
+    have validated their own tensor layout.  geom: (B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg).  -> (out, cols)"""
+    B, C, H, W, Co, kh, kw = geom[:7]
+    dg = geom[13]
+    out = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=input.device)
+    cols = None
+    if want_columns and W >= 2:          # (deformable_group > 1: the groups' buffers one behind the other, same size)
+        cols = torch.empty((B, kh * kw * C, Ho * Wo), dtype=torch.float32, device=input.device)
+    L = hr.lib()
+    ws = hr.workspace(L.cnuda_dcn_v2_workspace_bytes(*geom), input.device)
+    if dg == 1 and W >= 2:
+        hr.prof_arm('dcn_fwd', B, C, H, W, Co, kh, kw, Ho, Wo)
+    # stats_box (private): the caller's next layer is a train-mode BatchNorm (DeformConv, backends/dla.py:351-372) -- where
+    # the kernel can, its epilogue leaves the per-channel sum / sum of squares of `out` per pixel block (appended to the box)
+    stats, blk, rows = None, 0, 0
+    if stats_box is not None and act_slope < 0:
+        rec = hr.stats_side_output(stats_box, L.cnuda_dcn_v2_stats_block, geom, Ho * Wo, input.device)
+        if rec is not None:
+            stats, blk, rows = rec[:3]
+    tail = (*geom, hr.ptr(ws), ws.numel(), hr.stream())
+    # act_slope (not part of the reference's signature): fused epilogue activation of the BatchNorm-folded
+    # inference path; -1 = none = the reference's operation
+    with hr.pack_stamp(pack_token, weight, pack_version):     # (private) identity of the weights: pack cache
+        if om is not None:
+            rc = L.cnuda_dcn_v2_forward_om(hr.ptr(input), hr.ptr(weight), hr.ptr(bias), hr.ptr(om), hr.ptr(out), hr.ptr(cols),
+                                           hr.ptr(stats), blk, rows, float(act_slope), *tail)
+        elif stats is not None:
+            who += '_stats'
+            rc = L.cnuda_dcn_v2_forward_stats(hr.ptr(input), hr.ptr(weight), hr.ptr(bias), hr.ptr(offset), hr.ptr(mask),
+                                              hr.ptr(out), hr.ptr(cols), hr.ptr(stats), blk, rows, *tail)
+        else:
+            rc = L.cnuda_dcn_v2_forward_act(hr.ptr(input), hr.ptr(weight), hr.ptr(bias), hr.ptr(offset), hr.ptr(mask),
+                                            hr.ptr(out), hr.ptr(cols), float(act_slope), *tail)
+        hr.check(rc, who)
+    return out, cols
+
+
+def _backward(who, input, weight, bias, offset, mask, om, grad_output, geom, columns, grad_weight, grad_bias, grad_input):
+    """The one backward call behind dcn_v2_backward and dcn_v2_backward_om (as _forward).
+    -> [grad_input, grad_offset, grad_mask, grad_weight, grad_bias], or [grad_input, grad_om, grad_weight, grad_bias]"""
+    B, C, H, W, Co, kh, kw = geom[:7]
+    g_in = grad_input if grad_input is not None else torch.empty_like(input)
+    g_om = [torch.empty_like(om)] if om is not None else [torch.empty_like(offset), torch.empty_like(mask)]
+    # the parameter gradients may be written straight into caller-owned buffers (the arena's gradient sink)
+    g_wb = [grad_weight if grad_weight is not None else torch.empty_like(weight),
+            grad_bias if grad_bias is not None else torch.empty_like(bias)]
+    L = hr.lib()
+    ws = hr.workspace(L.cnuda_dcn_v2_workspace_bytes(*geom), input.device)
+    if geom[13] == 1:
+        hr.prof_arm('dcn_bwd', B, C, H, W, Co, kh, kw, grad_output.shape[2], grad_output.shape[3])
+    fn = L.cnuda_dcn_v2_backward_acc if om is None else L.cnuda_dcn_v2_backward_om
+    hr.check(fn(hr.ptr(input), hr.ptr(weight), hr.ptr(bias), *[hr.ptr(t) for t in ((offset, mask) if om is None else (om,))],
+                hr.ptr(grad_output), hr.ptr(columns), hr.ptr(g_in), 1 if grad_input is not None else 0,
+                *[hr.ptr(g) for g in g_om + g_wb], *geom, hr.ptr(ws), ws.numel(), hr.stream()), who)
+    return [g_in] + g_om + g_wb
+
+
 def dcn_v2_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w,
                    pad_h, pad_w, dilation_h, dilation_w, deformable_group, _want_columns=False, _act_slope=-1.0,
                    _pack_token=0, _pack_version=None, _stats_box=None):
@@ -42,39 +101,8 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride
                            % (tuple(offset.shape), tuple(mask.shape), Ho, Wo))
     geom = (B, C, H, W, Co, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
             dilation_h, dilation_w, deformable_group)
-    out = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=input.device)
-    cols = None
-    if _want_columns and W >= 2:          # (deformable_group > 1: the groups' buffers one behind the other, same size)
-        cols = torch.empty((B, T * C, Ho * Wo), dtype=torch.float32, device=input.device)
-    L = hr.lib()
-    nbytes = L.cnuda_dcn_v2_workspace_bytes(*geom)
-    ws = hr.workspace(nbytes, input.device)
-    if deformable_group == 1 and W >= 2:
-        hr.prof_arm('dcn_fwd', B, C, H, W, Co, kernel_h, kernel_w, Ho, Wo)
-    # _stats_box (private): the caller's next layer is a train-mode BatchNorm (DeformConv, backends/dla.py:351-372) -- where
-    # the kernel can, its epilogue leaves the per-channel sum / sum of squares of `out` per pixel block (appended to the box)
-    stats = None
-    if _stats_box is not None and _act_slope < 0:
-        import ctypes
-        rows = ctypes.c_int(0)
-        blk = L.cnuda_dcn_v2_stats_block(*geom, ctypes.byref(rows))
-        if blk:
-            stats = torch.empty(((B * Ho * Wo + 127) // 128 * (128 // blk), rows.value, 2), dtype=torch.float32,
-                                device=input.device)
-            _stats_box.append((stats, blk, rows.value, 0))
-    # _act_slope (not part of the reference's signature): fused epilogue activation of the BatchNorm-folded
-    # inference path; -1 = none = the reference's operation
-    with hr.pack_stamp(_pack_token, weight, _pack_version):     # (private) identity of the weights: pack cache
-        if stats is not None:
-            hr.check(L.cnuda_dcn_v2_forward_stats(hr.ptr(input), hr.ptr(weight), hr.ptr(bias), hr.ptr(offset), hr.ptr(mask),
-                                                  hr.ptr(out), hr.ptr(cols), hr.ptr(stats), blk, rows.value, *geom, hr.ptr(ws),
-                                                  ws.numel(),
-                                                  hr.stream()), 'dcn_v2_forward_stats')
-        else:
-            hr.check(L.cnuda_dcn_v2_forward_act(hr.ptr(input), hr.ptr(weight), hr.ptr(bias), hr.ptr(offset), hr.ptr(mask),
-                                                hr.ptr(out), hr.ptr(cols), float(_act_slope), *geom, hr.ptr(ws),
-                                                ws.numel(), hr.stream()),
-                     'dcn_v2_forward')
+    out, cols = _forward('dcn_v2_forward', input, weight, bias, offset, mask, None, geom, Ho, Wo, _want_columns, _act_slope,
+                         _pack_token, _pack_version, _stats_box)
     return (out, cols) if _want_columns else out
 
 
@@ -82,29 +110,16 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, ke
                     pad_h, pad_w, dilation_h, dilation_w, deformable_group, _columns=None, _grad_weight=None,
                     _grad_bias=None, _grad_input=None):
     """_grad_input: a buffer that already holds another consumer's share of the input's gradient (hip_runtime.fanout):
-    the data-gradient walks add into it instead of into a cleared tensor."""
+    the data-gradient walks add into it instead of into a cleared tensor.
+    -> [grad_input, grad_offset, grad_mask, grad_weight, grad_bias]"""
     hr.require_gpu(input, weight, bias, offset, mask, grad_output)
     input, weight, bias, offset, mask, grad_output = [
         hr.f32c(t) for t in (input, weight, bias, offset, mask, grad_output)]
     B, C, H, W, Co = _shapes(input, weight, offset, mask, kernel_h, kernel_w, deformable_group)
     geom = (B, C, H, W, Co, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
             dilation_h, dilation_w, deformable_group)
-    grads = [_grad_input if _grad_input is not None else torch.empty_like(input), torch.empty_like(offset),
-             torch.empty_like(mask)]
-    # the parameter gradients may be written straight into caller-owned buffers (the arena's gradient sink)
-    grads += [_grad_weight if _grad_weight is not None else torch.empty_like(weight),
-              _grad_bias if _grad_bias is not None else torch.empty_like(bias)]
-    L = hr.lib()
-    nbytes = L.cnuda_dcn_v2_workspace_bytes(*geom)
-    ws = hr.workspace(nbytes, input.device)
-    if deformable_group == 1:
-        hr.prof_arm('dcn_bwd', B, C, H, W, Co, kernel_h, kernel_w, grad_output.shape[2], grad_output.shape[3])
-    hr.check(L.cnuda_dcn_v2_backward_acc(hr.ptr(input), hr.ptr(weight), hr.ptr(bias), hr.ptr(offset), hr.ptr(mask),
-                                         hr.ptr(grad_output), hr.ptr(_columns), hr.ptr(grads[0]),
-                                         1 if _grad_input is not None else 0, *[hr.ptr(g) for g in grads[1:]], *geom,
-                                         hr.ptr(ws), ws.numel(), hr.stream()),
-             'dcn_v2_backward')
-    return grads        # [grad_input, grad_offset, grad_mask, grad_weight, grad_bias]
+    return _backward('dcn_v2_backward', input, weight, bias, offset, mask, None, grad_output, geom, _columns, _grad_weight,
+                     _grad_bias, _grad_input)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -126,26 +141,8 @@ def dcn_v2_forward_om(input, weight, bias, om, kernel_h, kernel_w, stride_h, str
     if tuple(om.shape) != (B, 3 * T, Ho, Wo):
         raise RuntimeError("dcn_v2_forward_om: om %s does not match [%d, %d, %d, %d]" % (tuple(om.shape), B, 3 * T, Ho, Wo))
     geom = (B, C, H, W, Co, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, 1)
-    out = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=input.device)
-    cols = torch.empty((B, T * C, Ho * Wo), dtype=torch.float32, device=input.device) if _want_columns else None
-    L = hr.lib()
-    ws = hr.workspace(L.cnuda_dcn_v2_workspace_bytes(*geom), input.device)
-    hr.prof_arm('dcn_fwd', B, C, H, W, Co, kernel_h, kernel_w, Ho, Wo)
-    stats, blk, nrows = None, 0, 0
-    if _stats_box is not None and _act_slope < 0:
-        import ctypes
-        rows = ctypes.c_int(0)
-        blk = L.cnuda_dcn_v2_stats_block(*geom, ctypes.byref(rows))
-        if blk:
-            nrows = rows.value
-            stats = torch.empty(((B * Ho * Wo + 127) // 128 * (128 // blk), nrows, 2), dtype=torch.float32, device=input.device)
-            _stats_box.append((stats, blk, nrows, 0))
-    with hr.pack_stamp(_pack_token, weight, _pack_version):
-        hr.check(L.cnuda_dcn_v2_forward_om(hr.ptr(input), hr.ptr(weight), hr.ptr(bias), hr.ptr(om), hr.ptr(out), hr.ptr(cols),
-                                           hr.ptr(stats), blk, nrows, float(_act_slope), *geom, hr.ptr(ws), ws.numel(),
-                                           hr.stream()),
-                 'dcn_v2_forward_om')
-    return out, cols
+    return _forward('dcn_v2_forward_om', input, weight, bias, None, None, om, geom, Ho, Wo, _want_columns, _act_slope,
+                    _pack_token, _pack_version, _stats_box)
 
 
 def dcn_v2_backward_om(input, weight, bias, om, grad_output, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
@@ -155,19 +152,9 @@ def dcn_v2_backward_om(input, weight, bias, om, grad_output, kernel_h, kernel_w,
     hr.require_gpu(input, weight, bias, om, grad_output)
     input, weight, bias, om, grad_output = [hr.f32c(t) for t in (input, weight, bias, om, grad_output)]
     B, C, H, W = input.shape
-    Co = weight.shape[0]
-    geom = (B, C, H, W, Co, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, 1)
-    grads = [_grad_input if _grad_input is not None else torch.empty_like(input), torch.empty_like(om),
-             _grad_weight if _grad_weight is not None else torch.empty_like(weight),
-             _grad_bias if _grad_bias is not None else torch.empty_like(bias)]
-    L = hr.lib()
-    ws = hr.workspace(L.cnuda_dcn_v2_workspace_bytes(*geom), input.device)
-    hr.prof_arm('dcn_bwd', B, C, H, W, Co, kernel_h, kernel_w, grad_output.shape[2], grad_output.shape[3])
-    hr.check(L.cnuda_dcn_v2_backward_om(hr.ptr(input), hr.ptr(weight), hr.ptr(bias), hr.ptr(om), hr.ptr(grad_output),
-                                        hr.ptr(_columns), hr.ptr(grads[0]), 1 if _grad_input is not None else 0,
-                                        hr.ptr(grads[1]), hr.ptr(grads[2]), hr.ptr(grads[3]), *geom, hr.ptr(ws), ws.numel(),
-                                        hr.stream()), 'dcn_v2_backward_om')
-    return grads
+    geom = (B, C, H, W, weight.shape[0], kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, 1)
+    return _backward('dcn_v2_backward_om', input, weight, bias, None, None, om, grad_output, geom, _columns, _grad_weight,
+                     _grad_bias, _grad_input)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

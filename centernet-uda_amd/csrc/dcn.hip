@@ -1649,6 +1649,35 @@ DcnPlan make_plan(const DcnGeom& g) {
     return q;
 }
 
+// cnuda_dcn_v2_stats_block on a plan: pixels per block of the BatchNorm statistics the forward of this plan leaves (0: none --
+// deformable_group > 1, width 1, planes that are no multiple of four pixels); *rows = rows per block
+int plan_stats_block(const DcnGeom& g, const DcnPlan& q, int* rows) {
+    if (q.fwd == DcnFwdPath::Naive || q.fwd == DcnFwdPath::Composed || ((g.Ho * g.Wo) & 3) != 0) return 0;
+    if (q.fwd == DcnFwdPath::Window) { if (rows) *rows = 64; return 32; }
+    if (rows) *rows = q.Mp;
+    return q.bm == 32 ? 32 : 64;
+}
+
+// One forward / backward call as the entry points hand it to dcn_forward_impl / dcn_backward_impl: the geometry fill_geom
+// made -- whose batch strides and gmask_logit the entry point has set where offsets and mask are not the reference's own
+// tensors -- and the pointers by name.  A new argument of the DCN calls is a new field here.
+struct DcnCall {
+    DcnGeom g;
+    const float *input, *weight, *bias, *offset, *mask;
+    void* workspace;
+    size_t workspace_bytes;
+    cnuda_stream_t stream;
+};
+struct DcnFwdCall : DcnCall {
+    float *output, *columns, *stats;     // columns, stats: side outputs, or null
+    float act_slope;                     // fused epilogue activation; < 0: none
+};
+struct DcnBwdCall : DcnCall {
+    const float *grad_output, *columns;  // columns: the forward's side output, or null (the weight gradient samples again)
+    float *grad_input, *grad_offset, *grad_mask, *grad_weight, *grad_bias;
+    int accumulate_input;                // grad_input holds another consumer's share: add to it
+};
+
 // The <true> or <false> instance of a kernel templated on QUADS (DcnPlan::dcol_quads), as with_tile picks a tile:
 // with_quads(q.dcol_quads, [&](auto Q) { ... kernel<Q()> ... }) returns what the lambda returns.
 template <class F>
@@ -1782,30 +1811,125 @@ extern "C" int cnuda_dcn_v2_stats_block(int B, int C, int H, int W, int Cout, in
                                         int dh, int dw, int dg, int* rows) {
     DcnGeom g;
     if (fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_stats_block")) return 0;
-    const DcnPlan q = make_plan(g);
-    if (q.fwd == DcnFwdPath::Naive || q.fwd == DcnFwdPath::Composed || ((g.Ho * g.Wo) & 3) != 0) return 0;
-    if (q.fwd == DcnFwdPath::Window) { if (rows) *rows = 64; return 32; }
-    if (rows) *rows = q.Mp;
-    return q.bm == 32 ? 32 : 64;
+    return plan_stats_block(g, make_plan(g), rows);
 }
 
-// elements per image of the offset / mask tensors and of their gradients when they are NOT the reference's own contiguous
-// tensors (0: default): rows of the offset convolution's 3T-channel output (cnuda_dcn_v2_*_om), or one deformable group's
-// rows of the dg-group tensors (the composed deformable_group > 1 path)
-struct DcnStrides { int off_bs = 0, mask_bs = 0, goff_bs = 0, gmask_bs = 0, gmask_logit = 0; };
-static int dcn_forward_impl(const float* input, const float* weight, const float* bias, const float* offset,
-                            const float* mask, float* output, float* columns, float* stats, float act_slope, int B, int C,
-                            int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg,
-                            void* workspace, size_t workspace_bytes, cnuda_stream_t stream,
-                            const DcnStrides* strides = nullptr);
+static int dcn_forward_impl(const DcnFwdCall& c, const DcnPlan& q) {
+    const DcnGeom& g = c.g;
+    CNUDA_REQUIRE(c.input && c.weight && c.bias && c.offset && c.mask && c.output, "cnuda_dcn_v2_forward: null pointer");
+    // (deformable_group > 1: the groups' column buffers one behind the other, [dg][B][T * C / dg][Ho * Wo] -- the same bytes)
+    CNUDA_REQUIRE(!c.columns || g.W >= 2, "cnuda_dcn_v2_forward_cols: columns output needs width >= 2");
+    hipStream_t st = (hipStream_t)c.stream;
+    CNUDA_REQUIRE(c.act_slope < 0.0f || (g.dg == 1 && g.W >= 2), "cnuda_dcn_v2_forward_act: fused activation needs deformable_group == 1 and width >= 2");
+    if (q.fwd == DcnFwdPath::Composed) {
+        // deformable_group > 1 (libs/DCNv2/dcn_v2.py:54-94 accepts any; testcpu.py:169-180 uses 2), round 6: the output is the sum
+        // over the groups of a deformable_group = 1 convolution of the group's C / dg input channels with its own offsets and
+        // mask -- the fast kernels run per group on a contiguous copy of the group's channels and weights, offsets / mask are
+        // read in place (the batch strides in `g` are those of the dg-group tensors); the group outputs are added in group order.
+        // (rounds 1-5: one thread per output element with global atomics in the backward: 45 ms / 1.5 s for the layer that
+        // takes 0.9 / 2.5 ms with one group, profiles/r6_dcn_dg2.txt)
+        const int Cg = g.C / g.dg, T = q.T, HoWo = g.Ho * g.Wo;
+        const long long HW = (long long)g.H * g.W;
+        const size_t inner = cnuda_dcn_v2_workspace_bytes(g.B, Cg, g.H, g.W, g.Co, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, g.dh, g.dw, 1);
+        Carver cv(c.workspace, c.workspace_bytes);
+        float* xg = cv.take<float>((size_t)g.B * Cg * HW);
+        float* wg = cv.take<float>((size_t)g.Co * Cg * T);
+        float* tmp = cv.take<float>((size_t)g.B * g.Co * HoWo);
+        float* zero = cv.take<float>((size_t)g.Co);
+        void* iws = cv.take<char>(inner);
+        CNUDA_REQUIRE(c.workspace && cv.cur <= cv.end, "cnuda_dcn_v2_forward: workspace too small");
+        if (hipMemsetAsync(zero, 0, (size_t)g.Co * sizeof(float), st) != hipSuccess) return check_launch("cnuda_dcn_v2_forward(dg>1)");
+        // a group's call: the caller's with the group's channels, one group, the copies and the inner workspace (no statistics,
+        // no activation: the checks above and the entry point's saw to that)
+        DcnFwdCall gc = c;
+        gc.g.C = Cg; gc.g.dg = 1;
+        gc.input = xg; gc.weight = wg;
+        gc.workspace = iws; gc.workspace_bytes = inner;
+        const DcnPlan gq = make_plan(gc.g);
+        // every group's weights pass through `wg`: under the caller's pack stamp the inner calls would all ask the pack cache
+        // for the same image of the same source, and groups 1.. would multiply with group 0's weights -- they do not cache
+        const PackStampSuspend uncached;
+        for (int grp = 0; grp < g.dg; ++grp) {
+            if (int rc = cnuda_copy_channels(c.input, xg, g.B, Cg, HW, g.C, grp * Cg, Cg, 0, c.stream)) return rc;
+            if (int rc = cnuda_copy_channels(c.weight, wg, g.Co, Cg, T, g.C, grp * Cg, Cg, 0, c.stream)) return rc;
+            gc.bias = grp == 0 ? c.bias : zero;
+            gc.offset = c.offset + (size_t)grp * 2 * T * HoWo;
+            gc.mask = c.mask + (size_t)grp * T * HoWo;
+            gc.output = grp == 0 ? c.output : tmp;
+            gc.columns = c.columns ? c.columns + (size_t)grp * g.B * T * Cg * HoWo : nullptr;
+            if (int rc = dcn_forward_impl(gc, gq)) return rc;
+            if (grp > 0)
+                if (int rc = cnuda_add(c.output, tmp, c.output, (long long)g.B * g.Co * HoWo, c.stream)) return rc;
+        }
+        return check_launch("cnuda_dcn_v2_forward(dg>1)");
+    }
+    if (q.fwd == DcnFwdPath::Naive) {
+        DcnNaiveParams p{g, c.input, c.weight, c.bias, c.offset, c.mask, nullptr, c.output, nullptr, nullptr, nullptr, nullptr};
+        CNUDA_LAUNCH(dcn_naive_fwd_kernel, dim3(stream_grid((long long)g.B * g.Co * g.Ho * g.Wo, 256)), dim3(256),
+                           0, st, p);
+        return check_launch("cnuda_dcn_v2_forward(dg>1)");
+    }
+    CNUDA_REQUIRE(q.N < (1ll << 31) - IG_BN, "cnuda_dcn_v2_forward: more than 2^31 pixels per call");
+    CNUDA_REQUIRE(c.workspace && c.workspace_bytes >= q.fwd_bytes, "cnuda_dcn_v2_forward: workspace too small");
+    Carver cv(c.workspace, c.workspace_bytes);
+    if (q.fwd == DcnFwdPath::Window) {
+        const int bm = 64;
+        const float* Aw = launch_pack(c.weight, cv.take<float>((size_t)q.Kp * bm), (size_t)q.Kp * bm * sizeof(float), g.Co, g.C,
+                                      q.T, PACK_HALO_FWD, q.Kp, bm, 0, st);
+        DcnFwdParams p{g, c.input, c.offset, c.mask, c.bias, c.act_slope, c.output, c.columns, c.stats, 64};
+        ProfScope prof(st);
+        prof.name("dcnw_fwd_kernel<%d>%s", bm, c.columns ? " (+ column side output)" : "");
+        const int tiles_x = g.W / dcnw_tile_cols(g.W), n_tiles = (int)(q.N / IG_BN);
+        // (a 128-row variant -- four accumulator tiles per wave -- spills and measured slower than the gathering
+        // loader's 128-row tile, 571 vs 452 us at 128 -> 128, 64 x 64, B = 32: layers with more than 64 outputs stay there)
+        bool lds_ok = true;
+        const bool found = with_tiles<Tile<64, 32>, Tile<64, 16>>(bm, dcnw_tile_cols(g.W), [&](auto BM, auto TC) {
+            const size_t fl = dcnw_lds_floats<TC()>(BM());
+            const size_t lds = (fl < (size_t)4 * IG_EPI_WAVE ? (size_t)4 * IG_EPI_WAVE : fl) * sizeof(float);
+            lds_ok = raise_dynamic_lds(reinterpret_cast<const void*>(&dcnw_fwd_kernel<BM(), TC()>), lds);
+            if (lds_ok) CNUDA_LAUNCH((dcnw_fwd_kernel<BM(), TC()>), dim3(n_tiles), dim3(IG_THREADS), lds, st, p, Aw, bm, q.Kp, n_tiles, tiles_x);
+        });
+        CNUDA_REQUIRE(lds_ok, "cnuda_dcn_v2_forward: dynamic LDS");
+        CNUDA_REQUIRE(found, "cnuda_dcn_v2_forward: no dcnw_fwd_kernel instance for %d-column tiles", dcnw_tile_cols(g.W));
+        return check_launch("cnuda_dcn_v2_forward(window)");
+    }
+    const float* A = launch_pack(c.weight, cv.take<float>((size_t)q.Kp * q.Mp), (size_t)q.Kp * q.Mp * sizeof(float), g.Co,
+                                 g.C, q.T, PACK_FWD, q.Kp, q.Mp, 0, st);
+    if (q.fwd == DcnFwdPath::SampleThenGemm) {
+        float* cols = c.columns ? c.columns : cv.take<float>((size_t)g.B * q.K * g.Ho * g.Wo);
+        ProfScope prof(st);   // brackets both kernels
+        prof.name("dcn_sample_kernel + igemm_fwd_kernel<%d, DcnColsLoader>", q.bm);
+        {
+            DcnSampleParams sp{g, c.input, c.offset, c.mask, cols};
+            const int tiles = ceil_div(g.Ho * g.Wo, 64), tw = q.T < 16 ? q.T : 16;
+            CNUDA_LAUNCH(dcn_sample_kernel, dim3(g.B * tiles), dim3(64, tw), 0, st, sp, tiles);
+        }
+        DcnColsParams p{g, cols, c.bias, c.act_slope, c.output, c.stats, q.Mp};
+        const bool found = q.fwd_ws    ? launch_dcn_fwd<DcnColsBufLoader, true>(q, p, A, g.Co, st)
+                           : q.fwd_buf ? launch_dcn_fwd<DcnColsBufLoader>(q, p, A, g.Co, st)
+                                       : launch_dcn_fwd<DcnColsLoader>(q, p, A, g.Co, st);
+        CNUDA_REQUIRE(found, "cnuda_dcn_v2_forward: no GEMM instance for a %d-row tile", q.bm);
+        return check_launch("cnuda_dcn_v2_forward(columns + GEMM)");
+    }
+    DcnFwdParams p{g, c.input, c.offset, c.mask, c.bias, c.act_slope, c.output, c.columns, c.stats, q.Mp};
+    ProfScope prof(st);
+    prof.name("igemm_fwd_kernel<%d, DcnFwdLoader>%s", q.bm, c.columns ? " (+ column side output)" : "");
+    const bool found = q.fwd_buf ? launch_dcn_fwd<DcnFwdBufLoader>(q, p, A, g.Co, st) : launch_dcn_fwd<DcnFwdLoader>(q, p, A, g.Co, st);
+    CNUDA_REQUIRE(found, "cnuda_dcn_v2_forward: no GEMM instance for a %d-row tile", q.bm);
+    return check_launch("cnuda_dcn_v2_forward");
+}
 
 extern "C" int cnuda_dcn_v2_forward_act(const float* input, const float* weight, const float* bias,
                                         const float* offset, const float* mask, float* output, float* columns,
                                         float act_slope, int B, int C, int H, int W, int Cout, int kh, int kw, int sh,
                                         int sw, int ph, int pw, int dh, int dw, int dg, void* workspace,
                                         size_t workspace_bytes, cnuda_stream_t stream) {
-    return dcn_forward_impl(input, weight, bias, offset, mask, output, columns, nullptr, act_slope, B, C, H, W, Cout, kh, kw,
-                            sh, sw, ph, pw, dh, dw, dg, workspace, workspace_bytes, stream);
+    DcnFwdCall c{};
+    if (int rc = fill_geom(c.g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_forward")) return rc;
+    c.input = input; c.weight = weight; c.bias = bias; c.offset = offset; c.mask = mask;
+    c.output = output; c.columns = columns; c.act_slope = act_slope;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return dcn_forward_impl(c, make_plan(c.g));
 }
 
 // forward (+ saved columns) that also leaves the BatchNorm statistics of the output: DeformConv = DCN + BatchNorm + ReLU
@@ -1816,124 +1940,216 @@ extern "C" int cnuda_dcn_v2_forward_stats(const float* input, const float* weigh
                                           int Cout, int kh, int kw, int sh,
                                           int sw, int ph, int pw, int dh, int dw, int dg, void* workspace,
                                           size_t workspace_bytes, cnuda_stream_t stream) {
+    DcnFwdCall c{};
+    if (int rc = fill_geom(c.g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_forward")) return rc;
+    const DcnPlan q = make_plan(c.g);
     if (stats) {
         // the layout THIS call will write (it follows the kernel choice, and that the offset regime in force now) against
         // the one the caller sized the buffer for
         int rows = 0;
-        const int blk = cnuda_dcn_v2_stats_block(B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, &rows);
+        const int blk = plan_stats_block(c.g, q, &rows);
         CNUDA_REQUIRE(blk != 0, "cnuda_dcn_v2_forward_stats: no statistics for this call (cnuda_dcn_v2_stats_block says which)");
         CNUDA_REQUIRE(blk == stats_block && rows == stats_rows,
                       "cnuda_dcn_v2_forward_stats: the statistics buffer was sized for blocks of %d pixels x %d rows, this call "
                       "writes %d x %d (did the offset regime change between cnuda_dcn_v2_stats_block and the call?)",
                       stats_block, stats_rows, blk, rows);
     }
-    return dcn_forward_impl(input, weight, bias, offset, mask, output, columns, stats, -1.0f, B, C, H, W, Cout, kh, kw, sh,
-                            sw, ph, pw, dh, dw, dg, workspace, workspace_bytes, stream);
+    c.input = input; c.weight = weight; c.bias = bias; c.offset = offset; c.mask = mask;
+    c.output = output; c.columns = columns; c.stats = stats; c.act_slope = -1.0f;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return dcn_forward_impl(c, q);
 }
 
-static int dcn_forward_impl(const float* input, const float* weight, const float* bias, const float* offset,
-                            const float* mask, float* output, float* columns, float* stats, float act_slope, int B, int C,
-                            int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg,
-                            void* workspace, size_t workspace_bytes, cnuda_stream_t stream, const DcnStrides* strides) {
-    CNUDA_REQUIRE(input && weight && bias && offset && mask && output, "cnuda_dcn_v2_forward: null pointer");
-    // (deformable_group > 1: the groups' column buffers one behind the other, [dg][B][T * C / dg][Ho * Wo] -- the same bytes)
-    CNUDA_REQUIRE(!columns || W >= 2, "cnuda_dcn_v2_forward_cols: columns output needs width >= 2");
-    DcnGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_forward")) return rc;
-    if (strides && strides->off_bs) g.off_bs = strides->off_bs;
-    if (strides && strides->mask_bs) g.mask_bs = strides->mask_bs;
-    hipStream_t st = (hipStream_t)stream;
-    CNUDA_REQUIRE(act_slope < 0.0f || (dg == 1 && W >= 2), "cnuda_dcn_v2_forward_act: fused activation needs deformable_group == 1 and width >= 2");
-    const DcnPlan q = make_plan(g);
+// Offsets and mask read straight out of `om`, the 3T-channel output of DCN's own offset convolution
+// (libs/DCNv2/dcn_v2.py:118-122: o1, o2, mask = chunk(out, 3); offset = cat(o1, o2); mask = sigmoid(mask)): rows 0 .. 2T-1
+// ARE the offsets, rows 2T .. 3T-1 the mask -- ALREADY sigmoid (cnuda_conv2d_forward_rowsig applies it in the
+// convolution's epilogue) -- and the backward writes one tensor `gom` of the same shape: the offsets' gradient and the
+// gradient of the mask's LOGIT (the walk multiplies by m (1 - m) where it stores).  No split / concatenate / sigmoid passes:
+// 32 launches of a benched step and two tensors per layer less (round 6).  deformable_group == 1.
+extern "C" int cnuda_dcn_v2_forward_om(const float* input, const float* weight, const float* bias, const float* om,
+                                       float* output, float* columns, float* stats, int stats_block, int stats_rows,
+                                       float act_slope, int B,
+                                       int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                                       int dw, int dg, void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
+    CNUDA_REQUIRE(om && dg == 1 && W >= 2, "cnuda_dcn_v2_forward_om: needs deformable_group == 1 and width >= 2");
+    DcnFwdCall c{};
+    if (int rc = fill_geom(c.g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_forward_om")) return rc;
+    const DcnPlan q = make_plan(c.g);
+    if (stats) {
+        int rows = 0;
+        const int blk = plan_stats_block(c.g, q, &rows);
+        CNUDA_REQUIRE(blk != 0 && blk == stats_block && rows == stats_rows,
+                      "cnuda_dcn_v2_forward_om: the statistics buffer was sized for blocks of %d pixels x %d rows, this call "
+                      "writes %d x %d", stats_block, stats_rows, blk, rows);
+    }
+    CNUDA_REQUIRE(!stats || act_slope < 0.0f, "cnuda_dcn_v2_forward_om: statistics are those of the output before an activation");
+    c.g.off_bs = c.g.mask_bs = 3 * q.T * c.g.Ho * c.g.Wo;      // offsets and mask are rows of one 3T-channel tensor
+    c.input = input; c.weight = weight; c.bias = bias; c.offset = om; c.mask = om + (size_t)2 * q.T * c.g.Ho * c.g.Wo;
+    c.output = output; c.columns = columns; c.stats = stats; c.act_slope = act_slope;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return dcn_forward_impl(c, q);
+}
+
+static int dcn_backward_impl(const DcnBwdCall& c, const DcnPlan& q) {
+    const DcnGeom& g = c.g;
+    CNUDA_REQUIRE(!c.columns || g.W >= 2, "cnuda_dcn_v2_backward_cols: columns input needs width >= 2");
+    CNUDA_REQUIRE(c.input && c.weight && c.offset && c.mask && c.grad_output && c.grad_input && c.grad_offset && c.grad_mask &&
+                      c.grad_weight && c.grad_bias,
+                  "cnuda_dcn_v2_backward: null pointer");
+    hipStream_t st = (hipStream_t)c.stream;
+    const int T = q.T, HoWo = g.Ho * g.Wo;
     if (q.fwd == DcnFwdPath::Composed) {
-        // deformable_group > 1 (libs/DCNv2/dcn_v2.py:54-94 accepts any; testcpu.py:169-180 uses 2), round 6: the output is the sum
-        // over the groups of a deformable_group = 1 convolution of the group's C / dg input channels with its own offsets and
-        // mask -- the fast kernels run per group on a contiguous copy of the group's channels and weights, offsets / mask are
-        // read in place (batch stride of the dg-group tensors, DcnStrides); the group outputs are added in group order.
-        // (rounds 1-5: one thread per output element with global atomics in the backward: 45 ms / 1.5 s for the layer that
-        // takes 0.9 / 2.5 ms with one group, profiles/r6_dcn_dg2.txt)
-        const int Cg = C / dg, T = kh * kw, HoWo = g.Ho * g.Wo;
-        const long long HW = (long long)H * W;
-        const size_t inner = cnuda_dcn_v2_workspace_bytes(B, Cg, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, 1);
-        Carver cv(workspace, workspace_bytes);
-        float* xg = cv.take<float>((size_t)B * Cg * HW);
-        float* wg = cv.take<float>((size_t)Cout * Cg * T);
-        float* tmp = cv.take<float>((size_t)B * Cout * HoWo);
-        float* zero = cv.take<float>((size_t)Cout);
+        // deformable_group > 1, composed from the deformable_group = 1 kernels (see dcn_forward_impl): per group the data
+        // gradient of its C / dg input channels, its rows of grad_offset / grad_mask (written in place: the batch strides in `g`
+        // are those of the dg-group tensors) and its slice of grad_weight; grad_bias by the first group's call
+        const int Cg = g.C / g.dg;
+        const long long HW = (long long)g.H * g.W;
+        const size_t inner = cnuda_dcn_v2_workspace_bytes(g.B, Cg, g.H, g.W, g.Co, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, g.dh, g.dw, 1);
+        Carver cv(c.workspace, c.workspace_bytes);
+        float* xg = cv.take<float>((size_t)g.B * Cg * HW);
+        float* wg = cv.take<float>((size_t)g.Co * Cg * T);
+        float* ging = cv.take<float>((size_t)g.B * Cg * HW);
+        float* gwg = cv.take<float>((size_t)g.Co * Cg * T);
+        float* gbt = cv.take<float>((size_t)g.Co);
         void* iws = cv.take<char>(inner);
-        CNUDA_REQUIRE(workspace && cv.cur <= cv.end, "cnuda_dcn_v2_forward: workspace too small");
-        if (hipMemsetAsync(zero, 0, (size_t)Cout * sizeof(float), st) != hipSuccess) return check_launch("cnuda_dcn_v2_forward(dg>1)");
-        const DcnStrides gs{dg * 2 * T * HoWo, dg * T * HoWo, 0, 0, 0};
-        // every group's weights pass through `wg`: under the caller's pack stamp the inner calls would all ask the pack cache
-        // for the same image of the same source, and groups 1.. would multiply with group 0's weights -- they do not cache
-        const PackStampSuspend uncached;
-        for (int grp = 0; grp < dg; ++grp) {
-            if (int rc = cnuda_copy_channels(input, xg, B, Cg, HW, C, grp * Cg, Cg, 0, stream)) return rc;
-            if (int rc = cnuda_copy_channels(weight, wg, Cout, Cg, T, C, grp * Cg, Cg, 0, stream)) return rc;
-            if (int rc = dcn_forward_impl(xg, wg, grp == 0 ? bias : zero, offset + (size_t)grp * 2 * T * HoWo,
-                                          mask + (size_t)grp * T * HoWo, grp == 0 ? output : tmp,
-                                          columns ? columns + (size_t)grp * B * T * Cg * HoWo : nullptr, nullptr, -1.0f, B, Cg, H,
-                                          W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, 1, iws, inner, stream, &gs))
-                return rc;
-            if (grp > 0)
-                if (int rc = cnuda_add(output, tmp, output, (long long)B * Cout * HoWo, stream)) return rc;
+        CNUDA_REQUIRE(c.workspace && cv.cur <= cv.end, "cnuda_dcn_v2_backward: workspace too small");
+        DcnBwdCall gc = c;       // a group's call: the caller's with the group's channels, one group, the copies, the inner workspace
+        gc.g.C = Cg; gc.g.dg = 1;
+        gc.input = xg; gc.weight = wg; gc.grad_input = ging; gc.grad_weight = gwg;
+        gc.workspace = iws; gc.workspace_bytes = inner;
+        const DcnPlan gq = make_plan(gc.g);
+        const PackStampSuspend uncached;       // (`wg` and the inner calls' transposed weights: one buffer for every group)
+        for (int grp = 0; grp < g.dg; ++grp) {
+            if (int rc = cnuda_copy_channels(c.input, xg, g.B, Cg, HW, g.C, grp * Cg, Cg, 0, c.stream)) return rc;
+            if (int rc = cnuda_copy_channels(c.weight, wg, g.Co, Cg, T, g.C, grp * Cg, Cg, 0, c.stream)) return rc;
+            // (a caller's running sum in grad_input: the group's slice goes in, is added to, and comes back)
+            if (c.accumulate_input)
+                if (int rc = cnuda_copy_channels(c.grad_input, ging, g.B, Cg, HW, g.C, grp * Cg, Cg, 0, c.stream)) return rc;
+            gc.offset = c.offset + (size_t)grp * 2 * T * HoWo;
+            gc.mask = c.mask + (size_t)grp * T * HoWo;
+            gc.columns = c.columns ? c.columns + (size_t)grp * g.B * T * Cg * HoWo : nullptr;
+            gc.grad_offset = c.grad_offset + (size_t)grp * 2 * T * HoWo;
+            gc.grad_mask = c.grad_mask + (size_t)grp * T * HoWo;
+            gc.grad_bias = grp == 0 ? c.grad_bias : gbt;
+            if (int rc = dcn_backward_impl(gc, gq)) return rc;
+            if (int rc = cnuda_copy_channels(ging, c.grad_input, g.B, Cg, HW, Cg, 0, g.C, grp * Cg, c.stream)) return rc;
+            if (int rc = cnuda_copy_channels(gwg, c.grad_weight, g.Co, Cg, T, Cg, 0, g.C, grp * Cg, c.stream)) return rc;
         }
-        return check_launch("cnuda_dcn_v2_forward(dg>1)");
+        return check_launch("cnuda_dcn_v2_backward(dg>1)");
     }
-    if (q.fwd == DcnFwdPath::Naive) {
-        DcnNaiveParams p{g, input, weight, bias, offset, mask, nullptr, output, nullptr, nullptr, nullptr, nullptr};
-        CNUDA_LAUNCH(dcn_naive_fwd_kernel, dim3(stream_grid((long long)B * Cout * g.Ho * g.Wo, 256)), dim3(256),
-                           0, st, p);
-        return check_launch("cnuda_dcn_v2_forward(dg>1)");
+    // (every data-gradient walk below ADDS into grad_input -- window flushes and strays are atomics -- so a caller that
+    // already holds another consumer's share of the input's gradient there passes accumulate_input and saves the sum)
+    // (deformable_group == 1: dcn_prep_kernel clears it beside its other work -- one launch less per layer; the walks run
+    // behind it on the same stream)
+    const long long gin_elems = (long long)g.B * g.C * g.H * g.W;
+    const bool zero_in_prep = !c.accumulate_input && g.dg == 1 && (gin_elems & 3) == 0 && (reinterpret_cast<uintptr_t>(c.grad_input) & 15) == 0;
+    if (!c.accumulate_input && !zero_in_prep &&
+        hipMemsetAsync(c.grad_input, 0, (size_t)gin_elems * sizeof(float), st) != hipSuccess)
+        return check_launch("cnuda_dcn_v2_backward(memset)");
+    if (g.dg != 1) {
+        launch_channel_sum(c.grad_output, c.grad_bias, g.B, g.Co, HoWo, st);
+        (void)hipMemsetAsync(c.grad_offset, 0, (size_t)g.B * g.dg * 2 * T * HoWo * sizeof(float), st);
+        (void)hipMemsetAsync(c.grad_mask, 0, (size_t)g.B * g.dg * T * HoWo * sizeof(float), st);
+        (void)hipMemsetAsync(c.grad_weight, 0, (size_t)g.Co * g.C * T * sizeof(float), st);
+        DcnNaiveParams p{g, c.input, c.weight, nullptr, c.offset, c.mask, c.grad_output, nullptr,
+                         c.grad_input, c.grad_offset, c.grad_mask, c.grad_weight};
+        CNUDA_LAUNCH(dcn_naive_bwd_kernel, dim3(stream_grid((long long)g.B * g.C * T * HoWo, 256)), dim3(256), 0, st,
+                           p);
+        return check_launch("cnuda_dcn_v2_backward(dg>1)");
     }
-    CNUDA_REQUIRE(q.N < (1ll << 31) - IG_BN, "cnuda_dcn_v2_forward: more than 2^31 pixels per call");
-    CNUDA_REQUIRE(workspace && workspace_bytes >= q.fwd_bytes, "cnuda_dcn_v2_forward: workspace too small");
-    Carver cv(workspace, workspace_bytes);
-    if (q.fwd == DcnFwdPath::Window) {
-        const int bm = 64;
-        const float* Aw = launch_pack(weight, cv.take<float>((size_t)q.Kp * bm), (size_t)q.Kp * bm * sizeof(float), Cout, C,
-                                      q.T, PACK_HALO_FWD, q.Kp, bm, 0, st);
-        DcnFwdParams p{g, input, offset, mask, bias, act_slope, output, columns, stats, 64};
-        ProfScope prof(st);
-        prof.name("dcnw_fwd_kernel<%d>%s", bm, columns ? " (+ column side output)" : "");
-        const int tiles_x = W / dcnw_tile_cols(W), n_tiles = (int)(q.N / IG_BN);
-        // (a 128-row variant -- four accumulator tiles per wave -- spills and measured slower than the gathering
-        // loader's 128-row tile, 571 vs 452 us at 128 -> 128, 64 x 64, B = 32: layers with more than 64 outputs stay there)
-        bool lds_ok = true;
-        const bool found = with_tiles<Tile<64, 32>, Tile<64, 16>>(bm, dcnw_tile_cols(W), [&](auto BM, auto TC) {
-            const size_t fl = dcnw_lds_floats<TC()>(BM());
-            const size_t lds = (fl < (size_t)4 * IG_EPI_WAVE ? (size_t)4 * IG_EPI_WAVE : fl) * sizeof(float);
-            lds_ok = raise_dynamic_lds(reinterpret_cast<const void*>(&dcnw_fwd_kernel<BM(), TC()>), lds);
-            if (lds_ok) CNUDA_LAUNCH((dcnw_fwd_kernel<BM(), TC()>), dim3(n_tiles), dim3(IG_THREADS), lds, st, p, Aw, bm, q.Kp, n_tiles, tiles_x);
-        });
-        CNUDA_REQUIRE(lds_ok, "cnuda_dcn_v2_forward: dynamic LDS");
-        CNUDA_REQUIRE(found, "cnuda_dcn_v2_forward: no dcnw_fwd_kernel instance for %d-column tiles", dcnw_tile_cols(W));
-        return check_launch("cnuda_dcn_v2_forward(window)");
+    CNUDA_REQUIRE(c.workspace && c.workspace_bytes >= q.bwd_bytes, "cnuda_dcn_v2_backward: workspace too small");
+    Carver cv(c.workspace, c.workspace_bytes);
+    float* slabs = cv.take<float>((size_t)q.Z * q.Mpw * q.Jp);
+    float* bsl = cv.take<float>(std::max((size_t)g.Co * g.B, (size_t)q.Z * q.Mpw));    // bias row sums per split: [Z][Mpw]
+    float* wt = cv.take<float>((size_t)12 * g.C * (g.Co < 64 ? 64 : g.Co));   // (or the window kernels' packs: [64][10 C], [12 C][64])
+    float* dcol = cv.take<float>((size_t)g.B * q.T * g.C * HoWo);
+    DcnGeo* geo = cv.take<DcnGeo>((size_t)g.B * q.T * HoWo);
+    void* gemm_ws = cv.take<char>(q.gemm_bytes);
+    // (running the weight gradient on a second stream beside the data-gradient chain was tried in round 2: the
+    // kernels do overlap but contend for the same LDS / issue slots -- nothing gained, removed)
+    hipStream_t wst = st;
+    // every timed scope below is recorded under the call's tag; sub 0: the column-gradient 1x1 GEMM (its own scope
+    // inside cnuda_conv2d_forward), 1: coord_grad, 2: col2im, 3: both as one launch, 4: the weight-gradient GEMM
+    ProfGroup prof;
+    // (2) weight gradient (and, from the same staging registers, the bias gradient: bsl -> slab reduce)
+    {
+      bool found;
+      {
+        ProfScope wscope(st, 4);
+        if (c.columns) {
+            DcnColWParams p{g, c.columns, c.grad_output};
+            wscope.name(q.colw_ws ? "igemm_wgrad_ws_kernel<%s, 64, %d>" : "igemm_wgrad_kernel<%s, 64, %d>",
+                        q.colw_buf ? "DcnColWBufLoader" : "DcnColWLoader", q.wbj);
+            found = q.colw_ws    ? launch_dcn_wgrad<DcnColWBufLoader, true, 64, 128>(q, q.wbj, p, slabs, bsl, wst)
+                    : q.colw_buf ? launch_dcn_wgrad<DcnColWBufLoader, false, 64, 128>(q, q.wbj, p, slabs, bsl, wst)
+                                 : launch_dcn_wgrad<DcnColWLoader, false, 64, 128>(q, q.wbj, p, slabs, bsl, wst);
+        } else {
+            DcnWParams p{g, c.input, c.offset, c.mask, c.grad_output};
+            wscope.name("igemm_wgrad_kernel<DcnWLoader, 64, 64>");
+            found = launch_dcn_wgrad<DcnWLoader, false, 64>(q, WG_BJ, p, slabs, bsl, wst);
+        }
+      }
+        CNUDA_REQUIRE(found, "cnuda_dcn_v2_backward: no weight-gradient instance for %d-column tiles", q.wbj);
+        if (int rc = check_launch("cnuda_dcn_v2_backward(weight)")) return rc;
+        launch_slab_reduce(slabs, c.grad_weight, q.Z, q.Mpw, q.Jp, g.Co, g.C, q.T, wst, bsl, c.grad_bias);
     }
-    const float* A = launch_pack(weight, cv.take<float>((size_t)q.Kp * q.Mp), (size_t)q.Kp * q.Mp * sizeof(float), Cout,
-                                 C, q.T, PACK_FWD, q.Kp, q.Mp, 0, st);
-    if (q.fwd == DcnFwdPath::SampleThenGemm) {
-        float* cols = columns ? columns : cv.take<float>((size_t)B * q.K * g.Ho * g.Wo);
-        ProfScope prof(st);   // brackets both kernels
-        prof.name("dcn_sample_kernel + igemm_fwd_kernel<%d, DcnColsLoader>", q.bm);
+    {
+        // (1) dcol = W^T x grad_output as a 1x1 implicit GEMM, then the two streaming consumers
         {
-            DcnSampleParams sp{g, input, offset, mask, cols};
-            const int tiles = ceil_div(g.Ho * g.Wo, 64), tw = q.T < 16 ? q.T : 16;
-            CNUDA_LAUNCH(dcn_sample_kernel, dim3(B * tiles), dim3(64, tw), 0, st, sp, tiles);
+            // transposed weights of the 1x1 GEMM + (fused form) the geometry records, one launch
+            const int wt_blocks = stream_grid((long long)q.T * g.C * g.Co, 256);
+            const int geo_blocks = q.fused_consumers ? stream_grid((long long)g.B * q.T * HoWo, 256) : 0;
+            const int zero_blocks = zero_in_prep ? stream_grid(gin_elems / 4, 256) : 0;
+            DcnPrepParams pp{g, c.weight, c.offset, c.mask, wt, q.fused_consumers ? geo : nullptr, wt_blocks,
+                             zero_in_prep ? c.grad_input : nullptr, gin_elems / 4, wt_blocks + geo_blocks};
+            CNUDA_LAUNCH(dcn_prep_kernel, dim3(wt_blocks + geo_blocks + zero_blocks), dim3(256), 0, st, pp);
         }
-        DcnColsParams p{g, cols, bias, act_slope, output, stats, q.Mp};
-        const bool found = q.fwd_ws    ? launch_dcn_fwd<DcnColsBufLoader, true>(q, p, A, Cout, st)
-                           : q.fwd_buf ? launch_dcn_fwd<DcnColsBufLoader>(q, p, A, Cout, st)
-                                       : launch_dcn_fwd<DcnColsLoader>(q, p, A, Cout, st);
-        CNUDA_REQUIRE(found, "cnuda_dcn_v2_forward: no GEMM instance for a %d-row tile", q.bm);
-        return check_launch("cnuda_dcn_v2_forward(columns + GEMM)");
+        const bool quads = q.dcol_quads;
+        if (int rc = quads ? cnuda_conv2d_forward_rowquads(c.grad_output, wt, dcol, g.B, g.Co, g.Ho, g.Wo, q.T * g.C, 1, 1, 1, 1, 0, 0,
+                                                           gemm_ws, q.gemm_bytes, c.stream)
+                           : cnuda_conv2d_forward(c.grad_output, wt, nullptr, dcol, g.B, g.Co, g.Ho, g.Wo, q.T * g.C, 1, 1, 1, 1, 0,
+                                                  0, -1.0f, gemm_ws, q.gemm_bytes, c.stream))
+            return rc;
+        if (q.fused_consumers) {
+            DcnBwdDataParams p{g, c.input, dcol, geo, c.grad_input, c.grad_offset, c.grad_mask, q.tile, q.fused_split};
+            const int n_wg = g.B * q.tile.tiles_y * q.tile.tiles_x * q.fused_split;
+            ProfScope scope(st, 3);
+            scope.name("dcn_bwd_data_kernel");
+            if (int rc = with_quads(quads, [&](auto Q) -> int {
+                    // (a wide-margin window: dynamic LDS beyond 64 KiB is opt-in)
+                    CNUDA_REQUIRE(raise_dynamic_lds(reinterpret_cast<const void*>(&dcn_bwd_data_kernel<Q()>), q.col2im_lds),
+                                  "cnuda_dcn_v2_backward: dynamic LDS");
+                    CNUDA_LAUNCH((dcn_bwd_data_kernel<Q()>), dim3(n_wg), dim3(512), q.col2im_lds, st, p, n_wg);
+                    return 0;
+                }))
+                return rc;
+        } else {
+            {
+                DcnCoordParams p{g, c.input, c.offset, c.mask, dcol, c.grad_offset, c.grad_mask, geo};
+                const int tiles = ceil_div(HoWo, 64), tw = q.T < 16 ? q.T : 16;
+                ProfScope scope(st, 1);
+                scope.name("dcn_coord_grad_kernel");
+                with_quads(quads, [&](auto Q) {
+                    CNUDA_LAUNCH((dcn_coord_grad_kernel<Q()>), dim3(g.B * tiles), dim3(64, tw), 0, st, p, tiles);
+                });
+            }
+            {
+                DcnCol2imParams p{g, dcol, geo, c.grad_input, q.tile};
+                const int n_wg = g.B * q.tile.tiles_y * q.tile.tiles_x * q.tile.ncg;
+                ProfScope scope(st, 2);
+                scope.name("dcn_col2im_kernel");
+                if (int rc = with_quads(quads, [&](auto Q) -> int {
+                        CNUDA_REQUIRE(raise_dynamic_lds(reinterpret_cast<const void*>(&dcn_col2im_kernel<Q()>), q.col2im_lds),
+                                      "cnuda_dcn_v2_backward: dynamic LDS");
+                        CNUDA_LAUNCH((dcn_col2im_kernel<Q()>), dim3(n_wg), dim3(256), q.col2im_lds, st, p, n_wg);
+                        return 0;
+                    }))
+                    return rc;
+            }
+        }
+        if (int rc = check_launch("cnuda_dcn_v2_backward(data)")) return rc;
     }
-    DcnFwdParams p{g, input, offset, mask, bias, act_slope, output, columns, stats, q.Mp};
-    ProfScope prof(st);
-    prof.name("igemm_fwd_kernel<%d, DcnFwdLoader>%s", q.bm, columns ? " (+ column side output)" : "");
-    const bool found = q.fwd_buf ? launch_dcn_fwd<DcnFwdBufLoader>(q, p, A, Cout, st) : launch_dcn_fwd<DcnFwdLoader>(q, p, A, Cout, st);
-    CNUDA_REQUIRE(found, "cnuda_dcn_v2_forward: no GEMM instance for a %d-row tile", q.bm);
-    return check_launch("cnuda_dcn_v2_forward");
+    return check_launch("cnuda_dcn_v2_backward");
 }
 
 extern "C" int cnuda_dcn_v2_backward(const float* input, const float* weight, const float* bias, const float* offset,
@@ -1959,13 +2175,6 @@ extern "C" int cnuda_dcn_v2_backward_cols(const float* input, const float* weigh
                                      workspace, workspace_bytes, stream);
 }
 
-static int dcn_backward_impl(const float* input, const float* weight, const float* bias,
-                             const float* offset, const float* mask, const float* grad_output,
-                             const float* columns, float* grad_input, int accumulate_input,
-                             float* grad_offset, float* grad_mask, float* grad_weight, float* grad_bias, int B,
-                             int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
-                             int dh, int dw, int dg, void* workspace, size_t workspace_bytes,
-                             cnuda_stream_t stream, const DcnStrides* strides);
 extern "C" int cnuda_dcn_v2_backward_acc(const float* input, const float* weight, const float* bias,
                                          const float* offset, const float* mask, const float* grad_output,
                                          const float* columns, float* grad_input, int accumulate_input,
@@ -1973,223 +2182,32 @@ extern "C" int cnuda_dcn_v2_backward_acc(const float* input, const float* weight
                                          int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                                          int dh, int dw, int dg, void* workspace, size_t workspace_bytes,
                                          cnuda_stream_t stream) {
-    return dcn_backward_impl(input, weight, bias, offset, mask, grad_output, columns, grad_input, accumulate_input, grad_offset,
-                             grad_mask, grad_weight, grad_bias, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, workspace,
-                             workspace_bytes, stream, nullptr);
+    DcnBwdCall c{};
+    if (int rc = fill_geom(c.g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_backward")) return rc;
+    c.input = input; c.weight = weight; c.bias = bias; c.offset = offset; c.mask = mask;
+    c.grad_output = grad_output; c.columns = columns; c.grad_input = grad_input; c.accumulate_input = accumulate_input;
+    c.grad_offset = grad_offset; c.grad_mask = grad_mask; c.grad_weight = grad_weight; c.grad_bias = grad_bias;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return dcn_backward_impl(c, make_plan(c.g));
 }
 
-// Offsets and mask read straight out of `om`, the 3T-channel output of DCN's own offset convolution
-// (libs/DCNv2/dcn_v2.py:118-122: o1, o2, mask = chunk(out, 3); offset = cat(o1, o2); mask = sigmoid(mask)): rows 0 .. 2T-1
-// ARE the offsets, rows 2T .. 3T-1 the mask -- ALREADY sigmoid (cnuda_conv2d_forward_rowsig applies it in the
-// convolution's epilogue) -- and the backward writes one tensor `gom` of the same shape: the offsets' gradient and the
-// gradient of the mask's LOGIT (the walk multiplies by m (1 - m) where it stores).  No split / concatenate / sigmoid passes:
-// 32 launches of a benched step and two tensors per layer less (round 6).  deformable_group == 1.
-extern "C" int cnuda_dcn_v2_forward_om(const float* input, const float* weight, const float* bias, const float* om,
-                                       float* output, float* columns, float* stats, int stats_block, int stats_rows,
-                                       float act_slope, int B,
-                                       int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
-                                       int dw, int dg, void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
-    CNUDA_REQUIRE(om && dg == 1 && W >= 2, "cnuda_dcn_v2_forward_om: needs deformable_group == 1 and width >= 2");
-    DcnGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_forward_om")) return rc;
-    if (stats) {
-        int rows = 0;
-        const int blk = cnuda_dcn_v2_stats_block(B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, &rows);
-        CNUDA_REQUIRE(blk != 0 && blk == stats_block && rows == stats_rows,
-                      "cnuda_dcn_v2_forward_om: the statistics buffer was sized for blocks of %d pixels x %d rows, this call "
-                      "writes %d x %d", stats_block, stats_rows, blk, rows);
-    }
-    CNUDA_REQUIRE(!stats || act_slope < 0.0f, "cnuda_dcn_v2_forward_om: statistics are those of the output before an activation");
-    const int s3 = 3 * kh * kw * g.Ho * g.Wo;      // offsets and mask are rows of one 3T-channel tensor
-    const DcnStrides ss{s3, s3, 0, 0, 0};
-    return dcn_forward_impl(input, weight, bias, om, om + (size_t)2 * kh * kw * g.Ho * g.Wo, output, columns, stats, act_slope, B, C,
-                            H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, workspace, workspace_bytes, stream, &ss);
-}
+// the backward of cnuda_dcn_v2_forward_om: one gradient tensor for `om`, its mask rows the gradient of the mask's LOGIT
 extern "C" int cnuda_dcn_v2_backward_om(const float* input, const float* weight, const float* bias, const float* om,
                                         const float* grad_output, const float* columns, float* grad_input,
                                         int accumulate_input, float* grad_om, float* grad_weight, float* grad_bias, int B,
                                         int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
                                         int dw, int dg, void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
     CNUDA_REQUIRE(om && grad_om && dg == 1 && W >= 2, "cnuda_dcn_v2_backward_om: needs deformable_group == 1 and width >= 2");
-    DcnGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_backward_om")) return rc;
+    DcnBwdCall c{};
+    if (int rc = fill_geom(c.g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_backward_om")) return rc;
+    DcnGeom& g = c.g;
     const size_t mo = (size_t)2 * kh * kw * g.Ho * g.Wo;
-    const int s3 = 3 * kh * kw * g.Ho * g.Wo;      // offsets / mask and their gradients as rows of 3T-channel tensors; the mask's as its logit's
-    const DcnStrides ss{s3, s3, s3, s3, 1};
-    return dcn_backward_impl(input, weight, bias, om, om + mo, grad_output, columns, grad_input, accumulate_input, grad_om,
-                             grad_om + mo, grad_weight, grad_bias, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, workspace,
-                             workspace_bytes, stream, &ss);
-}
-
-static int dcn_backward_impl(const float* input, const float* weight, const float* bias,
-                             const float* offset, const float* mask, const float* grad_output,
-                             const float* columns, float* grad_input, int accumulate_input,
-                             float* grad_offset, float* grad_mask, float* grad_weight, float* grad_bias, int B,
-                             int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
-                             int dh, int dw, int dg, void* workspace, size_t workspace_bytes,
-                             cnuda_stream_t stream, const DcnStrides* strides) {
-    CNUDA_REQUIRE(!columns || W >= 2, "cnuda_dcn_v2_backward_cols: columns input needs width >= 2");
-    CNUDA_REQUIRE(input && weight && offset && mask && grad_output && grad_input && grad_offset && grad_mask &&
-                      grad_weight && grad_bias,
-                  "cnuda_dcn_v2_backward: null pointer");
-    (void)bias;
-    DcnGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg, "cnuda_dcn_v2_backward")) return rc;
-    if (strides) {
-        if (strides->off_bs) g.off_bs = strides->off_bs;
-        if (strides->mask_bs) g.mask_bs = strides->mask_bs;
-        if (strides->goff_bs) g.goff_bs = strides->goff_bs;
-        if (strides->gmask_bs) g.gmask_bs = strides->gmask_bs;
-        g.gmask_logit = strides->gmask_logit;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int T = kh * kw, HoWo = g.Ho * g.Wo;
-    const DcnPlan q = make_plan(g);
-    if (q.fwd == DcnFwdPath::Composed) {
-        // deformable_group > 1, composed from the deformable_group = 1 kernels (see dcn_forward_impl): per group the data
-        // gradient of its C / dg input channels, its rows of grad_offset / grad_mask (written in place through the batch strides
-        // of the dg-group tensors) and its slice of grad_weight; grad_bias by the first group's call
-        const int Cg = C / dg;
-        const long long HW = (long long)H * W;
-        const size_t inner = cnuda_dcn_v2_workspace_bytes(B, Cg, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, 1);
-        Carver cv(workspace, workspace_bytes);
-        float* xg = cv.take<float>((size_t)B * Cg * HW);
-        float* wg = cv.take<float>((size_t)Cout * Cg * T);
-        float* ging = cv.take<float>((size_t)B * Cg * HW);
-        float* gwg = cv.take<float>((size_t)Cout * Cg * T);
-        float* gbt = cv.take<float>((size_t)Cout);
-        void* iws = cv.take<char>(inner);
-        CNUDA_REQUIRE(workspace && cv.cur <= cv.end, "cnuda_dcn_v2_backward: workspace too small");
-        const DcnStrides gs{dg * 2 * T * HoWo, dg * T * HoWo, dg * 2 * T * HoWo, dg * T * HoWo, 0};
-        const PackStampSuspend uncached;       // (`wg` and the inner calls' transposed weights: one buffer for every group)
-        for (int grp = 0; grp < dg; ++grp) {
-            if (int rc = cnuda_copy_channels(input, xg, B, Cg, HW, C, grp * Cg, Cg, 0, stream)) return rc;
-            if (int rc = cnuda_copy_channels(weight, wg, Cout, Cg, T, C, grp * Cg, Cg, 0, stream)) return rc;
-            // (a caller's running sum in grad_input: the group's slice goes in, is added to, and comes back)
-            if (accumulate_input)
-                if (int rc = cnuda_copy_channels(grad_input, ging, B, Cg, HW, C, grp * Cg, Cg, 0, stream)) return rc;
-            if (int rc = dcn_backward_impl(xg, wg, bias, offset + (size_t)grp * 2 * T * HoWo, mask + (size_t)grp * T * HoWo,
-                                           grad_output, columns ? columns + (size_t)grp * B * T * Cg * HoWo : nullptr, ging,
-                                           accumulate_input, grad_offset + (size_t)grp * 2 * T * HoWo,
-                                           grad_mask + (size_t)grp * T * HoWo, gwg, grp == 0 ? grad_bias : gbt, B, Cg, H, W, Cout,
-                                           kh, kw, sh, sw, ph, pw, dh, dw, 1, iws, inner, stream, &gs))
-                return rc;
-            if (int rc = cnuda_copy_channels(ging, grad_input, B, Cg, HW, Cg, 0, C, grp * Cg, stream)) return rc;
-            if (int rc = cnuda_copy_channels(gwg, grad_weight, Cout, Cg, T, Cg, 0, C, grp * Cg, stream)) return rc;
-        }
-        return check_launch("cnuda_dcn_v2_backward(dg>1)");
-    }
-    // (every data-gradient walk below ADDS into grad_input -- window flushes and strays are atomics -- so a caller that
-    // already holds another consumer's share of the input's gradient there passes accumulate_input and saves the sum)
-    // (deformable_group == 1: dcn_prep_kernel clears it beside its other work -- one launch less per layer; the walks run
-    // behind it on the same stream)
-    const long long gin_elems = (long long)B * C * H * W;
-    const bool zero_in_prep = !accumulate_input && dg == 1 && (gin_elems & 3) == 0 && (reinterpret_cast<uintptr_t>(grad_input) & 15) == 0;
-    if (!accumulate_input && !zero_in_prep &&
-        hipMemsetAsync(grad_input, 0, (size_t)gin_elems * sizeof(float), st) != hipSuccess)
-        return check_launch("cnuda_dcn_v2_backward(memset)");
-    if (dg != 1) {
-        launch_channel_sum(grad_output, grad_bias, B, Cout, HoWo, st);
-        (void)hipMemsetAsync(grad_offset, 0, (size_t)B * dg * 2 * T * HoWo * sizeof(float), st);
-        (void)hipMemsetAsync(grad_mask, 0, (size_t)B * dg * T * HoWo * sizeof(float), st);
-        (void)hipMemsetAsync(grad_weight, 0, (size_t)Cout * C * T * sizeof(float), st);
-        DcnNaiveParams p{g, input, weight, nullptr, offset, mask, grad_output, nullptr,
-                         grad_input, grad_offset, grad_mask, grad_weight};
-        CNUDA_LAUNCH(dcn_naive_bwd_kernel, dim3(stream_grid((long long)B * C * T * HoWo, 256)), dim3(256), 0, st,
-                           p);
-        return check_launch("cnuda_dcn_v2_backward(dg>1)");
-    }
-    CNUDA_REQUIRE(workspace && workspace_bytes >= q.bwd_bytes, "cnuda_dcn_v2_backward: workspace too small");
-    Carver cv(workspace, workspace_bytes);
-    float* slabs = cv.take<float>((size_t)q.Z * q.Mpw * q.Jp);
-    float* bsl = cv.take<float>(std::max((size_t)Cout * B, (size_t)q.Z * q.Mpw));    // bias row sums per split: [Z][Mpw]
-    float* wt = cv.take<float>((size_t)12 * C * (Cout < 64 ? 64 : Cout));   // (or the window kernels' packs: [64][10 C], [12 C][64])
-    float* dcol = cv.take<float>((size_t)B * q.T * C * HoWo);
-    DcnGeo* geo = cv.take<DcnGeo>((size_t)B * q.T * HoWo);
-    void* gemm_ws = cv.take<char>(q.gemm_bytes);
-    // (running the weight gradient on a second stream beside the data-gradient chain was tried in round 2: the
-    // kernels do overlap but contend for the same LDS / issue slots -- nothing gained, removed)
-    hipStream_t wst = st;
-    // every timed scope below is recorded under the call's tag; sub 0: the column-gradient 1x1 GEMM (its own scope
-    // inside cnuda_conv2d_forward), 1: coord_grad, 2: col2im, 3: both as one launch, 4: the weight-gradient GEMM
-    ProfGroup prof;
-    // (2) weight gradient (and, from the same staging registers, the bias gradient: bsl -> slab reduce)
-    {
-      bool found;
-      {
-        ProfScope wscope(st, 4);
-        if (columns) {
-            DcnColWParams p{g, columns, grad_output};
-            wscope.name(q.colw_ws ? "igemm_wgrad_ws_kernel<%s, 64, %d>" : "igemm_wgrad_kernel<%s, 64, %d>",
-                        q.colw_buf ? "DcnColWBufLoader" : "DcnColWLoader", q.wbj);
-            found = q.colw_ws    ? launch_dcn_wgrad<DcnColWBufLoader, true, 64, 128>(q, q.wbj, p, slabs, bsl, wst)
-                    : q.colw_buf ? launch_dcn_wgrad<DcnColWBufLoader, false, 64, 128>(q, q.wbj, p, slabs, bsl, wst)
-                                 : launch_dcn_wgrad<DcnColWLoader, false, 64, 128>(q, q.wbj, p, slabs, bsl, wst);
-        } else {
-            DcnWParams p{g, input, offset, mask, grad_output};
-            wscope.name("igemm_wgrad_kernel<DcnWLoader, 64, 64>");
-            found = launch_dcn_wgrad<DcnWLoader, false, 64>(q, WG_BJ, p, slabs, bsl, wst);
-        }
-      }
-        CNUDA_REQUIRE(found, "cnuda_dcn_v2_backward: no weight-gradient instance for %d-column tiles", q.wbj);
-        if (int rc = check_launch("cnuda_dcn_v2_backward(weight)")) return rc;
-        launch_slab_reduce(slabs, grad_weight, q.Z, q.Mpw, q.Jp, Cout, C, q.T, wst, bsl, grad_bias);
-    }
-    {
-        // (1) dcol = W^T x grad_output as a 1x1 implicit GEMM, then the two streaming consumers
-        {
-            // transposed weights of the 1x1 GEMM + (fused form) the geometry records, one launch
-            const int wt_blocks = stream_grid((long long)q.T * C * Cout, 256);
-            const int geo_blocks = q.fused_consumers ? stream_grid((long long)B * q.T * HoWo, 256) : 0;
-            const int zero_blocks = zero_in_prep ? stream_grid(gin_elems / 4, 256) : 0;
-            DcnPrepParams pp{g, weight, offset, mask, wt, q.fused_consumers ? geo : nullptr, wt_blocks,
-                             zero_in_prep ? grad_input : nullptr, gin_elems / 4, wt_blocks + geo_blocks};
-            CNUDA_LAUNCH(dcn_prep_kernel, dim3(wt_blocks + geo_blocks + zero_blocks), dim3(256), 0, st, pp);
-        }
-        const bool quads = q.dcol_quads;
-        if (int rc = quads ? cnuda_conv2d_forward_rowquads(grad_output, wt, dcol, B, Cout, g.Ho, g.Wo, q.T * C, 1, 1, 1, 1, 0, 0,
-                                                           gemm_ws, q.gemm_bytes, stream)
-                           : cnuda_conv2d_forward(grad_output, wt, nullptr, dcol, B, Cout, g.Ho, g.Wo, q.T * C, 1, 1, 1, 1, 0,
-                                                  0, -1.0f, gemm_ws, q.gemm_bytes, stream))
-            return rc;
-        if (q.fused_consumers) {
-            DcnBwdDataParams p{g, input, dcol, geo, grad_input, grad_offset, grad_mask, q.tile, q.fused_split};
-            const int n_wg = B * q.tile.tiles_y * q.tile.tiles_x * q.fused_split;
-            ProfScope scope(st, 3);
-            scope.name("dcn_bwd_data_kernel");
-            if (int rc = with_quads(quads, [&](auto Q) -> int {
-                    // (a wide-margin window: dynamic LDS beyond 64 KiB is opt-in)
-                    CNUDA_REQUIRE(raise_dynamic_lds(reinterpret_cast<const void*>(&dcn_bwd_data_kernel<Q()>), q.col2im_lds),
-                                  "cnuda_dcn_v2_backward: dynamic LDS");
-                    CNUDA_LAUNCH((dcn_bwd_data_kernel<Q()>), dim3(n_wg), dim3(512), q.col2im_lds, st, p, n_wg);
-                    return 0;
-                }))
-                return rc;
-        } else {
-            {
-                DcnCoordParams p{g, input, offset, mask, dcol, grad_offset, grad_mask, geo};
-                const int tiles = ceil_div(HoWo, 64), tw = q.T < 16 ? q.T : 16;
-                ProfScope scope(st, 1);
-                scope.name("dcn_coord_grad_kernel");
-                with_quads(quads, [&](auto Q) {
-                    CNUDA_LAUNCH((dcn_coord_grad_kernel<Q()>), dim3(B * tiles), dim3(64, tw), 0, st, p, tiles);
-                });
-            }
-            {
-                DcnCol2imParams p{g, dcol, geo, grad_input, q.tile};
-                const int n_wg = B * q.tile.tiles_y * q.tile.tiles_x * q.tile.ncg;
-                ProfScope scope(st, 2);
-                scope.name("dcn_col2im_kernel");
-                if (int rc = with_quads(quads, [&](auto Q) -> int {
-                        CNUDA_REQUIRE(raise_dynamic_lds(reinterpret_cast<const void*>(&dcn_col2im_kernel<Q()>), q.col2im_lds),
-                                      "cnuda_dcn_v2_backward: dynamic LDS");
-                        CNUDA_LAUNCH((dcn_col2im_kernel<Q()>), dim3(n_wg), dim3(256), q.col2im_lds, st, p, n_wg);
-                        return 0;
-                    }))
-                    return rc;
-            }
-        }
-        if (int rc = check_launch("cnuda_dcn_v2_backward(data)")) return rc;
-    }
-    return check_launch("cnuda_dcn_v2_backward");
+    // offsets / mask and their gradients as rows of 3T-channel tensors; the mask's as its logit's
+    g.off_bs = g.mask_bs = g.goff_bs = g.gmask_bs = 3 * kh * kw * g.Ho * g.Wo;
+    g.gmask_logit = 1;
+    c.input = input; c.weight = weight; c.bias = bias; c.offset = om; c.mask = om + mo;
+    c.grad_output = grad_output; c.columns = columns; c.grad_input = grad_input; c.accumulate_input = accumulate_input;
+    c.grad_offset = grad_om; c.grad_mask = grad_om + mo; c.grad_weight = grad_weight; c.grad_bias = grad_bias;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return dcn_backward_impl(c, make_plan(c.g));
 }

@@ -391,6 +391,22 @@ def workspace(nbytes, device):
     return buf
 
 
+def stats_side_output(box, query, geom, HoWo, device, per_image=False):
+    """The BatchNorm statistics a forward kernel's epilogue leaves beside its output: asks `query` (cnuda_conv2d_stats_block,
+    or cnuda_dcn_v2_stats_block, which has no blocks-per-image result: per_image False) how the call of geometry `geom`
+    (B first) cuts them, makes the buffer and appends the record batch_norm_act reads to `box`:
+    (stats, pixels per block on the flattened (image, pixel) axis -- or 0 --, rows, blocks per image -- or 0).
+    -> that record, or None where this geometry's kernel leaves no statistics."""
+    rows, bpi = ctypes.c_int(0), ctypes.c_int(0)
+    blk = query(*geom, ctypes.byref(rows), *([ctypes.byref(bpi)] if per_image else []))
+    if not blk:
+        return None
+    nblk = geom[0] * bpi.value if bpi.value else (geom[0] * HoWo + 127) // 128 * (128 // blk)
+    stats = torch.empty((nblk, rows.value, 2), dtype=torch.float32, device=device)
+    box.append((stats, 0 if bpi.value else blk, rows.value, bpi.value))
+    return box[-1]
+
+
 # ---------------------------------------------------------------------------
 # kernel timer used by bench.py (hipEvents recorded inside the library around the
 # main implicit-GEMM launch of a call, on the launch stream)

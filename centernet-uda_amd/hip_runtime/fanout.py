@@ -101,6 +101,19 @@ def first_writer(slot, like):
     return claim(slot, torch.empty_like(like))
 
 
+def accumulate_in_place(slot):
+    """A consumer that ADDS its share to whatever its output buffer holds (DCN's data-gradient atomics, max-pooling's
+    scatter, a head on the leading images): -> the slot's buffer, now recorded as including that share, when the slot owns
+    one; None otherwise -- the consumer then makes its own gradient (`claim` / `first_writer`)."""
+    if slot is None:
+        return None
+    slot = slot.root()
+    if slot._buf is None or not slot._owned:
+        return None
+    slot._included.append(slot._buf)
+    return slot._buf
+
+
 def accumulate_target(slot, like):
     """For a consumer that can add what the slot holds while it writes (convolution input gradient):
     -> (out, addend, addend2): write `out = own share + addend + addend2` (None: nothing to add).  The slot then holds `out`."""

@@ -2,13 +2,15 @@
 gfx950 kernels from libcenternet_uda_hip.so on torch's current HIP stream;
 torch contributes tensors (device memory), the autograd tape and nothing else.
 """
+import ctypes
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import check, f32c, lib, pack_stamp, prof_arm, ptr, require_gpu, stream, workspace
+from . import check, f32c, lib, pack_stamp, prof_arm, ptr, require_gpu, stats_side_output, stream, workspace
 from .arena import grad_sink
-from .fanout import accumulate_target, claim, first_writer, slot_of
+from .fanout import accumulate_in_place, accumulate_target, claim, first_writer, slot_of
 
 
 def _pair(v):
@@ -70,14 +72,8 @@ class _Conv2d(Function):
         stats = None
         if stats_box is not None and act_slope < 0:
             # BatchNorm statistics of y from the GEMM's epilogue, where this geometry's kernel can give them
-            import ctypes
-            rows, bpi = ctypes.c_int(0), ctypes.c_int(0)
-            blk = L.cnuda_conv2d_stats_block(*g, ctypes.byref(rows), ctypes.byref(bpi))
-            if blk:
-                # (stats, pixels per block on the flattened (image, pixel) axis -- or 0 --, rows, blocks per image -- or 0)
-                nblk = B * bpi.value if bpi.value else (B * Ho * Wo + 127) // 128 * (128 // blk)
-                stats = torch.empty((nblk, rows.value, 2), dtype=torch.float32, device=x.device)
-                stats_box.append((stats, 0 if bpi.value else blk, rows.value, bpi.value))
+            rec = stats_side_output(stats_box, L.cnuda_conv2d_stats_block, g, Ho * Wo, x.device, per_image=True)
+            stats = rec and rec[0]
         prof_arm('conv_fwd', B, C, H, W, Co, kh, kw, Ho, Wo)
         with pack_stamp(pack_token, weight):
             if norm is not None:
@@ -153,6 +149,19 @@ def conv2d_rowsig(x, weight, bias, stride, padding, sig_from, pack_token=0):
 EPILOGUE_STATS = True      # (A/B measurements flip it: profiles/microbench/ab_bn_stats.py)
 
 
+def with_bn_stats(emit, call):
+    """y = call(stats_box).  emit: the caller's next layer is a train-mode BatchNorm over y -- where the producing kernel can,
+    it leaves sum / sum of squares per (pixel block, channel) beside y (the node appends the record to its stats_box);
+    batch_norm_act finds them on the tensor.  Otherwise, or with EPILOGUE_STATS off, the node gets no box."""
+    if not (emit and EPILOGUE_STATS):
+        return call(None)
+    box = []
+    y = call(box)
+    if box:
+        y._cnuda_bn_stats = box[0]
+    return y
+
+
 def conv2d(x, weight, bias=None, stride=1, padding=0, act_slope=-1.0, pack_token=0, emit_stats=False):
     """y = act(conv2d(x, weight) + bias); act_slope < 0 none, 0 ReLU, 0.2 LeakyReLU(0.2).  pack_token: identity of
     the module that owns `weight` (hip_runtime.new_pack_token) -- lets the library keep the packed weight image
@@ -163,15 +172,8 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act_slope=-1.0, pack_token
         if not lib().cnuda_conv2d_norm_input_supported(*g):
             raise RuntimeError("conv2d: the input is a deferred BatchNorm output, but no apply-on-load kernel takes this "
                                "convolution (cnuda_conv2d_norm_input_supported); ask batch_norm_act to apply it")
-    if not (emit_stats and EPILOGUE_STATS):
-        return _Conv2d.apply(x, weight, bias, stride, padding, float(act_slope), pack_token, None, norm, None)
-    # emit_stats: the caller's next layer is a train-mode BatchNorm over y.  Where the kernel can, it leaves
-    # sum / sum of squares per (pixel block, channel) beside y; batch_norm_act finds them on the tensor.
-    box = []
-    y = _Conv2d.apply(x, weight, bias, stride, padding, float(act_slope), pack_token, box, norm, None)
-    if box:
-        y._cnuda_bn_stats = box[0]
-    return y
+    return with_bn_stats(emit_stats, lambda box: _Conv2d.apply(x, weight, bias, stride, padding, float(act_slope), pack_token,
+                                                               box, norm, None))
 
 
 class _ConvActConv1x1(Function):
@@ -244,11 +246,9 @@ class _ConvActConv1x1(Function):
             if ctx.full is None:
                 gx, addend, addend2 = accumulate_target(slot, x)
                 part = gx
-            elif slot is not None and slot.buf is not None and slot.owned:
-                gx = slot.buf                                   # the leading images' share lands on top of the slot's total
-                part = addend = gx[:B]
+            elif (gx := accumulate_in_place(slot)) is not None:
+                part = addend = gx[:B]                          # the leading images' share lands on top of the slot's total
                 addend2 = None
-                slot.included.append(gx)
             else:
                 gx = claim(slot, torch.empty(ctx.full, dtype=torch.float32, device=x.device))
                 gx[B:].zero_()
@@ -509,13 +509,10 @@ class _MaxPool(Function):
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
         B, C, H, W = x.shape
-        slot = ctx.slot
-        if slot is not None and slot.buf is not None and slot.owned:
-            # another consumer's share is already in the slot's own buffer: only the arg-max cells are touched (+=)
-            gx, acc = slot.buf, 1
-            slot.included.append(gx)
-        else:
-            gx, acc = first_writer(slot, x), 0
+        # another consumer's share already in the slot's own buffer: only the arg-max cells are touched (+=)
+        gx, acc = accumulate_in_place(ctx.slot), 1
+        if gx is None:
+            gx, acc = first_writer(ctx.slot, x), 0
         check(lib().cnuda_maxpool2d_backward_acc(ptr(x), ptr(f32c(gy)), ptr(gx), acc, B, C, H, W, ctx.k, stream()),
               'maxpool2d_backward')
         return gx, None
@@ -697,7 +694,6 @@ def cat_channels(xs):
 
 
 def _ptr_array(ts):
-    import ctypes
     return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
 
 
@@ -708,7 +704,6 @@ class _CatConv1x1(Function):
 
     @staticmethod
     def forward(ctx, weight, pack_token, stats_box, *xs):
-        import ctypes
         require_gpu(weight, *xs)
         ctx.slots = [slot_of(t) for t in xs]
         xs = [f32c(t) for t in xs]
@@ -727,12 +722,8 @@ class _CatConv1x1(Function):
         wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), y)
         stats = None
         if stats_box is not None:
-            rows, bpi = ctypes.c_int(0), ctypes.c_int(0)
-            blk = L.cnuda_conv2d_stats_block(*g, ctypes.byref(rows), ctypes.byref(bpi))
-            if blk:
-                nblk = B * bpi.value if bpi.value else (B * H * W + 127) // 128 * (128 // blk)
-                stats = torch.empty((nblk, rows.value, 2), dtype=torch.float32, device=weight.device)
-                stats_box.append((stats, 0 if bpi.value else blk, rows.value, bpi.value))
+            rec = stats_side_output(stats_box, L.cnuda_conv2d_stats_block, g, H * W, weight.device, per_image=True)
+            stats = rec and rec[0]
         cs_arr = (ctypes.c_int * len(cs))(*cs)
         prof_arm('conv_fwd', B, sum(cs), H, W, Co, 1, 1, H, W)
         with pack_stamp(pack_token, weight):
@@ -745,7 +736,6 @@ class _CatConv1x1(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        import ctypes
         weight, xs = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         cs, n = ctx.cs, len(ctx.cs)
         B, _, H, W = xs[0].shape
@@ -782,7 +772,6 @@ class _CatConv1x1(Function):
 
 
 def _cat_supported(xs, weight):
-    import ctypes
     xs = list(xs)
     if not (2 <= len(xs) <= 4) or any(t.dim() != 4 or getattr(t, '_cnuda_deferred_bn', None) is not None for t in xs):
         return False
@@ -796,7 +785,6 @@ def _cat_supported(xs, weight):
 def conv1x1_cat_infer(xs, weight, bias=None, act_slope=-1.0, pack_token=0, pack_version=None):
     """Tape-free y = act(conv1x1(cat(xs, 1), weight) + bias) without the concatenation (a BatchNorm-folded Root, export.py),
     or None where no kernel takes the sources (the caller concatenates)."""
-    import ctypes
     xs = list(xs)
     if not _cat_supported(xs, weight):
         return None
@@ -825,13 +813,7 @@ def conv1x1_cat(xs, weight, pack_token=0, emit_stats=False):
     xs = list(xs)
     if not _cat_supported(xs, weight):
         return None
-    if not (emit_stats and EPILOGUE_STATS):
-        return _CatConv1x1.apply(weight, pack_token, None, *xs)
-    box = []
-    y = _CatConv1x1.apply(weight, pack_token, box, *xs)
-    if box:
-        y._cnuda_bn_stats = box[0]
-    return y
+    return with_bn_stats(emit_stats, lambda box: _CatConv1x1.apply(weight, pack_token, box, *xs))
 
 
 class _SplitOffsetMask(Function):

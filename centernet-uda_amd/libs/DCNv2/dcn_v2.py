@@ -8,17 +8,22 @@ reference (libs/DCNv2/dcn_v2.py:18-128), running on the MI355X kernels behind
 implicit-GEMM convolution (hip_runtime.nn.Conv2d), not a vendor library.
 """
 import math
+import os as _os
 
 import torch
 from torch import nn
 
 import _ext as _backend
+import hip_runtime as hr
+from hip_runtime import nn as hnn
+from hip_runtime import ops
+from hip_runtime.arena import grad_sink
+from hip_runtime.fanout import accumulate_in_place, claim, fork, slot_of
 
 
 # CNUDA_DCN_KEEP_COLS=0: the forward does not store the sampled columns and the weight gradient samples the input again
 # (the reference's scheme, dcn_v2_cuda.cu:302-319) -- an A/B switch for the measurement in DESIGN.md section 12; the
 # default keeps them (one 1 GB side output per 128 x 128 layer, read once by a plain-GEMM weight gradient)
-import os as _os
 _KEEP_COLUMNS = _os.environ.get('CNUDA_DCN_KEEP_COLS', '1') != '0'
 # CNUDA_DCN_OM=0 (or dcn_v2.USE_OM = False): DCN.forward materialises offset and mask tensors like the reference
 # (split + sigmoid kernel, its backward twin) instead of reading them out of the offset convolution's output
@@ -29,50 +34,50 @@ def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
 
+def _node_forward(ctx, fwd, input, sampling, weight, bias, geom, keep, pack_token, stats_box, regime):
+    """The forward of both autograd nodes.  sampling: (offset, mask) or (om,); fwd: the `_ext` function that takes them."""
+    ctx.regime = int(regime)       # offset regime of this layer (DCN._census): which kernels the library picks
+    ctx.slot = slot_of(input)      # where the offset convolution (the input's other consumer) meets this gradient
+    ctx.geom = geom
+    # keep the sampled columns (a side output of the forward kernel) for the weight gradient:
+    # on a 288 GB part re-reading ~0.3 GB per layer beats re-sampling the input (DESIGN.md)
+    keep = keep and any(ctx.needs_input_grad[:3 + len(sampling)]) and _KEEP_COLUMNS
+    with _offset_regime(ctx.regime):
+        out = fwd(input, weight, bias, *sampling, *geom, _want_columns=keep, _pack_token=pack_token, _stats_box=stats_box)
+    out, cols = out if isinstance(out, tuple) else (out, None)      # (dcn_v2_forward without columns: the output alone)
+    ctx.save_for_backward(input, *sampling, weight, bias, cols)
+    return out
+
+
+def _node_backward(ctx, bwd, grad_output):
+    """The backward of both nodes -> (grad_input, [the sampling tensors' gradients], grad_weight, grad_bias)."""
+    input, *sampling, weight, bias, cols = ctx.saved_tensors
+    sw, sb = grad_sink(weight), grad_sink(bias)       # arena slots: written by the kernels, not returned
+    # the data-gradient walks ADD into grad_input: on top of what the slot already holds when it is the slot's own
+    # buffer, else into a cleared tensor -- which an empty slot takes over
+    acc = accumulate_in_place(ctx.slot)
+    with _offset_regime(ctx.regime):
+        g_in, *g_sampling, g_w, g_b = bwd(input, weight, bias, *sampling, grad_output, *ctx.geom, _columns=cols,
+                                          _grad_weight=sw, _grad_bias=sb, _grad_input=acc)
+    if acc is None:
+        claim(ctx.slot, g_in)
+    return g_in, g_sampling, (None if sw is not None else g_w), (None if sb is not None else g_b)
+
+
 class _DeformConvFn(torch.autograd.Function):
     # autograd-visible argument order (dcn_v2.py:18-19): input, offset, mask, weight, bias, ...
     @staticmethod
     def forward(ctx, input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups, pack_token=0,
                 stats_box=None, regime=0):
-        kh, kw = weight.shape[2], weight.shape[3]
-        ctx.regime = int(regime)       # offset regime of this layer (DCN._census): which kernels the library picks
-        from hip_runtime.fanout import slot_of
-        ctx.slot = slot_of(input)      # where the offset convolution (the input's other consumer) meets this gradient
-        ctx.geom = (kh, kw) + _pair(stride) + _pair(padding) + _pair(dilation) + (deformable_groups,)
-        # keep the sampled columns (a side output of the forward kernel) for the weight gradient:
-        # on a 288 GB part re-reading ~0.3 GB per layer beats re-sampling the input
-        keep = input.shape[3] >= 2 and any(ctx.needs_input_grad[:5]) and _KEEP_COLUMNS
-        with _offset_regime(ctx.regime):
-            if keep:
-                out, cols = _backend.dcn_v2_forward(input, weight, bias, offset, mask, *ctx.geom, _want_columns=True,
-                                                    _pack_token=pack_token, _stats_box=stats_box)
-            else:
-                out, cols = _backend.dcn_v2_forward(input, weight, bias, offset, mask, *ctx.geom,
-                                                    _pack_token=pack_token, _stats_box=stats_box), None
-        ctx.save_for_backward(input, offset, mask, weight, bias, cols)
-        return out
+        geom = tuple(weight.shape[2:]) + _pair(stride) + _pair(padding) + _pair(dilation) + (deformable_groups,)
+        return _node_forward(ctx, _backend.dcn_v2_forward, input, (offset, mask), weight, bias, geom, input.shape[3] >= 2,
+                             pack_token, stats_box, regime)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        input, offset, mask, weight, bias, cols = ctx.saved_tensors
-        from hip_runtime.arena import grad_sink
-        sw, sb = grad_sink(weight), grad_sink(bias)       # arena slots: written by the kernels, not returned
-        # the data-gradient walks ADD into grad_input: on top of what the slot already holds when it is the slot's own
-        # buffer, else into a cleared tensor -- which an empty slot takes over
-        slot = ctx.slot
-        acc = slot.buf if (slot is not None and slot.buf is not None and slot.owned) else None
-        with _offset_regime(ctx.regime):
-            g_in, g_off, g_mask, g_w, g_b = _backend.dcn_v2_backward(
-                input, weight, bias, offset, mask, grad_output, *ctx.geom, _columns=cols, _grad_weight=sw, _grad_bias=sb,
-                _grad_input=acc)
-        if acc is None:
-            from hip_runtime.fanout import claim
-            claim(slot, g_in)
-        else:
-            slot.included.append(acc)
-        return g_in, g_off, g_mask, (None if sw is not None else g_w), (None if sb is not None else g_b), \
-            None, None, None, None, None, None, None
+        g_in, (g_off, g_mask), g_w, g_b = _node_backward(ctx, _backend.dcn_v2_backward, grad_output)
+        return g_in, g_off, g_mask, g_w, g_b, None, None, None, None, None, None, None
 
 
 class _DeformConvOmFn(torch.autograd.Function):
@@ -83,36 +88,15 @@ class _DeformConvOmFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, om, weight, bias, stride, padding, dilation, pack_token=0, stats_box=None, regime=0):
-        kh, kw = weight.shape[2], weight.shape[3]
-        ctx.regime = int(regime)
-        from hip_runtime.fanout import slot_of
-        ctx.slot = slot_of(input)
-        ctx.geom = (kh, kw) + _pair(stride) + _pair(padding) + _pair(dilation)
-        keep = any(ctx.needs_input_grad[:4]) and _KEEP_COLUMNS
-        with _offset_regime(ctx.regime):
-            out, cols = _backend.dcn_v2_forward_om(input, weight, bias, om, *ctx.geom, _want_columns=keep,
-                                                   _pack_token=pack_token, _stats_box=stats_box)
-        ctx.save_for_backward(input, om, weight, bias, cols)
-        return out
+        geom = tuple(weight.shape[2:]) + _pair(stride) + _pair(padding) + _pair(dilation)
+        return _node_forward(ctx, _backend.dcn_v2_forward_om, input, (om,), weight, bias, geom, True, pack_token, stats_box,
+                             regime)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        input, om, weight, bias, cols = ctx.saved_tensors
-        from hip_runtime.arena import grad_sink
-        sw, sb = grad_sink(weight), grad_sink(bias)
-        slot = ctx.slot
-        acc = slot.buf if (slot is not None and slot.buf is not None and slot.owned) else None
-        with _offset_regime(ctx.regime):
-            g_in, g_om, g_w, g_b = _backend.dcn_v2_backward_om(input, weight, bias, om, grad_output, *ctx.geom, _columns=cols,
-                                                               _grad_weight=sw, _grad_bias=sb, _grad_input=acc)
-        if acc is None:
-            from hip_runtime.fanout import claim
-            claim(slot, g_in)
-        else:
-            slot.included.append(acc)
-        return g_in, g_om, (None if sw is not None else g_w), (None if sb is not None else g_b), \
-            None, None, None, None, None, None
+        g_in, (g_om,), g_w, g_b = _node_backward(ctx, _backend.dcn_v2_backward_om, grad_output)
+        return g_in, g_om, g_w, g_b, None, None, None, None, None, None
 
 
 class _offset_regime:
@@ -124,11 +108,9 @@ class _offset_regime:
         self.prev = 0
 
     def __enter__(self):
-        import hip_runtime as hr
         self.prev = hr.lib().cnuda_dcn_set_offset_regime(self.regime)
 
     def __exit__(self, *exc):
-        import hip_runtime as hr
         hr.lib().cnuda_dcn_set_offset_regime(self.prev)
 
 
@@ -136,16 +118,8 @@ def dcn_v2_conv(input, offset, mask, weight, bias, stride, padding, dilation, de
                 emit_stats=False, regime=0):
     """emit_stats (not part of the reference's signature): the output goes straight into a train-mode BatchNorm -- the
     kernel's epilogue then leaves the statistics with it (hip_runtime.ops.batch_norm_act finds them on the tensor)."""
-    from hip_runtime import ops
-    if not (emit_stats and ops.EPILOGUE_STATS):
-        return _DeformConvFn.apply(input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups, pack_token,
-                                   None, regime)
-    box = []
-    out = _DeformConvFn.apply(input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups, pack_token, box,
-                              regime)
-    if box:
-        out._cnuda_bn_stats = box[0]
-    return out
+    return ops.with_bn_stats(emit_stats, lambda box: _DeformConvFn.apply(
+        input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups, pack_token, box, regime))
 
 
 class DCNv2(nn.Module):
@@ -158,7 +132,6 @@ class DCNv2(nn.Module):
         self.deformable_groups = deformable_groups
         self.weight = nn.Parameter(torch.empty(out_channels, in_channels, *self.kernel_size))
         self.bias = nn.Parameter(torch.empty(out_channels))
-        import hip_runtime as hr
         self._pack_token = hr.PackToken()           # identity of these weights for the library's pack cache
         self.reset_parameters()
 
@@ -182,7 +155,6 @@ class DCN(DCNv2):
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation=1,
                  deformable_groups=1):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, deformable_groups)
-        from hip_runtime import nn as hnn
         taps = self.deformable_groups * self.kernel_size[0] * self.kernel_size[1]
         self.conv_offset_mask = hnn.Conv2d(in_channels, 3 * taps, self.kernel_size, self.stride,
                                            self.padding, bias=True)
@@ -195,8 +167,6 @@ class DCN(DCNv2):
             self.conv_offset_mask.bias.zero_()
 
     def forward(self, input):
-        from hip_runtime import ops
-        from hip_runtime.fanout import fork
         # the input feeds the offset / mask convolution AND the sampling: their gradients meet in a slot, not in the engine
         input_om, input = fork(input, 2)
         taps = self.kernel_size[0] * self.kernel_size[1]
@@ -209,24 +179,16 @@ class DCN(DCNv2):
             # offsets and mask out of its one output tensor (no split kernels, no offset / mask tensors of their own)
             om = ops.conv2d_rowsig(input_om, cm.weight, cm.bias, cm.stride, cm.padding, 2 * taps, cm._pack_token)
             if om is not None:
-                if self.training:
-                    self._census_calls += 1
-                    if self._census_calls % self.CENSUS_EVERY == 1:
-                        self._regime = self._census(om.detach()[:, :2 * taps].contiguous())
-                box = [] if (self.emit_stats and self.training and ops.EPILOGUE_STATS) else None
-                out = _DeformConvOmFn.apply(input, om, self.weight, self.bias, self.stride, self.padding, self.dilation,
-                                            self._pack_token, box, self._regime)
-                if box:
-                    out._cnuda_bn_stats = box[0]
-                return out
+                self._take_census(lambda: om.detach()[:, :2 * taps].contiguous())
+                return ops.with_bn_stats(self.emit_stats and self.training, lambda box: _DeformConvOmFn.apply(
+                    input, om, self.weight, self.bias, self.stride, self.padding, self.dilation, self._pack_token, box,
+                    self._regime))
         om = cm(input_om)
         # channels [0, 2*taps) are offsets (chunks o1|o2 re-concatenated, dcn_v2.py:120-121),
         # [2*taps, 3*taps) the mask logits
         offset, mask = ops.split_offset_mask(om)
-        if self.training and self.deformable_groups == 1:
-            self._census_calls += 1
-            if self._census_calls % self.CENSUS_EVERY == 1:
-                self._regime = self._census(offset)
+        if self.deformable_groups == 1:
+            self._take_census(lambda: offset)
         return dcn_v2_conv(input, offset, mask, self.weight, self.bias, self.stride, self.padding,
                            self.dilation, self.deformable_groups, self._pack_token,
                            emit_stats=self.emit_stats and self.training, regime=self._regime)
@@ -236,8 +198,14 @@ class DCN(DCNv2):
     # (profiles/r5_dcn_margin_sweep.txt, r4_dcnw_large_offsets.txt: the crossovers sit near sigma = 0.75 px and 1.25 px)
     CENSUS_SHARES = (0.015, 0.03)
 
+    def _take_census(self, offsets):
+        """Every CENSUS_EVERY-th training forward: the regime from a census of offsets() -- [B, 2 * taps, Ho, Wo], contiguous."""
+        if self.training:
+            self._census_calls += 1
+            if self._census_calls % self.CENSUS_EVERY == 1:
+                self._regime = self._census(offsets())
+
     def _census(self, offset):
-        import hip_runtime as hr
         off = offset.detach()
         B, HW = off.shape[0], off.shape[2] * off.shape[3]
         taps = off.shape[1] // 2
