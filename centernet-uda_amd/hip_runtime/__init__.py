@@ -115,6 +115,16 @@ class _Sig:
     cnuda_dwconv2d_workspace_bytes = (c_size_t, [_I] * 3)
     cnuda_dwconv2d_forward = (_I, [_P] * 3 + [_I] * 7 + [_P])
     cnuda_dwconv2d_backward = (_I, [_P] * 5 + [_I] * 7 + _WS)
+    cnuda_dwconv2d_same_workspace_bytes = (c_size_t, [_I] * 3)
+    cnuda_dwconv2d_same_forward = (_I, [_P] * 3 + [_I] * 10 + [_P])
+    cnuda_dwconv2d_same_backward = (_I, [_P] * 5 + [_I] * 10 + _WS)
+    cnuda_swish_forward = (_I, [_P] * 2 + [_LL, _P])
+    cnuda_swish_backward = (_I, [_P] * 3 + [_LL, _P])
+    cnuda_se_workspace_bytes = (c_size_t, [_I] * 3)
+    cnuda_se_forward = (_I, [_P] * 9 + [_I] * 3 + [_LL, _P])
+    cnuda_se_backward = (_I, [_P] * 12 + [_I] * 3 + [_LL] + _WS)
+    cnuda_drop_connect_add = (_I, [_P] * 4 + [_I, _LL, _P])
+    cnuda_pad_right_bottom = (_I, [_P] * 2 + [_LL] + [_I] * 4 + [_P])
     cnuda_add = (_I, [_P] * 3 + [_LL, _P])
     cnuda_act_backward = (_I, [_P] * 3 + [_LL, _F, _P])
     cnuda_conv1x1_backward_data_act = (_I, [_P] * 4 + [_I] * 3 + [_LL, _F, _P])

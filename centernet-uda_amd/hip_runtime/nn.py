@@ -155,6 +155,112 @@ class DepthwiseConv2d(nn.Module):
         return ops.depthwise_conv2d(x, self.weight, self.stride, self.padding)
 
 
+class DepthwiseConv2dSame(nn.Module):
+    """Depthwise nn.Conv2d(C, C, k, stride, groups=C, bias=False) with TensorFlow "SAME" padding; weight [C,1,k,k].
+    image_size (int or (H, W)): the padding is fixed at construction for that nominal map size, as EfficientNet's static
+    form does (top / left get the smaller half); None: derived from every input's own size."""
+
+    def __init__(self, channels, kernel_size, stride=1, image_size=None):
+        super().__init__()
+        self.channels, self.kernel_size, self.stride = channels, int(kernel_size), int(stride)
+        self.in_channels = self.out_channels = channels
+        self.static_padding = None
+        if image_size is not None:
+            ih, iw = _pair(image_size)
+            (pt, pb), (pl, pr) = (ops.same_padding(ih, self.kernel_size, self.stride),
+                                  ops.same_padding(iw, self.kernel_size, self.stride))
+            self.static_padding = (pt, pl, pb, pr)
+        self.weight = nn.Parameter(torch.empty(channels, 1, self.kernel_size, self.kernel_size))
+        with torch.no_grad():
+            self.weight.normal_(0.0, math.sqrt(2.0 / (self.kernel_size * self.kernel_size * channels)))
+
+    def forward(self, x):
+        return ops.depthwise_conv2d_same(x, self.weight, self.stride, self.static_padding)
+
+    def extra_repr(self):
+        return '%d, kernel_size=%d, stride=%d, static_padding=%s' % (self.channels, self.kernel_size, self.stride,
+                                                                     self.static_padding)
+
+
+class Swish(nn.Module):
+    def forward(self, x):
+        return ops.swish(x)
+
+
+class _Pointwise(nn.Module):
+    """Parameters of a 1x1 convolution with bias (weight [out,in,1,1]) that its owner applies itself."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, 1, 1))
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+        with torch.no_grad():
+            self.weight.normal_(0.0, math.sqrt(2.0 / out_channels))
+
+
+class SqueezeExcite(nn.Module):
+    """x * sigmoid(_se_expand(swish(_se_reduce(mean_hw(x))))), the two 1x1 convolutions on a [B,C,1,1] vector: pool, gate and
+    scale kernels (ops.squeeze_excite), no GEMM."""
+
+    def __init__(self, channels, squeezed_channels):
+        super().__init__()
+        self._se_reduce = _Pointwise(channels, squeezed_channels)
+        self._se_expand = _Pointwise(squeezed_channels, channels)
+
+    def forward(self, x):
+        return ops.squeeze_excite(x, self._se_reduce.weight, self._se_reduce.bias, self._se_expand.weight,
+                                  self._se_expand.bias)
+
+
+class MBConvBlock(nn.Module):
+    """EfficientNet's mobile inverted bottleneck with squeeze-and-excite: [1x1 expand, BN, swish]? -> depthwise k x k SAME, BN,
+    swish -> SE -> 1x1 project, BN [-> drop-connect + skip connection when stride == 1 and in == out].  Parameter names
+    are those of the published PyTorch port (_expand_conv, _bn0, _depthwise_conv, _bn1, _se_reduce, _se_expand,
+    _project_conv, _bn2); every BatchNorm has momentum 0.01 and eps 1e-3."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride, expand_ratio, se_ratio=0.25, image_size=None):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.stride, self.expand_ratio = int(kernel_size), int(stride), expand_ratio
+        mid = in_channels * expand_ratio
+        bn = lambda c: BatchNorm2d(c, momentum=0.01, eps=1e-3)
+        if expand_ratio != 1:
+            self._expand_conv = Conv2d(in_channels, mid, 1, bias=False)
+            self._bn0 = bn(mid)
+        self._depthwise_conv = DepthwiseConv2dSame(mid, kernel_size, stride, image_size)
+        self._bn1 = bn(mid)
+        squeezed = max(1, int(in_channels * se_ratio))
+        self._se_reduce = _Pointwise(mid, squeezed)
+        self._se_expand = _Pointwise(squeezed, mid)
+        self._project_conv = Conv2d(mid, out_channels, 1, bias=False)
+        self._bn2 = bn(out_channels)
+        self.has_skip = self.stride == 1 and in_channels == out_channels
+        with torch.no_grad():
+            for conv in (getattr(self, '_expand_conv', None), self._project_conv):
+                if conv is not None:
+                    conv.weight.normal_(0.0, math.sqrt(2.0 / conv.out_channels))
+
+    def forward(self, x, drop_connect_rate=None):
+        skip = None
+        if self.has_skip:
+            from .fanout import fork
+            x, skip = fork(x, 2)          # the input also is the skip connection: two aliases, one gradient slot
+        if self.expand_ratio != 1:
+            x = ops.swish(self._bn0(self._expand_conv(x)))
+        x = ops.swish(self._bn1(self._depthwise_conv(x)))
+        x = ops.squeeze_excite(x, self._se_reduce.weight, self._se_reduce.bias, self._se_expand.weight,
+                               self._se_expand.bias)
+        x = self._project_conv(x)
+        if skip is None:
+            return self._bn2(x)
+        if self.training and drop_connect_rate:
+            keep = 1.0 - drop_connect_rate
+            mask = torch.floor(keep + torch.rand([x.shape[0]], device=x.device)) / keep
+            return ops.drop_connect_add(self._bn2(x), mask, skip)
+        return self._bn2(x, residual=skip)          # BN + the skip connection in one kernel
+
+
 class Slot(nn.Module):
     """Parameter-free placeholder that keeps Sequential indices aligned with the
     reference's module lists (e.g. the ReLU at index 1 of a head, dla.py:476-483)."""

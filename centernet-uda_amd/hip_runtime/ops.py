@@ -633,6 +633,174 @@ def depthwise_conv2d(x, weight, stride=1, padding=0):
     return _DwConv.apply(x, weight, int(stride), int(padding))
 
 
+class _DwConvSame(Function):
+    """Depthwise convolution with TensorFlow "SAME" padding: pads = (top, left, bottom, right) zeros, which may differ
+    per side; weight [C,1,k,k], no bias (cnuda_dwconv2d_same_*)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, pads):
+        require_gpu(x, weight)
+        x, weight = f32c(x), f32c(weight)
+        B, C, H, W = x.shape
+        k = weight.shape[2]
+        if weight.shape[0] != C or weight.shape[1] != 1 or weight.shape[3] != k:
+            raise RuntimeError("depthwise conv2d (same): weight %s does not fit %d channels" % (tuple(weight.shape), C))
+        pt, pl, pb, pr = pads
+        Ho, Wo = (H + pt + pb - k) // stride + 1, (W + pl + pr - k) // stride + 1
+        if Ho < 1 or Wo < 1:
+            raise RuntimeError("depthwise conv2d (same): a %dx%d map with padding %s is smaller than the kernel" % (H, W, pads))
+        y = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device)
+        ctx.geom = (B, C, H, W, k, stride, pt, pl, Ho, Wo)
+        check(lib().cnuda_dwconv2d_same_forward(ptr(x), ptr(weight), ptr(y), *ctx.geom, stream()), 'dwconv2d_same_forward')
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, weight = ctx.saved_tensors
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gw_buf, gw = _param_grad(weight, ctx.needs_input_grad[1])
+        L = lib()
+        B, C, _, _, k = ctx.geom[:5]
+        wp, wn = _ws(L.cnuda_dwconv2d_same_workspace_bytes(B, C, k), x)
+        check(L.cnuda_dwconv2d_same_backward(ptr(x), ptr(weight), ptr(f32c(gy)), ptr(gx), ptr(gw_buf), *ctx.geom,
+                                             wp, wn, stream()), 'dwconv2d_same_backward')
+        return gx, gw, None, None
+
+
+def same_padding(size, kernel_size, stride):
+    """TensorFlow's SAME rule for one axis of `size` pixels -> (before, after): total max((ceil(size/s)-1)*s + k - size, 0),
+    the smaller half in front."""
+    total = max((-(-size // stride) - 1) * stride + kernel_size - size, 0)
+    return total // 2, total - total // 2
+
+
+def depthwise_conv2d_same(x, weight, stride=1, pads=None):
+    """pads (top, left, bottom, right); None: SAME padding derived from x's own size."""
+    if pads is None:
+        k = weight.shape[2]
+        (pt, pb), (pl, pr) = same_padding(x.shape[2], k, int(stride)), same_padding(x.shape[3], k, int(stride))
+        pads = (pt, pl, pb, pr)
+    return _DwConvSame.apply(x, weight, int(stride), tuple(int(p) for p in pads))
+
+
+class _Swish(Function):
+    @staticmethod
+    def forward(ctx, x):
+        require_gpu(x)
+        x = f32c(x)
+        y = torch.empty_like(x)
+        if x.numel():
+            check(lib().cnuda_swish_forward(ptr(x), ptr(y), x.numel(), stream()), 'swish_forward')
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        if x.numel():
+            check(lib().cnuda_swish_backward(ptr(f32c(gy)), ptr(x), ptr(gx), x.numel(), stream()), 'swish_backward')
+        return gx
+
+
+def swish(x):
+    """x * sigmoid(x); the backward recomputes the sigmoid from x (the output is not kept)."""
+    return _Swish.apply(x)
+
+
+class _SqueezeExcite(Function):
+    """y = x * sigmoid(W2 swish(W1 mean_hw(x) + b1) + b2): pool, gate (one workgroup per image) and scale kernels."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2):
+        require_gpu(x, w1, b1, w2, b2)
+        x, w1, b1, w2, b2 = [f32c(t) for t in (x, w1, b1, w2, b2)]
+        B, C = x.shape[0], x.shape[1]
+        HW = x.numel() // (B * C)
+        Cse = w1.shape[0]
+        if w1.numel() != Cse * C or w2.numel() != C * Cse or w2.shape[0] != C or b1.numel() != Cse or b2.numel() != C:
+            raise RuntimeError("squeeze_excite: weights %s / %s, biases %s / %s do not fit %d channels"
+                               % (tuple(w1.shape), tuple(w2.shape), tuple(b1.shape), tuple(b2.shape), C))
+        y = torch.empty_like(x)
+        pool = torch.empty((B, C), dtype=torch.float32, device=x.device)
+        hpre = torch.empty((B, Cse), dtype=torch.float32, device=x.device)
+        gate = torch.empty((B, C), dtype=torch.float32, device=x.device)
+        ctx.dims = (B, C, Cse, HW)
+        check(lib().cnuda_se_forward(ptr(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(y), ptr(pool), ptr(hpre), ptr(gate),
+                                     B, C, Cse, HW, stream()), 'se_forward')
+        ctx.save_for_backward(x, w1, b1, w2, b2, pool, hpre, gate)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, w1, b1, w2, b2, pool, hpre, gate = ctx.saved_tensors
+        B, C, Cse, HW = ctx.dims
+        gx = torch.empty_like(x)
+        bufs, grads = zip(*[_param_grad(p, ctx.needs_input_grad[i + 1]) for i, p in enumerate((w1, b1, w2, b2))])
+        L = lib()
+        wp, wn = _ws(L.cnuda_se_workspace_bytes(B, C, Cse), x)
+        check(L.cnuda_se_backward(ptr(x), ptr(f32c(gy)), ptr(w1), ptr(w2), ptr(pool), ptr(hpre), ptr(gate), ptr(gx),
+                                  *[ptr(t) for t in bufs], B, C, Cse, HW, wp, wn, stream()), 'se_backward')
+        return (gx if ctx.needs_input_grad[0] else None,) + tuple(grads)
+
+
+def squeeze_excite(x, w_reduce, b_reduce, w_expand, b_expand):
+    """w_reduce [Cse,C,1,1] (or [Cse,C]), w_expand [C,Cse,1,1]: the two 1x1 convolutions of an MBConv block's SE branch."""
+    return _SqueezeExcite.apply(x, w_reduce, b_reduce, w_expand, b_expand)
+
+
+class _DropConnectAdd(Function):
+    @staticmethod
+    def forward(ctx, x, mask, residual):
+        require_gpu(x, mask, residual)
+        if x.shape != residual.shape or mask.numel() != x.shape[0]:
+            raise RuntimeError("drop_connect_add: x %s, residual %s, mask %s" % (tuple(x.shape), tuple(residual.shape),
+                                                                                tuple(mask.shape)))
+        x, mask, residual = f32c(x), f32c(mask), f32c(residual)
+        y = torch.empty_like(x)
+        ctx.dims = (x.shape[0], x.numel() // x.shape[0])
+        check(lib().cnuda_drop_connect_add(ptr(x), ptr(mask), ptr(residual), ptr(y), *ctx.dims, stream()), 'drop_connect_add')
+        ctx.save_for_backward(mask)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        mask, = ctx.saved_tensors
+        gy = f32c(gy)
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(gy)
+            check(lib().cnuda_drop_connect_add(ptr(gy), ptr(mask), None, ptr(gx), *ctx.dims, stream()), 'drop_connect_add')
+        return gx, None, gy if ctx.needs_input_grad[2] else None
+
+
+def drop_connect_add(x, mask, residual):
+    """x * mask[b] + residual: the stochastic-depth branch of an MBConv block joined with its skip connection; mask [B] is
+    the caller's (0 or 1 / keep probability per image)."""
+    return _DropConnectAdd.apply(x, mask, residual)
+
+
+def pad_right_bottom(x, pad_bottom, pad_right):
+    """[B,C,H,W] -> [B,C,H+pad_bottom,W+pad_right], zeros added below / to the right (the SAME padding of a stride-2 stem in
+    front of a padding-0 convolution).  No backward: for network inputs."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("pad_right_bottom has no backward in this build (it pads the network's input)")
+    require_gpu(x)
+    if pad_bottom == 0 and pad_right == 0:
+        return x
+    x = f32c(x)
+    B, C, H, W = x.shape
+    y = torch.empty((B, C, H + pad_bottom, W + pad_right), dtype=torch.float32, device=x.device)
+    check(lib().cnuda_pad_right_bottom(ptr(x), ptr(y), B * C, H, W, int(pad_bottom), int(pad_right), stream()),
+          'pad_right_bottom')
+    return y
+
+
 class _Add(Function):
     @staticmethod
     def forward(ctx, a, b):

@@ -577,6 +577,46 @@ int cnuda_gather_feat(const float* feat, const int64_t* ind, float* out, int B, 
                       cnuda_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * EfficientNet MBConv block (backends/efficientnet.py; csrc/mbconv.hip).  fp32, caller's stream, no float atomics:
+ * every reduction has a fixed order and two runs give the same bits.
+ *
+ * Depthwise convolution with TensorFlow "SAME" padding, weight [C,1,k,k] (k = 3 or 5, stride 1 or 2), no bias:
+ *   y[b,c,oy,ox] = sum_{r,t} w[c,r,t] * x[b,c, oy*s - pad_top + r, ox*s - pad_left + t], zero outside the map.
+ * The bottom / right padding is implied by the output size, (Ho-1)*s + k - pad_top - H (and likewise for W); it must
+ * lie in [0, k) like pad_top / pad_left.  backward writes grad_x and/or grad_w (either may be NULL); grad_w needs the
+ * workspace (per-image partial sums, added in image order).
+ * ---------------------------------------------------------------------- */
+size_t cnuda_dwconv2d_same_workspace_bytes(int B, int C, int k);
+int cnuda_dwconv2d_same_forward(const float* x, const float* w, float* y, int B, int C, int H, int W, int k, int s,
+                                int pad_top, int pad_left, int Ho, int Wo, cnuda_stream_t stream);
+int cnuda_dwconv2d_same_backward(const float* x, const float* w, const float* grad_y, float* grad_x, float* grad_w,
+                                 int B, int C, int H, int W, int k, int s, int pad_top, int pad_left, int Ho, int Wo,
+                                 void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+/* y = x * sigmoid(x);  grad_x = grad_y * (s + x*s*(1-s)), s = sigmoid(x), recomputed from x */
+int cnuda_swish_forward(const float* x, float* y, long long n, cnuda_stream_t stream);
+int cnuda_swish_backward(const float* grad_y, const float* x, float* grad_x, long long n, cnuda_stream_t stream);
+/* Squeeze-and-excite: pool[b,c] = mean_hw x;  hpre = W1 pool + b1 (W1 [Cse,C]);  gate = sigmoid(W2 swish(hpre) + b2)
+ * (W2 [C,Cse]);  y = x * gate[b,c].  One workgroup per image computes the gate with pool and the hidden vector in LDS
+ * ((C + Cse) * 4 bytes <= 60 KiB).  pool [B,C], hpre [B,Cse], gate [B,C] are outputs the backward takes back:
+ *   dg = sum_hw grad_y * x;  grad_x = grad_y * gate + dpool / HW;  grad_w1 / grad_b1 / grad_w2 / grad_b2 summed over the
+ *   images in increasing order (each nullable).  Workspace: cnuda_se_workspace_bytes. */
+size_t cnuda_se_workspace_bytes(int B, int C, int Cse);
+int cnuda_se_forward(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y,
+                     float* pool, float* hpre, float* gate, int B, int C, int Cse, long long HW, cnuda_stream_t stream);
+int cnuda_se_backward(const float* x, const float* grad_y, const float* w1, const float* w2, const float* pool,
+                      const float* hpre, const float* gate, float* grad_x, float* grad_w1, float* grad_b1,
+                      float* grad_w2, float* grad_b2, int B, int C, int Cse, long long HW,
+                      void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+/* Drop-connect + residual: y[b,i] = x[b,i] * mask[b] + residual[b,i], mask [B] from the caller.  residual NULL:
+ * y = x * mask[b], which also is the backward (grad_x = grad_y * mask[b]; grad_residual = grad_y). */
+int cnuda_drop_connect_add(const float* x, const float* mask, const float* residual, float* y, int B,
+                           long long per_image, cnuda_stream_t stream);
+/* y [planes, H+pad_bottom, W+pad_right] = x [planes,H,W] in the top-left corner, zeros elsewhere: the SAME padding of
+ * the dense stride-2 stem, so that the implicit-GEMM loaders keep their symmetric padding.  No backward. */
+int cnuda_pad_right_bottom(const float* x, float* y, long long planes, int H, int W, int pad_bottom, int pad_right,
+                           cnuda_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Fourier domain adaptation (utils/image.py:137-230, FDA_source_to_target): out = irfft2 of the source's half
  * spectrum (columns 0 .. W/2) whose amplitude is replaced by the target's where use_target_amp[ky][kx] != 0
  * (a bin with |S| = 0 becomes (|T|, 0)); the DC and Nyquist columns contribute their real part only.
