@@ -55,6 +55,7 @@ _P = c_void_p
 
 _LL = ctypes.c_longlong
 _F = c_float
+_D = ctypes.c_double
 _WS = [_P, c_size_t, _P]          # workspace, workspace_bytes, stream
 
 
@@ -153,6 +154,9 @@ class _Sig:
     cnuda_fda_workspace_bytes = (c_size_t, [_I] * 4)
     cnuda_fda_source_to_target = (_I, [_P] * 4 + [_I] * 4 + _WS)
     cnuda_adam_step = (_I, [_P] * 4 + [_LL] + [_F] * 5 + [_I, _P])
+    cnuda_sgd_step = (_I, [_P] * 3 + [_LL] + [_D] * 4 + [_I] * 3 + [_P])
+    cnuda_adamw_step = (_I, [_P] * 5 + [_LL] + [_D] * 5 + [_I] * 3 + [_P])
+    cnuda_rmsprop_step = (_I, [_P] * 5 + [_LL] + [_D] * 5 + [_I, _P])
     cnuda_set_matrix_mode = (_I, [_I])
     cnuda_get_matrix_mode = (_I, [])
     cnuda_pack_cache_attach = (_I, [_P, c_size_t])

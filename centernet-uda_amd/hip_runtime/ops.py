@@ -1301,6 +1301,40 @@ def adam_step_(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_d
           'adam_step')
 
 
+def _flat_operands(what, param, *others):
+    """param and every tensor of `others` that is not None: flat contiguous fp32 on the GPU, of one length."""
+    require_gpu(param, *others)
+    for t in (param,) + others:
+        if t is not None and (not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != param.numel()):
+            raise RuntimeError("%s: flat contiguous float32 tensors of equal length required" % what)
+
+
+def sgd_step_(param, grad, momentum_buffer, lr, momentum, dampening, weight_decay, nesterov, maximize, first):
+    """torch.optim.SGD over one flat range (csrc/optim.hip).  momentum_buffer None <=> momentum == 0; `first`: the
+    range's first update, which sets the buffer to the gradient."""
+    _flat_operands('sgd_step_', param, grad, momentum_buffer)
+    check(lib().cnuda_sgd_step(ptr(param), ptr(grad), ptr(momentum_buffer), param.numel(), float(lr), float(momentum),
+                               float(dampening), float(weight_decay), int(bool(nesterov)), int(bool(maximize)),
+                               int(bool(first)), stream()), 'sgd_step')
+
+
+def adamw_step_(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, beta1, beta2, eps, weight_decay, decoupled,
+                maximize, step):
+    """The Adam family over one flat range: decoupled weight decay (AdamW) or L2, max_exp_avg_sq None <=> no amsgrad."""
+    _flat_operands('adamw_step_', param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq)
+    check(lib().cnuda_adamw_step(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), ptr(max_exp_avg_sq),
+                                 param.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                 int(bool(decoupled)), int(bool(maximize)), int(step), stream()), 'adamw_step')
+
+
+def rmsprop_step_(param, grad, square_avg, grad_avg, momentum_buffer, lr, alpha, eps, weight_decay, momentum, maximize):
+    """torch.optim.RMSprop over one flat range: grad_avg None <=> not centered, momentum_buffer None <=> momentum == 0."""
+    _flat_operands('rmsprop_step_', param, grad, square_avg, grad_avg, momentum_buffer)
+    check(lib().cnuda_rmsprop_step(ptr(param), ptr(grad), ptr(square_avg), ptr(grad_avg), ptr(momentum_buffer),
+                                   param.numel(), float(lr), float(alpha), float(eps), float(weight_decay),
+                                   float(momentum), int(bool(maximize)), stream()), 'rmsprop_step')
+
+
 # ---------------------------------------------------------------------------
 # Fourier domain adaptation (csrc/fda.hip)
 # ---------------------------------------------------------------------------

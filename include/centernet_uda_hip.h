@@ -636,6 +636,26 @@ int cnuda_fda_source_to_target(const float* src, const float* trg, const uint8_t
 int cnuda_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n,
                     float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                     cnuda_stream_t stream);
+/* The other update rules of torch.optim over a flat range of the arena (csrc/optim.hip): torch's single-tensor
+ * arithmetic in torch's order of operations, every operand n fp32.  A range begins and ends on an arena slot boundary:
+ * every pointer must be 16-byte aligned and n a multiple of 4 (checked).  Optional operands are NULL exactly when the
+ * rule does not use them.  Hyper-parameters are doubles: the derived constants (1 - dampening, 1 - lr*wd, lr / bias
+ * correction, ...) are formed in double, as torch forms them in Python floats, and rounded to fp32 once.  flags are 0 / 1.
+ * Elements whose gradient and state are all zero (the arena's alignment gaps) stay finite for every eps, eps = 0
+ * included: a zero numerator gives a zero quotient.
+ *   sgd:     momentum_buffer NULL <=> momentum == 0;  first = 1: this is the range's first update (buf = g);
+ *            nesterov needs momentum > 0 and dampening == 0.
+ *   adamw:   Adam family beyond plain Adam.  decoupled = 1: p *= 1 - lr*wd (AdamW), 0: g += wd*p (Adam);
+ *            max_exp_avg_sq non-NULL: amsgrad;  step: 1-based count of updates of this range (bias correction).
+ *   rmsprop: grad_avg non-NULL: centered;  momentum_buffer NULL <=> momentum == 0. */
+int cnuda_sgd_step(float* param, const float* grad, float* momentum_buffer, long long n, double lr, double momentum,
+                   double dampening, double weight_decay, int nesterov, int maximize, int first, cnuda_stream_t stream);
+int cnuda_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                     long long n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                     int decoupled, int maximize, int step, cnuda_stream_t stream);
+int cnuda_rmsprop_step(float* param, const float* grad, float* square_avg, float* grad_avg, float* momentum_buffer,
+                       long long n, double lr, double alpha, double eps, double weight_decay, double momentum,
+                       int maximize, cnuda_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Target encoding for a batch (the step right before the hot path):
