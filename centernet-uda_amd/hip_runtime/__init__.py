@@ -80,6 +80,11 @@ class _Sig:
     cnuda_dcn_v2_psroi_pooling_workspace_bytes = (c_size_t, [_I] * 4)
     cnuda_dcn_v2_psroi_pooling_forward = (_I, [_P] * 5 + [_I] * 6 + [_F] + [_I] * 5 + [_F, _I, _P])
     cnuda_dcn_v2_psroi_pooling_backward = (_I, [_P] * 6 + [_I, _P] + [_I] * 6 + [_F] + [_I] * 5 + [_F, _I] + _WS)
+    cnuda_eval_workspace_bytes = (c_size_t, [_I, _I])
+    cnuda_eval_box_spans = (_I, [_P, _I, _I, _I, _P, _P] + _WS)
+    cnuda_eval_iou_rotated = (_I, [_P, _I, _I, _I, _LL, _P, _P, _I, _P] + _WS)
+    cnuda_eval_iou_axis = (_I, [_P, _P, _P, _I, _I, _I, _LL, _P, _P])
+    cnuda_eval_match = (_I, [_P, _P, _I, _P, _P, _I, _I, _LL, _P, _I, _P, _P, _P, _P])
     cnuda_conv2d_workspace_bytes = (c_size_t, [_I] * 11)
     cnuda_conv2d_forward = (_I, [_P] * 4 + [_I] * 11 + [_F] + _WS)
     cnuda_conv2d_forward_res = (_I, [_P] * 5 + [_I] * 11 + [_F] + _WS)

@@ -311,6 +311,41 @@ int cnuda_dcn_v2_psroi_pooling_backward(const float* grad_output, const float* i
                                         void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * COCO evaluation (evaluation/coco.py): what pycocotools' computeIoU and evaluateImg do for one batch of images, with
+ * the per-box masks of the rotated mode rasterised here instead of cv2.fillPoly + RLE.
+ *   group: one (image, category), five ints {first detection, detections, first ground truth, ground truths, first
+ *   pair}; detections of a group are consecutive and in descending score order, pair (d, g) is element
+ *   first pair + d * ground truths + g of `iou`.  A group that does not fit num_det / num_gt / num_pairs is skipped.
+ * cnuda_eval_box_spans: verts [num_boxes, 4, 2] integer (x, y) corners.  The mask of a box is the project's convex-fill
+ *   rule (utils/image.py::_fill_convex_poly: 8-connected outline, then scanlines) clipped to H x W, held as one
+ *   (left, right) span per image row in the workspace (cnuda_eval_workspace_bytes).  rows [num_boxes, 2]: first and
+ *   last non-empty row (0, -1 for an empty mask); area [num_boxes]: pixel count.  H, W <= 8192.
+ * cnuda_eval_iou_rotated: boxes [0, num_det) of that workspace are the detections, [num_det, num_det + num_gt) the
+ *   ground truths; iou = |D and G| / (|D| + |G| - |D and G|) on pixel counts, 0 for an empty union.
+ * cnuda_eval_iou_axis: boxes float32 (x, y, w, h); pycocotools' bbIou in double, 0 where width or height of the
+ *   intersection is <= 0.  No fused multiply-add.
+ * cnuda_eval_match: thresholds [num_thresholds <= 16] and area_ranges [4, 2] (lo, hi) are HOST arrays.  For every
+ *   group and range: a ground truth is ignored when its area is < lo or > hi; detections in order take, among the
+ *   ground truths not yet matched at that threshold with iou >= min(t, 1 - 1e-10), the non-ignored one of largest IoU
+ *   (ties: the later one), else the ignored one by the same rule.  det_bits [num_det, 4]: bits 0..15 matched per
+ *   threshold, bits 16..31 ignored per threshold (matched to an ignored ground truth, or unmatched with an area outside
+ *   the range).  gt_ignore [num_gt, 4] bytes.  num_gt <= 16384 per call (one 32-bit word of LDS per ground truth).
+ * Integers and doubles only, no floating-point atomics: bit-stable.  Nothing synchronises the stream.
+ * ---------------------------------------------------------------------- */
+size_t cnuda_eval_workspace_bytes(int num_boxes, int H);
+int cnuda_eval_box_spans(const int* verts, int num_boxes, int H, int W, int* rows, double* area,
+                         void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+int cnuda_eval_iou_rotated(const int* groups, int num_groups, int num_det, int num_gt, long long num_pairs,
+                           const int* rows, const double* area, int H, double* iou,
+                           void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+int cnuda_eval_iou_axis(const float* det_boxes, const float* gt_boxes, const int* groups, int num_groups,
+                        int num_det, int num_gt, long long num_pairs, double* iou, cnuda_stream_t stream);
+int cnuda_eval_match(const double* iou, const int* groups, int num_groups, const double* det_area,
+                     const double* gt_area, int num_det, int num_gt, long long num_pairs,
+                     const double* thresholds, int num_thresholds, const double* area_ranges,
+                     unsigned* det_bits, unsigned char* gt_ignore, cnuda_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Dense convolution (groups 1, dilation 1) -- replaces torch.nn.Conv2d -> cuDNN
  * on the hot path: backends/dla.py:37-44,153-155,234-235,281-283,478-483 (DLA
  * trunk, roots, heads), libs/DCNv2/dcn_v2.py:104-110 (offset/mask conv),
