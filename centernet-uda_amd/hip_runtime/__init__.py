@@ -156,6 +156,8 @@ class _Sig:
     cnuda_sigmoid_clamp_ = (_I, [_P, _P, _LL, _P])
     cnuda_gather_feat = (_I, [_P] * 3 + [_I, _I, _I, _LL, _P])
     cnuda_encode_targets = (_I, [_P] * 10 + [_I] * 5 + [_P])
+    cnuda_encode_targets_modes = (_I, [_P] * 17 + [_I] * 6 + [_P])
+    cnuda_prepare_input = (_I, [_P, _P, _I, _I, _I] + [_F] * 6 + [_P])
     cnuda_fda_workspace_bytes = (c_size_t, [_I] * 4)
     cnuda_fda_source_to_target = (_I, [_P] * 4 + [_I] * 4 + _WS)
     cnuda_adam_step = (_I, [_P] * 4 + [_LL] + [_F] * 5 + [_I, _P])

@@ -2,7 +2,9 @@
 degrees] as integer pixel coordinates -- the polygon the COCO evaluator rasterises in rotated mode
 (evaluation/coco.py).
 
-`get_annotation_with_angle` of the reference's file is dataset-side code and not part of this build."""
+`get_annotation_with_angle` (utils/box.py:4-38) is the dataset-side normalisation of a rotated annotation: w the
+short side, h the long one, the angle in [-90, 90).  `datasets.encode_targets(corners=...)` applies the same rules on
+the device; this is the host form for annotations read from a file."""
 import numpy as np
 
 
@@ -32,3 +34,28 @@ def rotate_bbox(x, y, w, h, angle):
     """-> list of four integer [x, y] vertices of the rotated box"""
     dtype = np.result_type(*[np.asarray(v).dtype for v in (x, y, w, h, angle)])
     return list(rotate_bboxes(np.array([[x, y, w, h, angle]], dtype=dtype))[0])
+
+
+def get_annotation_with_angle(ann):
+    """ann['rbbox'] = (cx, cy, w, h, angle in degrees) -> float32 [5] with w < h and -90 <= angle < 90, by the
+    reference's arithmetic on float32 values: w > h swaps the sides and turns the angle by 90 degrees towards zero
+    (a positive angle loses 90, any other gains 90); w == h makes h += 1; an angle of exactly 90 becomes -90; the
+    angle is then clipped to [-90, 90 - eps] with the float64 eps the reference's `np.float` meant.
+    Only annotations that carry `rbbox` are accepted: the reference's branch for plain `bbox` annotations calls
+    `.append` on an ndarray and cannot run, so there is nothing to restate -- ValueError."""
+    if 'rbbox' not in ann:
+        raise ValueError("get_annotation_with_angle: the annotation has no 'rbbox' (cx, cy, w, h, angle)")
+    box = np.array(ann['rbbox'], dtype=np.float32)
+    if box.shape != (5,):
+        raise ValueError("get_annotation_with_angle: 'rbbox' must be (cx, cy, w, h, angle), got shape %s" % (box.shape,))
+    if box[2] > box[3]:
+        box[2:4] = box[3], box[2]
+        box[4] += np.float32(-90 if box[4] > 0 else 90)
+    if box[2] == box[3]:
+        box[3] += 1
+    if box[4] == 90:
+        box[4] = -90
+    box[4] = np.clip(box[4], -90, 90 - np.finfo(np.float64).eps)
+    if not (box[2] < box[3] and -90 <= box[4] < 90):
+        raise ValueError("get_annotation_with_angle: %s does not normalise to w < h, -90 <= angle < 90" % (box,))
+    return box

@@ -705,6 +705,33 @@ int cnuda_encode_targets(const double* boxes, const int* classes, const int* cou
                          float* hm, unsigned char* reg_mask, long long* ind, float* wh, float* reg,
                          float* gt_dets, float* gt_areas,
                          int B, int C, int H, int W, int M, cnuda_stream_t stream);
+/* The other modes of the dataset's loop (datasets/coco.py:176-184,217-233 keypoints and "area"; 303-376 rotated
+ * boxes), one workgroup per (image, slot) like the call above, whose outputs this one reproduces when it is given
+ * boxes alone.  Exactly one of boxes / corners is non-NULL.
+ *   corners [B,M,4,2] double: the four corner points in output-map pixels.  Each is clipped to [0,W-1] x [0,H-1] and
+ *     rounded to float32; the object becomes the least-area enclosing rectangle with a side along an edge of the
+ *     points' convex hull (what the reference asks of cv2.minAreaRect), in double from the float32 points, then
+ *     utils/box.py's normalisation on float32 values: w the short side, h the long one (w == h: h += 1), angle the
+ *     direction of the short side in degrees (y down, the convention of rotate_bbox) folded into [-90, 90).  Fewer
+ *     than three hull vertices or a zero extent: the slot stays zero (the reference's `continue`).  Then wh is
+ *     [B,M,3] (w, h, angle) and gt_dets [B,M,7] (cx, cy, w, h, angle, 1, class); with boxes they are [B,M,2] / [B,M,6].
+ *   keypoints [B,M,J,2] double, visibility [B,M,J] int32 (COCO's v), kps [B,M,2J] f32 (offsets from the integer
+ *     centre), gt_kps [B,M,J,2] f32, kp_reg_mask [B,M,2J] u8 (v == 2 and 0 <= x < W and 0 <= y < W: the reference
+ *     tests y against the width): all five non-NULL when J > 0, all NULL when J == 0.  Written for valid slots only.
+ *   areas [B,M] f32 or NULL: the annotation's "area"; NaN (or NULL) = absent, gt_areas falls back to w*h.
+ *   counts is clamped to M.  Every output is fully overwritten. */
+int cnuda_encode_targets_modes(const double* boxes, const double* corners, const int* classes, const int* counts,
+                               const double* keypoints, const int* visibility, const float* areas,
+                               float* hm, unsigned char* reg_mask, long long* ind, float* wh, float* reg,
+                               float* gt_dets, float* gt_areas, float* kps, float* gt_kps,
+                               unsigned char* kp_reg_mask,
+                               int B, int C, int H, int W, int M, int J, cnuda_stream_t stream);
+/* Input normalisation (datasets/coco.py:160-162, 105-109): images [B,H,W,3] uint8 (4-byte aligned) ->
+ * out [B,3,H,W] f32 (16-byte aligned), out = (float(u8) / 255 - mean_c) / std_c, each step one IEEE float32
+ * operation: bit-identical to the numpy expression. */
+int cnuda_prepare_input(const unsigned char* images, float* out, int B, int H, int W,
+                        float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                        cnuda_stream_t stream);
 
 #ifdef __cplusplus
 }
