@@ -8,8 +8,8 @@ image into a network input (datasets/coco.py:160-162 and, for `target_domain_inp
 
 for a whole batch in one kernel (`cnuda_prepare_input`), so that the image crosses to the device as bytes, a quarter
 of the fp32 tensor.  `images` is [B, H, W, 3] uint8 on the GPU; the result is [B, 3, H, W] float32 and bit-identical
-to the numpy expression: every step is one float32 operation in the same order, with IEEE division.  Resizing,
-decoding and augmentation stay outside this build.
+to the numpy expression: every step is one float32 operation in the same order, with IEEE division.  Resizing and
+augmentation come before it (datasets/augment.py); decoding stays on the host.
 """
 import numpy as np
 import torch

@@ -733,6 +733,31 @@ int cnuda_prepare_input(const unsigned char* images, float* out, int B, int H, i
                         float mean0, float mean1, float mean2, float std0, float std1, float std2,
                         cnuda_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * Augmentation and resizing (the reference's imgaug chain, datasets/coco.py:140-158, restated geometrically: DESIGN.md,
+ * "Augmentation on the device").  The draws and the matrices come from the host; these calls apply them.
+ * Continuous image coordinates: pixel (row i, col j) covers [j, j+1) x [i, i+1).
+ * ---------------------------------------------------------------------- */
+/* Pointwise colour step: src, dst [B,H,W,3] uint8 (different buffers, 4-byte aligned), color [B,3] f32 = (grayscale
+ * alpha, hue rotation in degrees, brightness add on V of HSV).  An image whose three values are 0 is copied. */
+int cnuda_augment_color(const unsigned char* src, unsigned char* dst, const float* color, int B, int H, int W,
+                        cnuda_stream_t stream);
+/* One resampling per image.  src [B,Hmax,Wmax,3] uint8, sizes [B,2] int32 the valid (h, w) of each image (clamped to
+ * the buffer), inverse [B,6] f32 the map from output to source coordinates (u = (a0 x + a1 y) + a2, v = (a3 x + a4 y)
+ * + a5 at x = j + 0.5, y = i + 0.5), taps [B,10,3] f32 (offset x, offset y, weight) with ntaps [B] int32 (clamped to
+ * 10) the motion-blur line in source space, noise [B] f32 the standard deviation of the additive gaussian noise (0 =
+ * none), ids [B] int64 or NULL (= the position in the batch) the images' noise counters, seed the Philox4x32-10 key.
+ * dst [B,Hin,Win,3] uint8, 4-byte aligned.  A pixel whose source point lies outside [0, w] x [0, h] is 0; otherwise
+ * clamp(rint(sum_m weight_m * bilinear(u + ox_m - 0.5, v + oy_m - 0.5) + noise), 0, 255) with replicated edges. */
+int cnuda_augment_warp(const unsigned char* src, unsigned char* dst, const int* sizes, const float* inverse,
+                       const float* taps, const int* ntaps, const float* noise, const long long* ids,
+                       unsigned long long seed, int B, int Hmax, int Wmax, int Hin, int Win, cnuda_stream_t stream);
+/* Annotations through the forward matrices, in double: forward [B,6]; points [B,N,2] -> points_out (may alias);
+ * boxes [B,M,4] (x1, y1, x2, y2) -> boxes_out, the bounding box of the four mapped corners.  N or M may be 0 (then
+ * the two pointers may be NULL). */
+int cnuda_augment_points(const double* forward, const double* points, double* points_out, int N,
+                         const double* boxes, double* boxes_out, int M, int B, cnuda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
