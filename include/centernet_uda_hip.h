@@ -758,6 +758,44 @@ int cnuda_augment_warp(const unsigned char* src, unsigned char* dst, const int* 
 int cnuda_augment_points(const double* forward, const double* points, double* points_out, int N,
                          const double* boxes, double* boxes_out, int M, int B, cnuda_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * Detection previews (utils/visualize.py:23-49 behind utils/tensorboard.py:21-44 of the reference, restated as pixel
+ * rules: DESIGN.md, "Detection previews on the device").  One launch paints n images of the batch twice, side by side:
+ *   input [B,3,H,W] f32 the normalised batch, index [n] int32 which images to render (an index outside [0, B) renders
+ *   over black), out [n,3,H,2W] uint8 with the prediction panel in columns [0, W) and the ground-truth panel in
+ *   [W, 2W).  H, W <= 8192, n <= 65535.
+ * Base pixel of both panels: v = (x * std_c + mean_c) * 255, each step one float32 operation, clamped to [0, 255] and
+ * truncated toward zero.
+ * prims [N, CNUDA_RENDER_RECORD] int32 (16-byte aligned), first [n+1] int32: rendered image i takes the records
+ * [first[i], first[i+1]) (clamped to [0, N]), applied IN LIST ORDER.  A record is 16 words:
+ *   0 kind (CNUDA_RENDER_RING / _FILL / _QUAD / _GLYPH; anything else is skipped), 1 panel (0 prediction, 1 ground truth;
+ *   anything else is skipped), 2 colour r | g << 8 | b << 16, 3 alpha (the bits of a float32 in [0, 1]),
+ *   4 thickness t (RING, QUAD; clamped to [0, 1024]) or glyph index g (GLYPH; outside [0, G) is skipped),
+ *   5..12 geometry in panel-local pixels, x = column, y = row, each clamped to [-32768, 32767]:
+ *           RING, FILL x1, y1, x2, y2;  QUAD x0, y0, x1, y1, x2, y2, x3, y3;  GLYPH x0, y0 (the cell's origin),
+ *   13..15 reserved (0).
+ * A pixel (x, y) of the record's own panel is covered iff
+ *   RING   x1-t+1 <= x <= x2+t-1 and y1-t+1 <= y <= y2+t-1 and not (x1 < x < x2 and y1 < y < y2);
+ *   FILL   x1 <= x <= x2 and y1 <= y <= y2;
+ *   QUAD   4 d^2 <= t^2 for the distance d to one of the four segments of the closed outline, in exact integers: with
+ *          e = Q - P, w = X - P, L = e.e, s = w.e:  s <= 0: 4 |w|^2 <= t^2;  s >= L: 4 |X - Q|^2 <= t^2;  else
+ *          4 (w x e)^2 <= t^2 L (a zero-length edge is its end point);
+ *   GLYPH  0 <= x - x0 < gw and 0 <= y - y0 < gh; its alpha is float(atlas[g, y - y0, x - x0]) / 255.0f, the record's
+ *          alpha is ignored.  atlas [G, gh, gw] uint8 coverage (G may be 0 and atlas NULL; gh, gw <= 256).
+ * and then, per channel, v = rint(v + alpha * (c - v)) in float32: one subtract, one multiply, one add, round half to
+ * even; the pixel is a byte again after every record.  Nothing crosses the seam between the panels.
+ * A gather without atomics: bit-stable.  CNUDA_RENDER_CHUNK records are tested and compacted per pass of a workgroup. */
+#define CNUDA_RENDER_RECORD 16
+#define CNUDA_RENDER_CHUNK 256
+#define CNUDA_RENDER_RING 0
+#define CNUDA_RENDER_FILL 1
+#define CNUDA_RENDER_QUAD 2
+#define CNUDA_RENDER_GLYPH 3
+int cnuda_render_detections(const float* input, const int* index, const int* prims, const int* first,
+                            const unsigned char* atlas, unsigned char* out, int B, int n, int H, int W, int N,
+                            int G, int gh, int gw, float mean0, float mean1, float mean2,
+                            float std0, float std1, float std2, cnuda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
