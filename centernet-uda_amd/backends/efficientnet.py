@@ -28,7 +28,8 @@ blocks SKIP_MAPPINGS[variant] added after the stage whose ReLU has index <id> in
 x4 + stride-2 convolution instead of the transposed convolution, :176-185; no config sets it) is declined.
 
 All layers run on this repo's gfx950 kernels: 1x1 / 3x3 / transposed convolutions on the implicit-GEMM MFMA kernels,
-the depthwise SAME convolution, swish, squeeze-and-excite, drop-connect and the stem's zero-pad copy on csrc/mbconv.hip.
+the depthwise SAME convolution on the depthwise kernels of csrc/spatial.hip, swish, squeeze-and-excite, drop-connect
+and the stem's zero-pad copy on csrc/mbconv.hip.
 """
 import math
 import os

@@ -25,7 +25,8 @@ where those entries are the first two ConvTranspose layers; with both flags the 
 mismatch and so does this build), and per-head 3x3(256->64) + ReLU + 1x1 (:74-90, torch default init).
 
 All layers run on this repo's gfx950 kernels: 1x1 / 3x3 convolutions on the implicit-GEMM MFMA kernels, the
-depthwise 3x3 on `cnuda_dwconv2d_*`, BN (+ residual) + ReLU6 in one kernel, DCN on the deformable kernels.
+depthwise 3x3 on `cnuda_dwconv2d_*` (the depthwise kernels of csrc/spatial.hip, which EfficientNet's SAME-padded
+layers share), BN (+ residual) + ReLU6 in one kernel, DCN on the deformable kernels.
 """
 import math
 import os

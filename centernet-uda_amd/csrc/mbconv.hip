@@ -1,8 +1,8 @@
-// HBM-bound kernels of the EfficientNet MBConv block (backends/efficientnet.py; NCHW fp32, all on the caller's stream):
-//   depthwise convolution with TensorFlow "SAME" padding (separate top / left padding, bottom / right implied by the
-//   output size), swish, squeeze-and-excite (pool, gate, scale), drop-connect + residual, and the right / bottom
-//   zero-pad copy in front of the dense stem.  No float atomics anywhere: every reduction has a fixed order, so two
-//   runs give the same bits.
+// HBM-bound kernels specific to the EfficientNet MBConv block (backends/efficientnet.py; NCHW fp32, all on the caller's
+//   stream): swish, squeeze-and-excite (pool, gate, scale), drop-connect + residual, and the right / bottom zero-pad
+//   copy in front of the dense stem.  (The block's depthwise convolution with TensorFlow "SAME" padding is
+//   cnuda_dwconv2d_same_* in spatial.hip.)  No float atomics anywhere: every reduction has a fixed order, so two runs
+//   give the same bits.
 #include "common.h"
 
 namespace cnuda {
@@ -15,168 +15,6 @@ __device__ __forceinline__ float swishf(float v) { return v * sigmoidf(v); }
 __device__ __forceinline__ float swish_gradf(float v) {
     const float s = sigmoidf(v);
     return s + v * s * (1.0f - s);
-}
-
-// ---------------- depthwise convolution, asymmetric padding ----------------
-// y[b,c,oy,ox] = sum_{r,t} w[c,r,t] * x[b,c, oy*s - pt + r, ox*s - pl + t]; taps outside the map read zero, whichever
-// side they fall off (that is the implied bottom / right padding).  One thread per output, k*k weights in registers.
-template <int K>
-__global__ __launch_bounds__(kT) void dwsame_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                        float* __restrict__ y, int C, int H, int W, int Ho, int Wo,
-                                                        int s, int pt, int pl) {
-    const int c = blockIdx.x % C;
-    const size_t plane = blockIdx.x;
-    float wk[K * K];
-#pragma unroll
-    for (int i = 0; i < K * K; ++i) wk[i] = w[(size_t)c * K * K + i];
-    const float* xp = x + plane * H * W;
-    float* yp = y + plane * Ho * Wo;
-    for (int o = blockIdx.y * kT + threadIdx.x; o < Ho * Wo; o += gridDim.y * kT) {
-        const int oy = o / Wo, ox = o - oy * Wo;
-        float acc = 0.0f;
-#pragma unroll
-        for (int r = 0; r < K; ++r) {
-            const int iy = oy * s - pt + r;
-            if (iy < 0 || iy >= H) continue;
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                const int ix = ox * s - pl + t;
-                if (ix >= 0 && ix < W) acc += wk[r * K + t] * xp[iy * W + ix];
-            }
-        }
-        yp[o] = acc;
-    }
-}
-// W % 4 == 0 and Wo % 4 == 0, left padding PL in 0..2 (what SAME padding gives k = 3 and 5; a compile-time constant, so
-// the row window stays in registers): one thread per four outputs of a row.
-// The input window of the quad lies inside the NV aligned float4 segments that start at column S*ox - 4 (a segment is
-// wholly inside or wholly outside the row, because W is a multiple of 4): 16-byte loads, one 16-byte store; taps are
-// accumulated in the scalar kernel's order (r, then t), so both paths round alike.
-template <int K, int S, int PL>
-__global__ __launch_bounds__(kT) void dwsame_fwd_vec_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                            float* __restrict__ y, int C, int H, int W, int Ho, int Wo,
-                                                            int pt) {
-    constexpr int NV = S == 1 ? 3 : 4;
-    const int c = blockIdx.x % C;
-    const size_t plane = blockIdx.x;
-    float wk[K * K];
-#pragma unroll
-    for (int i = 0; i < K * K; ++i) wk[i] = w[(size_t)c * K * K + i];
-    const float* xp = x + plane * H * W;
-    float* yp = y + plane * Ho * Wo;
-    const int Wq = Wo >> 2;
-    for (int q = blockIdx.y * kT + threadIdx.x; q < Ho * Wq; q += gridDim.y * kT) {
-        const int oy = q / Wq, ox = (q - oy * Wq) * 4;
-        const int x0 = S * ox - 4;
-        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int r = 0; r < K; ++r) {
-            const int iy = oy * S - pt + r;
-            if (iy < 0 || iy >= H) continue;
-            float v[NV * 4];
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                const int xs = x0 + 4 * j;
-                float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (xs >= 0 && xs + 3 < W) f = *reinterpret_cast<const float4*>(xp + (size_t)iy * W + xs);
-                v[4 * j] = f.x; v[4 * j + 1] = f.y; v[4 * j + 2] = f.z; v[4 * j + 3] = f.w;
-            }
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    constexpr int kLast = S * 3 - PL + K - 1 + 4;
-                    static_assert(PL <= 4 && kLast < NV * 4, "the quad's window must lie inside the loaded segments");
-                    acc[i] += wk[r * K + t] * v[S * i - PL + t + 4];      // column S*(ox+i) - PL + t
-                }
-            }
-        }
-        *reinterpret_cast<float4*>(yp + (size_t)oy * Wo + ox) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    }
-}
-// gx[b,c,iy,ix] = sum_{r,t} w[c,r,t] * gy[b,c,(iy+pt-r)/s,(ix+pl-t)/s] over the taps that divide.  VEC: W % 4 == 0, one
-// thread per four inputs of a row and one 16-byte store (the gradient loads stay scalar: they are strided by 1/s).
-template <int K, int VEC>
-__global__ __launch_bounds__(kT) void dwsame_bwd_data_kernel(const float* __restrict__ gy, const float* __restrict__ w,
-                                                             float* __restrict__ gx, int C, int H, int W, int Ho, int Wo,
-                                                             int s, int pt, int pl) {
-    const int c = blockIdx.x % C;
-    const size_t plane = blockIdx.x;
-    float wk[K * K];
-#pragma unroll
-    for (int i = 0; i < K * K; ++i) wk[i] = w[(size_t)c * K * K + i];
-    const float* gp = gy + plane * Ho * Wo;
-    float* xp = gx + plane * H * W;
-    const int Wv = W / VEC;
-    for (int q = blockIdx.y * kT + threadIdx.x; q < H * Wv; q += gridDim.y * kT) {
-        const int iy = q / Wv, ix0 = (q - iy * Wv) * VEC;
-        float acc[VEC];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = 0.0f;
-#pragma unroll
-        for (int r = 0; r < K; ++r) {
-            const int ty = iy + pt - r;
-            if (ty < 0 || ty % s) continue;
-            const int oy = ty / s;
-            if (oy >= Ho) continue;
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    const int tx = ix0 + i + pl - t;
-                    if (tx < 0 || tx % s) continue;
-                    const int ox = tx / s;
-                    if (ox < Wo) acc[i] += wk[r * K + t] * gp[oy * Wo + ox];
-                }
-            }
-        }
-        if constexpr (VEC == 4)
-            *reinterpret_cast<float4*>(xp + (size_t)iy * W + ix0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        else
-            xp[(size_t)iy * W + ix0] = acc[0];
-    }
-}
-// Weight gradient, step 1: one workgroup per (channel, image) reduces its plane to k*k sums (each thread its strided
-// share in order, then a fixed-shape fp64 block reduction) -> part[(c*B + b)*K*K + tap].
-template <int K>
-__global__ __launch_bounds__(kT) void dwsame_bwd_weight_kernel(const float* __restrict__ x, const float* __restrict__ gy,
-                                                               float* __restrict__ part, int B, int C, int H, int W,
-                                                               int Ho, int Wo, int s, int pt, int pl) {
-    __shared__ double red[16];
-    const int c = blockIdx.x, b = blockIdx.y;
-    const float* xp = x + ((size_t)b * C + c) * H * W;
-    const float* gp = gy + ((size_t)b * C + c) * Ho * Wo;
-    float acc[K * K];
-#pragma unroll
-    for (int i = 0; i < K * K; ++i) acc[i] = 0.0f;
-    for (int o = threadIdx.x; o < Ho * Wo; o += kT) {
-        const int oy = o / Wo, ox = o - oy * Wo;
-        const float g = gp[o];
-#pragma unroll
-        for (int r = 0; r < K; ++r) {
-            const int iy = oy * s - pt + r;
-            if (iy < 0 || iy >= H) continue;
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                const int ix = ox * s - pl + t;
-                if (ix >= 0 && ix < W) acc[r * K + t] += g * xp[iy * W + ix];
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < K * K; ++i) {
-        const double v = block_sum((double)acc[i], red);
-        if (threadIdx.x == 0) part[((size_t)c * B + b) * K * K + i] = (float)v;
-    }
-}
-// step 2: the images in increasing order
-__global__ void dwsame_wsum_kernel(const float* __restrict__ part, float* __restrict__ gw, int B, int C, int T) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= C * T) return;
-    const int c = i / T, t = i - c * T;
-    float acc = 0.0f;
-    for (int b = 0; b < B; ++b) acc += part[((size_t)c * B + b) * T + t];
-    gw[i] = acc;
 }
 
 // ---------------- swish ----------------
@@ -403,80 +241,10 @@ int launch_scale(const float* x, const float* g, const float* add, float* y, lon
     return 0;
 }
 
-int dwsame_geom(int B, int C, int H, int W, int k, int s, int pt, int pl, int Ho, int Wo, const char* who) {
-    CNUDA_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && (k == 3 || k == 5) && (s == 1 || s == 2), "%s: k must be 3 or 5, stride 1 or 2", who);
-    CNUDA_REQUIRE(pt >= 0 && pl >= 0 && pt < k && pl < k, "%s: top / left padding must lie in [0, k)", who);
-    CNUDA_REQUIRE(Ho > 0 && Wo > 0, "%s: empty output", who);
-    // the implied bottom / right padding (Ho-1)*s + k - pt - H must lie in [0, k) as well: every output sees the map
-    const int pb = (Ho - 1) * s + k - pt - H, pr = (Wo - 1) * s + k - pl - W;
-    CNUDA_REQUIRE(pb >= 0 && pb < k && pr >= 0 && pr < k,
-                  "%s: output %dx%d does not fit input %dx%d (k %d, stride %d, top %d, left %d)", who, Ho, Wo, H, W, k, s, pt, pl);
-    CNUDA_REQUIRE((long long)B * C <= 2147483647LL && (long long)H * W <= 2147483647LL, "%s: tensor too large", who);
-    return 0;
-}
-
 }  // namespace
 }  // namespace cnuda
 
 using namespace cnuda;
-
-extern "C" size_t cnuda_dwconv2d_same_workspace_bytes(int B, int C, int k) {
-    return (size_t)(B > 0 ? B : 0) * (size_t)(C > 0 ? C : 0) * k * k * sizeof(float);
-}
-
-extern "C" int cnuda_dwconv2d_same_forward(const float* x, const float* w, float* y, int B, int C, int H, int W, int k, int s,
-                                           int pad_top, int pad_left, int Ho, int Wo, cnuda_stream_t stream) {
-    if (int rc = dwsame_geom(B, C, H, W, k, s, pad_top, pad_left, Ho, Wo, "cnuda_dwconv2d_same_forward")) return rc;
-    CNUDA_REQUIRE(x && w && y, "cnuda_dwconv2d_same_forward: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    // the quad's window, columns S*ox - PL .. S*(ox+3) - PL + k - 1, lies inside [S*ox - 4, S*ox + 4*NV) for PL <= 2, k <= 5
-    const bool vec = (W % 4 == 0) && (Wo % 4 == 0) && pad_left <= 2;
-    if (vec) {
-        const dim3 grid(B * C, ceil_div((long long)Ho * (Wo / 4), kT) < 64 ? ceil_div((long long)Ho * (Wo / 4), kT) : 64);
-#define CNUDA_DWV(K, S, PL) CNUDA_LAUNCH((dwsame_fwd_vec_kernel<K, S, PL>), grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, pad_top)
-#define CNUDA_DWP(K, S) do { if (pad_left == 0) CNUDA_DWV(K, S, 0); else if (pad_left == 1) CNUDA_DWV(K, S, 1); else CNUDA_DWV(K, S, 2); } while (0)
-        if (k == 3 && s == 1) CNUDA_DWP(3, 1);
-        else if (k == 3) CNUDA_DWP(3, 2);
-        else if (s == 1) CNUDA_DWP(5, 1);
-        else CNUDA_DWP(5, 2);
-#undef CNUDA_DWP
-#undef CNUDA_DWV
-    } else {
-        const dim3 grid(B * C, ceil_div((long long)Ho * Wo, kT) < 64 ? ceil_div((long long)Ho * Wo, kT) : 64);
-        if (k == 3) CNUDA_LAUNCH(dwsame_fwd_kernel<3>, grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, s, pad_top, pad_left);
-        else CNUDA_LAUNCH(dwsame_fwd_kernel<5>, grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, s, pad_top, pad_left);
-    }
-    return check_launch("cnuda_dwconv2d_same_forward");
-}
-
-extern "C" int cnuda_dwconv2d_same_backward(const float* x, const float* w, const float* grad_y, float* grad_x, float* grad_w,
-                                            int B, int C, int H, int W, int k, int s, int pad_top, int pad_left, int Ho, int Wo,
-                                            void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
-    if (int rc = dwsame_geom(B, C, H, W, k, s, pad_top, pad_left, Ho, Wo, "cnuda_dwconv2d_same_backward")) return rc;
-    CNUDA_REQUIRE(x && w && grad_y, "cnuda_dwconv2d_same_backward: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (grad_x) {
-        if (W % 4 == 0) {
-            const dim3 grid(B * C, ceil_div((long long)H * (W / 4), kT) < 64 ? ceil_div((long long)H * (W / 4), kT) : 64);
-            if (k == 3) CNUDA_LAUNCH((dwsame_bwd_data_kernel<3, 4>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pad_top, pad_left);
-            else CNUDA_LAUNCH((dwsame_bwd_data_kernel<5, 4>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pad_top, pad_left);
-        } else {
-            const dim3 grid(B * C, ceil_div((long long)H * W, kT) < 64 ? ceil_div((long long)H * W, kT) : 64);
-            if (k == 3) CNUDA_LAUNCH((dwsame_bwd_data_kernel<3, 1>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pad_top, pad_left);
-            else CNUDA_LAUNCH((dwsame_bwd_data_kernel<5, 1>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pad_top, pad_left);
-        }
-    }
-    if (grad_w) {
-        CNUDA_REQUIRE(workspace && workspace_bytes >= cnuda_dwconv2d_same_workspace_bytes(B, C, k),
-                      "cnuda_dwconv2d_same_backward: workspace too small");
-        CNUDA_REQUIRE(B <= 65535, "cnuda_dwconv2d_same_backward: batch > 65535");
-        float* part = reinterpret_cast<float*>(workspace);
-        if (k == 3) CNUDA_LAUNCH(dwsame_bwd_weight_kernel<3>, dim3(C, B), dim3(kT), 0, st, x, grad_y, part, B, C, H, W, Ho, Wo, s, pad_top, pad_left);
-        else CNUDA_LAUNCH(dwsame_bwd_weight_kernel<5>, dim3(C, B), dim3(kT), 0, st, x, grad_y, part, B, C, H, W, Ho, Wo, s, pad_top, pad_left);
-        CNUDA_LAUNCH(dwsame_wsum_kernel, dim3(ceil_div((long long)C * k * k, 256)), dim3(256), 0, st, part, grad_w, B, C, k * k);
-    }
-    return check_launch("cnuda_dwconv2d_same_backward");
-}
 
 extern "C" int cnuda_swish_forward(const float* x, float* y, long long n, cnuda_stream_t stream) {
     CNUDA_REQUIRE(x && y && n > 0, "cnuda_swish_forward: bad arguments");

@@ -1,9 +1,11 @@
-// HBM-bound spatial / elementwise kernels of the DLA-34 graph (NCHW fp32):
+// HBM-bound spatial / elementwise kernels (NCHW fp32).  Of the DLA-34 graph:
 //   max-pool k=s (Tree.downsample, backends/dla.py:202-203), depthwise
 //   ConvTranspose2d k=2f s=f p=f/2 (IDAUp.up, dla.py:385-388), channel
 //   concat / slice (Root, dla.py:162), elementwise add (IDAUp, dla.py:399),
 //   ReLU / LeakyReLU gradients, and the offset|mask split + sigmoid of
 //   DCN.forward (libs/DCNv2/dcn_v2.py:119-122).
+// Of the other trunks: the windowed max-pool (ResNet stem) and the depthwise convolution, 3x3 / 5x5, with symmetric
+//   padding (MobileNetV2) or TensorFlow "SAME" padding (EfficientNet's MBConv): one kernel family for both.
 #include "common.h"
 
 namespace cnuda {
@@ -418,6 +420,8 @@ __global__ __launch_bounds__(kT) void dwconvt_bwd_k4s2_kernel(const float* __res
     for (int t = threadIdx.x; t < K * K; t += kT)
         part[((size_t)c * B + b) * K * K + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
 }
+// gw[c,tap] = sum_b part[(c*B + b)*T + tap], the images in increasing order: the second step of every depthwise weight
+// gradient (transposed and plain)
 __global__ void dwconvt_wsum_kernel(const float* __restrict__ part, float* __restrict__ gw, int B, int C, int T) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= C * T) return;
@@ -593,15 +597,16 @@ __global__ void split_offset_mask_bwd_kernel(const float* __restrict__ goff, con
 }
 
 
-// ---------------- depthwise convolution (groups == channels) ----------------
-// torchvision MobileNetV2's `ConvBNReLU(hidden, hidden, stride, groups=hidden)`: y[b,c,oy,ox] =
-// sum_{r,t} w[c,r,t] * x[b,c,oy*s-p+r, ox*s-p+t].  HBM-streaming: one thread per output / input element, the k*k
-// weights of the plane in registers.  Weight gradient: one workgroup per (channel, image) reduces its plane to
-// k*k partial sums (fp64 block reduction), a second kernel adds the images in order (reproducible).
+// ---------------- depthwise convolution (groups == channels), top / left padding given ----------------
+// torchvision MobileNetV2's `ConvBNReLU(hidden, hidden, stride, groups=hidden)` (pt = pl = p) and EfficientNet's MBConv
+// with TensorFlow "SAME" padding (pt, pl the smaller halves).  y[b,c,oy,ox] = sum_{r,t} w[c,r,t] * x[b,c, oy*s - pt + r,
+// ox*s - pl + t]; taps outside the map read zero, whichever side they fall off: the bottom / right padding is implied
+// by the output size and may be negative (trailing rows / columns never read).  s, pt, pl are run-time values, any
+// s >= 1 and pt, pl >= 0.  One thread per output, k*k weights in registers.  No float atomics.
 template <int K>
 __global__ __launch_bounds__(kT) void dwconv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         float* __restrict__ y, int C, int H, int W, int Ho, int Wo,
-                                                        int s, int p) {
+                                                        int s, int pt, int pl) {
     const int c = blockIdx.x % C;
     const size_t plane = blockIdx.x;
     float wk[K * K];
@@ -614,21 +619,70 @@ __global__ __launch_bounds__(kT) void dwconv_fwd_kernel(const float* __restrict_
         float acc = 0.0f;
 #pragma unroll
         for (int r = 0; r < K; ++r) {
-            const int iy = oy * s - p + r;
+            const int iy = oy * s - pt + r;
             if (iy < 0 || iy >= H) continue;
 #pragma unroll
             for (int t = 0; t < K; ++t) {
-                const int ix = ox * s - p + t;
+                const int ix = ox * s - pl + t;
                 if (ix >= 0 && ix < W) acc += wk[r * K + t] * xp[iy * W + ix];
             }
         }
         yp[o] = acc;
     }
 }
-template <int K>
+// W % 4 == 0 and Wo % 4 == 0, stride S 1 or 2, left padding PL in 0..2 (what p = (k-1)/2 and SAME padding give k = 3
+// and 5; a compile-time constant, so the row window stays in registers): one thread per four outputs of a row.
+// The input window of the quad lies inside the NV aligned float4 segments that start at column S*ox - 4 (a segment is
+// wholly inside or wholly outside the row, because W is a multiple of 4): 16-byte loads, one 16-byte store; taps are
+// accumulated in the scalar kernel's order (r, then t), so both paths round alike.
+template <int K, int S, int PL>
+__global__ __launch_bounds__(kT) void dwconv_fwd_vec_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                            float* __restrict__ y, int C, int H, int W, int Ho, int Wo,
+                                                            int pt) {
+    constexpr int NV = S == 1 ? 3 : 4;
+    const int c = blockIdx.x % C;
+    const size_t plane = blockIdx.x;
+    float wk[K * K];
+#pragma unroll
+    for (int i = 0; i < K * K; ++i) wk[i] = w[(size_t)c * K * K + i];
+    const float* xp = x + plane * H * W;
+    float* yp = y + plane * Ho * Wo;
+    const int Wq = Wo >> 2;
+    for (int q = blockIdx.y * kT + threadIdx.x; q < Ho * Wq; q += gridDim.y * kT) {
+        const int oy = q / Wq, ox = (q - oy * Wq) * 4;
+        const int x0 = S * ox - 4;
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int r = 0; r < K; ++r) {
+            const int iy = oy * S - pt + r;
+            if (iy < 0 || iy >= H) continue;
+            float v[NV * 4];
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int xs = x0 + 4 * j;
+                float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (xs >= 0 && xs + 3 < W) f = *reinterpret_cast<const float4*>(xp + (size_t)iy * W + xs);
+                v[4 * j] = f.x; v[4 * j + 1] = f.y; v[4 * j + 2] = f.z; v[4 * j + 3] = f.w;
+            }
+#pragma unroll
+            for (int t = 0; t < K; ++t) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    constexpr int kLast = S * 3 - PL + K - 1 + 4;
+                    static_assert(PL <= 4 && kLast < NV * 4, "the quad's window must lie inside the loaded segments");
+                    acc[i] += wk[r * K + t] * v[S * i - PL + t + 4];      // column S*(ox+i) - PL + t
+                }
+            }
+        }
+        *reinterpret_cast<float4*>(yp + (size_t)oy * Wo + ox) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+}
+// gx[b,c,iy,ix] = sum_{r,t} w[c,r,t] * gy[b,c,(iy+pt-r)/s,(ix+pl-t)/s] over the taps that divide.  VEC: W % 4 == 0, one
+// thread per four inputs of a row and one 16-byte store (the gradient loads stay scalar: they are strided by 1/s).
+template <int K, int VEC>
 __global__ __launch_bounds__(kT) void dwconv_bwd_data_kernel(const float* __restrict__ gy, const float* __restrict__ w,
                                                              float* __restrict__ gx, int C, int H, int W, int Ho, int Wo,
-                                                             int s, int p) {
+                                                             int s, int pt, int pl) {
     const int c = blockIdx.x % C;
     const size_t plane = blockIdx.x;
     float wk[K * K];
@@ -636,31 +690,41 @@ __global__ __launch_bounds__(kT) void dwconv_bwd_data_kernel(const float* __rest
     for (int i = 0; i < K * K; ++i) wk[i] = w[(size_t)c * K * K + i];
     const float* gp = gy + plane * Ho * Wo;
     float* xp = gx + plane * H * W;
-    for (int i = blockIdx.y * kT + threadIdx.x; i < H * W; i += gridDim.y * kT) {
-        const int iy = i / W, ix = i - iy * W;
-        float acc = 0.0f;
+    const int Wv = W / VEC;
+    for (int q = blockIdx.y * kT + threadIdx.x; q < H * Wv; q += gridDim.y * kT) {
+        const int iy = q / Wv, ix0 = (q - iy * Wv) * VEC;
+        float acc[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) acc[i] = 0.0f;
 #pragma unroll
         for (int r = 0; r < K; ++r) {
-            const int ty = iy + p - r;
+            const int ty = iy + pt - r;
             if (ty < 0 || ty % s) continue;
             const int oy = ty / s;
             if (oy >= Ho) continue;
 #pragma unroll
             for (int t = 0; t < K; ++t) {
-                const int tx = ix + p - t;
-                if (tx < 0 || tx % s) continue;
-                const int ox = tx / s;
-                if (ox < Wo) acc += wk[r * K + t] * gp[oy * Wo + ox];
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    const int tx = ix0 + i + pl - t;
+                    if (tx < 0 || tx % s) continue;
+                    const int ox = tx / s;
+                    if (ox < Wo) acc[i] += wk[r * K + t] * gp[oy * Wo + ox];
+                }
             }
         }
-        xp[i] = acc;
+        if constexpr (VEC == 4)
+            *reinterpret_cast<float4*>(xp + (size_t)iy * W + ix0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        else
+            xp[(size_t)iy * W + ix0] = acc[0];
     }
 }
-// part[(c*B + b)*K*K + tap]
+// Weight gradient, step 1: one workgroup per (channel, image) reduces its plane to k*k sums (each thread its strided
+// share in order, then a fixed-shape fp64 block reduction) -> part[(c*B + b)*K*K + tap].  Step 2 is dwconvt_wsum_kernel.
 template <int K>
 __global__ __launch_bounds__(kT) void dwconv_bwd_weight_kernel(const float* __restrict__ x, const float* __restrict__ gy,
                                                                float* __restrict__ part, int B, int C, int H, int W,
-                                                               int Ho, int Wo, int s, int p) {
+                                                               int Ho, int Wo, int s, int pt, int pl) {
     __shared__ double red[16];
     const int c = blockIdx.x, b = blockIdx.y;
     const float* xp = x + ((size_t)b * C + c) * H * W;
@@ -673,11 +737,11 @@ __global__ __launch_bounds__(kT) void dwconv_bwd_weight_kernel(const float* __re
         const float g = gp[o];
 #pragma unroll
         for (int r = 0; r < K; ++r) {
-            const int iy = oy * s - p + r;
+            const int iy = oy * s - pt + r;
             if (iy < 0 || iy >= H) continue;
 #pragma unroll
             for (int t = 0; t < K; ++t) {
-                const int ix = ox * s - p + t;
+                const int ix = ox * s - pl + t;
                 if (ix >= 0 && ix < W) acc[r * K + t] += g * xp[iy * W + ix];
             }
         }
@@ -788,52 +852,122 @@ extern "C" int cnuda_dwconvt2d_forward(const float* x, const float* w, float* y,
                                        int s, int p, cnuda_stream_t stream) {
     return cnuda_dwconvt2d_add_forward(x, w, nullptr, y, B, C, H, W, k, s, p, stream);
 }
-extern "C" size_t cnuda_dwconv2d_workspace_bytes(int B, int C, int k) {
+// ---- depthwise convolution: cnuda_dwconv2d_* (symmetric padding p, torch's floor rule for the output size) and
+// cnuda_dwconv2d_same_* (top / left padding and the output size given) share the kernels and the two launch bodies ----
+// per-image partial weight gradients [C][B][k*k] of every depthwise backward, the transposed one included
+static size_t dw_workspace_bytes(int B, int C, int k) {
     return (size_t)(B > 0 ? B : 0) * (C > 0 ? C : 0) * k * k * sizeof(float) + 256;
 }
+extern "C" size_t cnuda_dwconv2d_workspace_bytes(int B, int C, int k) { return dw_workspace_bytes(B, C, k); }
+extern "C" size_t cnuda_dwconv2d_same_workspace_bytes(int B, int C, int k) { return dw_workspace_bytes(B, C, k); }
+extern "C" size_t cnuda_dwconvt2d_workspace_bytes(int B, int C, int k) { return dw_workspace_bytes(B, C, k); }
+
+// one plane per blockIdx.x, up to 64 workgroups stride over its `items`
+static dim3 dwconv_grid(int planes, long long items) {
+    const int g = ceil_div(items, kT);
+    return dim3(planes, g < 64 ? g : 64);
+}
+// The launch bodies.  The entry (`who` in messages) has checked its own contract, which is at least: B, C, H, W, Ho,
+// Wo > 0, k 3 or 5, s >= 1, pt, pl >= 0.  Whatever the 16-byte forms do not take goes to the scalar kernels, which are
+// right for every such geometry and accumulate in the same order.
+static int dwconv_forward(const char* who, const float* x, const float* w, float* y, int B, int C, int H, int W, int k,
+                          int s, int pt, int pl, int Ho, int Wo, hipStream_t st) {
+    CNUDA_REQUIRE(x && w && y, "%s: null pointer", who);
+    CNUDA_REQUIRE((long long)B * C <= 2147483647LL && (long long)H * W <= 2147483647LL && (long long)Ho * Wo <= 2147483647LL,
+                  "%s: tensor too large", who);
+    // the quad's window, columns S*ox - PL .. S*(ox+3) - PL + k - 1, lies inside [S*ox - 4, S*ox + 4*NV) for S <= 2, PL <= 2, k <= 5
+    const bool vec = (W % 4 == 0) && (Wo % 4 == 0) && pl <= 2 && s <= 2 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+    if (vec) {
+        const dim3 grid = dwconv_grid(B * C, (long long)Ho * (Wo / 4));
+#define CNUDA_DWV(K, S, PL) CNUDA_LAUNCH((dwconv_fwd_vec_kernel<K, S, PL>), grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, pt)
+#define CNUDA_DWP(K, S) do { if (pl == 0) CNUDA_DWV(K, S, 0); else if (pl == 1) CNUDA_DWV(K, S, 1); else CNUDA_DWV(K, S, 2); } while (0)
+        if (k == 3 && s == 1) CNUDA_DWP(3, 1);
+        else if (k == 3) CNUDA_DWP(3, 2);
+        else if (s == 1) CNUDA_DWP(5, 1);
+        else CNUDA_DWP(5, 2);
+#undef CNUDA_DWP
+#undef CNUDA_DWV
+    } else {
+        const dim3 grid = dwconv_grid(B * C, (long long)Ho * Wo);
+        if (k == 3) CNUDA_LAUNCH(dwconv_fwd_kernel<3>, grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, s, pt, pl);
+        else CNUDA_LAUNCH(dwconv_fwd_kernel<5>, grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, s, pt, pl);
+    }
+    return check_launch(who);
+}
+static int dwconv_backward(const char* who, const float* x, const float* w, const float* grad_y, float* grad_x,
+                           float* grad_w, int B, int C, int H, int W, int k, int s, int pt, int pl, int Ho, int Wo,
+                           void* workspace, size_t workspace_bytes, hipStream_t st) {
+    CNUDA_REQUIRE(x && w && grad_y, "%s: null pointer", who);
+    CNUDA_REQUIRE((long long)B * C <= 2147483647LL && (long long)H * W <= 2147483647LL && (long long)Ho * Wo <= 2147483647LL,
+                  "%s: tensor too large", who);
+    if (grad_x) {
+        if (W % 4 == 0 && ((uintptr_t)grad_x & 15) == 0) {
+            const dim3 grid = dwconv_grid(B * C, (long long)H * (W / 4));
+            if (k == 3) CNUDA_LAUNCH((dwconv_bwd_data_kernel<3, 4>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pt, pl);
+            else CNUDA_LAUNCH((dwconv_bwd_data_kernel<5, 4>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pt, pl);
+        } else {
+            const dim3 grid = dwconv_grid(B * C, (long long)H * W);
+            if (k == 3) CNUDA_LAUNCH((dwconv_bwd_data_kernel<3, 1>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pt, pl);
+            else CNUDA_LAUNCH((dwconv_bwd_data_kernel<5, 1>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pt, pl);
+        }
+    }
+    if (grad_w) {
+        CNUDA_REQUIRE(workspace && workspace_bytes >= dw_workspace_bytes(B, C, k), "%s: workspace too small", who);
+        CNUDA_REQUIRE(B <= 65535, "%s: batch > 65535", who);
+        float* part = reinterpret_cast<float*>(workspace);
+        if (k == 3) CNUDA_LAUNCH(dwconv_bwd_weight_kernel<3>, dim3(C, B), dim3(kT), 0, st, x, grad_y, part, B, C, H, W, Ho, Wo, s, pt, pl);
+        else CNUDA_LAUNCH(dwconv_bwd_weight_kernel<5>, dim3(C, B), dim3(kT), 0, st, x, grad_y, part, B, C, H, W, Ho, Wo, s, pt, pl);
+        CNUDA_LAUNCH(dwconvt_wsum_kernel, dim3(ceil_div((long long)C * k * k, 256)), dim3(256), 0, st, part, grad_w, B, C, k * k);
+    }
+    return check_launch(who);
+}
+
+// any stride s >= 1 and padding p >= 0; the output size by torch's floor rule
 static int dwconv_geom(int B, int C, int H, int W, int k, int s, int p, int& Ho, int& Wo, const char* who) {
     CNUDA_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && s > 0 && p >= 0, "%s: bad arguments", who);
     CNUDA_REQUIRE(k == 3 || k == 5, "%s: kernel size %d (3 and 5 are built)", who, k);
-    CNUDA_REQUIRE((long long)B * C <= 2147483647ll, "%s: too many planes", who);
+    CNUDA_REQUIRE(H + 2 * p >= k && W + 2 * p >= k, "%s: empty output", who);
     Ho = (H + 2 * p - k) / s + 1;
     Wo = (W + 2 * p - k) / s + 1;
-    CNUDA_REQUIRE(Ho > 0 && Wo > 0, "%s: empty output", who);
     return 0;
 }
 extern "C" int cnuda_dwconv2d_forward(const float* x, const float* w, float* y, int B, int C, int H, int W, int k,
                                       int s, int p, cnuda_stream_t stream) {
     int Ho, Wo;
     if (int rc = dwconv_geom(B, C, H, W, k, s, p, Ho, Wo, "cnuda_dwconv2d_forward")) return rc;
-    CNUDA_REQUIRE(x && w && y, "cnuda_dwconv2d_forward: null pointer");
-    const dim3 grid(B * C, ceil_div(ceil_div(Ho * Wo, kT), 4) > 0 ? ceil_div(ceil_div(Ho * Wo, kT), 4) : 1);
-    if (k == 3) CNUDA_LAUNCH(dwconv_fwd_kernel<3>, grid, dim3(kT), 0, (hipStream_t)stream, x, w, y, C, H, W, Ho, Wo, s, p);
-    else CNUDA_LAUNCH(dwconv_fwd_kernel<5>, grid, dim3(kT), 0, (hipStream_t)stream, x, w, y, C, H, W, Ho, Wo, s, p);
-    return check_launch("cnuda_dwconv2d_forward");
+    return dwconv_forward("cnuda_dwconv2d_forward", x, w, y, B, C, H, W, k, s, p, p, Ho, Wo, (hipStream_t)stream);
 }
 extern "C" int cnuda_dwconv2d_backward(const float* x, const float* w, const float* grad_y, float* grad_x, float* grad_w,
                                        int B, int C, int H, int W, int k, int s, int p, void* workspace,
                                        size_t workspace_bytes, cnuda_stream_t stream) {
     int Ho, Wo;
     if (int rc = dwconv_geom(B, C, H, W, k, s, p, Ho, Wo, "cnuda_dwconv2d_backward")) return rc;
-    CNUDA_REQUIRE(x && w && grad_y, "cnuda_dwconv2d_backward: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (grad_x) {
-        const dim3 grid(B * C, ceil_div(ceil_div(H * W, kT), 4) > 0 ? ceil_div(ceil_div(H * W, kT), 4) : 1);
-        if (k == 3) CNUDA_LAUNCH(dwconv_bwd_data_kernel<3>, grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, p);
-        else CNUDA_LAUNCH(dwconv_bwd_data_kernel<5>, grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, p);
-    }
-    if (grad_w) {
-        CNUDA_REQUIRE(workspace && workspace_bytes >= cnuda_dwconv2d_workspace_bytes(B, C, k), "cnuda_dwconv2d_backward: workspace too small");
-        CNUDA_REQUIRE(C <= 2147483647 && B <= 65535, "cnuda_dwconv2d_backward: batch > 65535");
-        float* part = (float*)workspace;
-        if (k == 3) CNUDA_LAUNCH(dwconv_bwd_weight_kernel<3>, dim3(C, B), dim3(kT), 0, st, x, grad_y, part, B, C, H, W, Ho, Wo, s, p);
-        else CNUDA_LAUNCH(dwconv_bwd_weight_kernel<5>, dim3(C, B), dim3(kT), 0, st, x, grad_y, part, B, C, H, W, Ho, Wo, s, p);
-        CNUDA_LAUNCH(dwconvt_wsum_kernel, dim3(ceil_div((long long)C * k * k, 256)), dim3(256), 0, st, part, grad_w, B, C, k * k);
-    }
-    return check_launch("cnuda_dwconv2d_backward");
+    return dwconv_backward("cnuda_dwconv2d_backward", x, w, grad_y, grad_x, grad_w, B, C, H, W, k, s, p, p, Ho, Wo, workspace,
+                           workspace_bytes, (hipStream_t)stream);
 }
-extern "C" size_t cnuda_dwconvt2d_workspace_bytes(int B, int C, int k) {
-    return (size_t)(B > 0 ? B : 0) * (C > 0 ? C : 0) * k * k * sizeof(float) + 256;
+
+// stride 1 or 2; top / left padding and the bottom / right padding that the output size implies all in [0, k)
+static int dwconv_same_geom(int B, int C, int H, int W, int k, int s, int pt, int pl, int Ho, int Wo, const char* who) {
+    CNUDA_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && (k == 3 || k == 5) && (s == 1 || s == 2), "%s: k must be 3 or 5, stride 1 or 2", who);
+    CNUDA_REQUIRE(pt >= 0 && pl >= 0 && pt < k && pl < k, "%s: top / left padding must lie in [0, k)", who);
+    CNUDA_REQUIRE(Ho > 0 && Wo > 0, "%s: empty output", who);
+    // the implied bottom / right padding (Ho-1)*s + k - pt - H must lie in [0, k) as well: every output sees the map
+    const int pb = (Ho - 1) * s + k - pt - H, pr = (Wo - 1) * s + k - pl - W;
+    CNUDA_REQUIRE(pb >= 0 && pb < k && pr >= 0 && pr < k,
+                  "%s: output %dx%d does not fit input %dx%d (k %d, stride %d, top %d, left %d)", who, Ho, Wo, H, W, k, s, pt, pl);
+    return 0;
+}
+extern "C" int cnuda_dwconv2d_same_forward(const float* x, const float* w, float* y, int B, int C, int H, int W, int k, int s,
+                                           int pad_top, int pad_left, int Ho, int Wo, cnuda_stream_t stream) {
+    if (int rc = dwconv_same_geom(B, C, H, W, k, s, pad_top, pad_left, Ho, Wo, "cnuda_dwconv2d_same_forward")) return rc;
+    return dwconv_forward("cnuda_dwconv2d_same_forward", x, w, y, B, C, H, W, k, s, pad_top, pad_left, Ho, Wo, (hipStream_t)stream);
+}
+extern "C" int cnuda_dwconv2d_same_backward(const float* x, const float* w, const float* grad_y, float* grad_x, float* grad_w,
+                                            int B, int C, int H, int W, int k, int s, int pad_top, int pad_left, int Ho, int Wo,
+                                            void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
+    if (int rc = dwconv_same_geom(B, C, H, W, k, s, pad_top, pad_left, Ho, Wo, "cnuda_dwconv2d_same_backward")) return rc;
+    return dwconv_backward("cnuda_dwconv2d_same_backward", x, w, grad_y, grad_x, grad_w, B, C, H, W, k, s, pad_top, pad_left, Ho,
+                           Wo, workspace, workspace_bytes, (hipStream_t)stream);
 }
 extern "C" int cnuda_dwconvt2d_backward(const float* x, const float* w, const float* grad_y, float* grad_x,
                                         float* grad_w, int B, int C, int H, int W, int k, int s, int p,

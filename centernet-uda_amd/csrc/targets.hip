@@ -6,10 +6,10 @@
 // identical; the splat is exp() in double, cast to float32 and merged with an integer atomicMax (non-negative
 // floats order like their bit patterns), which makes overlapping objects order-independent like np.maximum.
 //
-// encode_targets_modes_kernel covers the rest of the batch schema (coco.py:176-184,217-233 and 303-376): keypoint
-// targets, the annotation's own `area`, and rotated boxes from four corner points.  The enclosing rectangle of the
-// four points (the reference's cv2.minAreaRect) is defined geometrically: the least-area rectangle with a side along
-// an edge of the convex hull, in double from the float32 points ("Target modes").
+// encode_targets_kernel<ROT> covers the whole batch schema: the plain boxes above and (coco.py:176-184,217-233 and
+// 303-376) keypoint targets, the annotation's own `area`, and rotated boxes from four corner points.  The enclosing
+// rectangle of the four points (the reference's cv2.minAreaRect) is defined geometrically: the least-area rectangle
+// with a side along an edge of the convex hull, in double from the float32 points ("Target modes").
 #include "common.h"
 
 namespace cnuda {
@@ -51,39 +51,6 @@ __device__ __forceinline__ void splat_gaussian(float* __restrict__ hm, int b, in
     }
 }
 
-__global__ __launch_bounds__(256) void encode_targets_kernel(
-    const double* __restrict__ boxes, const int* __restrict__ classes, const int* __restrict__ counts,
-    float* __restrict__ hm, unsigned char* __restrict__ reg_mask, long long* __restrict__ ind,
-    float* __restrict__ wh, float* __restrict__ reg, float* __restrict__ gt_dets, float* __restrict__ gt_areas,
-    int C, int H, int W, int M) {
-    const int b = blockIdx.y, k = blockIdx.x;
-    if (k >= counts[b]) return;
-    const double* bx = boxes + ((size_t)b * M + k) * 4;
-    const double x1 = fmin(fmax(bx[0], 0.0), (double)(W - 1)), x2 = fmin(fmax(bx[2], 0.0), (double)(W - 1));
-    const double y1 = fmin(fmax(bx[1], 0.0), (double)(H - 1)), y2 = fmin(fmax(bx[3], 0.0), (double)(H - 1));
-    const double h = y2 - y1, w = x2 - x1;
-    if (!(h > 0 && w > 0)) return;
-    const int cls = classes[(size_t)b * M + k];
-    if (cls < 0 || cls >= C) return;
-    int radius = (int)gaussian_radius(ceil(h), ceil(w));     // int(): truncation (the radius is never negative)
-    if (radius < 0) radius = 0;
-    const float ctx = (float)((x1 + x2) / 2), cty = (float)((y1 + y2) / 2);
-    const int cx = (int)ctx, cy = (int)cty;
-    if (threadIdx.x == 0) {
-        const size_t o = (size_t)b * M + k;
-        wh[o * 2] = (float)w; wh[o * 2 + 1] = (float)h;
-        ind[o] = (long long)cy * W + cx;
-        reg[o * 2] = ctx - (float)cx; reg[o * 2 + 1] = cty - (float)cy;
-        reg_mask[o] = 1;
-        // gt_det is assigned as a float64 tuple and cast to float32 (coco.py:219-220)
-        gt_dets[o * 6 + 0] = (float)((double)ctx - w / 2); gt_dets[o * 6 + 1] = (float)((double)cty - h / 2);
-        gt_dets[o * 6 + 2] = (float)((double)ctx + w / 2); gt_dets[o * 6 + 3] = (float)((double)cty + h / 2);
-        gt_dets[o * 6 + 4] = 1.0f; gt_dets[o * 6 + 5] = (float)cls;
-        gt_areas[o] = (float)(w * h);
-    }
-    splat_gaussian(hm, b, cls, cx, cy, radius, C, H, W);
-}
-
 // The enclosing rectangle with a side along the line through points I and J, if that line carries an edge of the
 // convex hull (every point on one closed side of it) and the rectangle is smaller than the best so far.  Projections
 // stay unnormalised (dot and cross with d = pJ - pI), so collinear points give a cross extent of exactly 0: the
@@ -116,10 +83,10 @@ __device__ __forceinline__ void try_edge(const double (&x)[4], const double (&y)
     best.dx = dx; best.dy = dy;
 }
 
-// One workgroup per (image, slot), like encode_targets_kernel.  ROT: the object is four corner points
+// One workgroup per (image, slot).  ROT: the object is four corner points
 // (coco.py:329-358) instead of a box (coco.py:191-215).  kps / areas may be null (J == 0: no keypoints).
 template <bool ROT>
-__global__ __launch_bounds__(256) void encode_targets_modes_kernel(
+__global__ __launch_bounds__(256) void encode_targets_kernel(
     const double* __restrict__ geom, const int* __restrict__ classes, const int* __restrict__ counts,
     const double* __restrict__ keypoints, const int* __restrict__ visibility, const float* __restrict__ areas,
     float* __restrict__ hm, unsigned char* __restrict__ reg_mask, long long* __restrict__ ind,
@@ -172,12 +139,13 @@ __global__ __launch_bounds__(256) void encode_targets_modes_kernel(
         if (!(h > 0 && w > 0)) return;
         ctx = (float)((x1 + x2) / 2); cty = (float)((y1 + y2) / 2);
         wh3[0] = (float)w; wh3[1] = (float)h; wh3[2] = 0.0f;
+        // gt_det is assigned as a float64 tuple and cast to float32 (coco.py:219-220)
         det4[0] = (float)((double)ctx - w / 2); det4[1] = (float)((double)cty - h / 2);
         det4[2] = (float)((double)ctx + w / 2); det4[3] = (float)((double)cty + h / 2);
         area = (float)(w * h);
         rh = ceil(h); rw = ceil(w);
     }
-    int radius = (int)gaussian_radius(rh, rw);
+    int radius = (int)gaussian_radius(rh, rw);              // int(): truncation (the radius is never negative)
     if (radius < 0) radius = 0;
     const int cx = (int)ctx, cy = (int)cty;
     if (threadIdx.x == 0) {
@@ -219,21 +187,8 @@ using namespace cnuda;
 extern "C" int cnuda_encode_targets(const double* boxes, const int* classes, const int* counts, float* hm,
                                     unsigned char* reg_mask, long long* ind, float* wh, float* reg, float* gt_dets,
                                     float* gt_areas, int B, int C, int H, int W, int M, cnuda_stream_t stream) {
-    CNUDA_REQUIRE(boxes && classes && counts && hm && reg_mask && ind && wh && reg && gt_dets && gt_areas,
-                  "cnuda_encode_targets: null pointer");
-    CNUDA_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && M > 0 && B <= 65535, "cnuda_encode_targets: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    // the outputs start from zeros like the reference's np.zeros (coco.py:168-174)
-    (void)hipMemsetAsync(hm, 0, (size_t)B * C * H * W * sizeof(float), st);
-    (void)hipMemsetAsync(reg_mask, 0, (size_t)B * M, st);
-    (void)hipMemsetAsync(ind, 0, (size_t)B * M * sizeof(long long), st);
-    (void)hipMemsetAsync(wh, 0, (size_t)B * M * 2 * sizeof(float), st);
-    (void)hipMemsetAsync(reg, 0, (size_t)B * M * 2 * sizeof(float), st);
-    (void)hipMemsetAsync(gt_dets, 0, (size_t)B * M * 6 * sizeof(float), st);
-    (void)hipMemsetAsync(gt_areas, 0, (size_t)B * M * sizeof(float), st);
-    CNUDA_LAUNCH(encode_targets_kernel, dim3(M, B), dim3(256), 0, st, boxes, classes, counts, hm, reg_mask, ind,
-                       wh, reg, gt_dets, gt_areas, C, H, W, M);
-    return check_launch("cnuda_encode_targets");
+    return cnuda_encode_targets_modes(boxes, nullptr, classes, counts, nullptr, nullptr, nullptr, hm, reg_mask, ind, wh, reg,
+                                      gt_dets, gt_areas, nullptr, nullptr, nullptr, B, C, H, W, M, 0, stream);
 }
 
 extern "C" int cnuda_encode_targets_modes(const double* boxes, const double* corners, const int* classes,
@@ -254,6 +209,7 @@ extern "C" int cnuda_encode_targets_modes(const double* boxes, const double* cor
     hipStream_t st = (hipStream_t)stream;
     const bool rot = corners != nullptr;
     const size_t BM = (size_t)B * M;
+    // the outputs start from zeros like the reference's np.zeros (coco.py:168-174)
     (void)hipMemsetAsync(hm, 0, (size_t)B * C * H * W * sizeof(float), st);
     (void)hipMemsetAsync(reg_mask, 0, BM, st);
     (void)hipMemsetAsync(ind, 0, BM * sizeof(long long), st);
@@ -267,11 +223,11 @@ extern "C" int cnuda_encode_targets_modes(const double* boxes, const double* cor
         (void)hipMemsetAsync(kp_reg_mask, 0, BM * 2 * J, st);
     }
     if (rot)
-        CNUDA_LAUNCH(encode_targets_modes_kernel<true>, dim3(M, B), dim3(256), 0, st, corners, classes, counts,
+        CNUDA_LAUNCH(encode_targets_kernel<true>, dim3(M, B), dim3(256), 0, st, corners, classes, counts,
                      keypoints, visibility, areas, hm, reg_mask, ind, wh, reg, gt_dets, gt_areas, kps, gt_kps,
                      kp_reg_mask, C, H, W, M, J);
     else
-        CNUDA_LAUNCH(encode_targets_modes_kernel<false>, dim3(M, B), dim3(256), 0, st, boxes, classes, counts,
+        CNUDA_LAUNCH(encode_targets_kernel<false>, dim3(M, B), dim3(256), 0, st, boxes, classes, counts,
                      keypoints, visibility, areas, hm, reg_mask, ind, wh, reg, gt_dets, gt_areas, kps, gt_kps,
                      kp_reg_mask, C, H, W, M, J);
     return check_launch("cnuda_encode_targets_modes");

@@ -9,7 +9,7 @@ int32 (already mapped through `cat_mapping`), `counts` [B] int32.  Returns the d
 and dtypes (`reg_mask` uint8, `ind` int64).
 
 Keyword arguments select the loop's other modes (all coordinates at output-map resolution: after `resize_out`,
-before the loop's `np.clip`); any of them routes the call to `cnuda_encode_targets_modes`:
+before the loop's `np.clip`).  Every call, with or without them, is one `cnuda_encode_targets_modes`:
 
 `corners` [B, M, 4, 2] float64, with `boxes=None`: rotated boxes (coco.py:303-312,329-358).  The four points are
     clipped to the map and rounded to float32; the object is their minimum-area enclosing rectangle -- the
@@ -48,32 +48,9 @@ def _alloc(B, M, num_classes, output_h, output_w, ncol, dev):
 def encode_targets(boxes, classes, counts, num_classes, output_h, output_w, *,
                    corners=None, keypoints=None, visibility=None, areas=None):
     require_gpu(boxes, classes, counts, corners, keypoints, visibility, areas)
-    if corners is None and keypoints is None and visibility is None and areas is None:
-        if boxes is None:
-            raise RuntimeError("encode_targets: boxes or corners must be given")
-        if boxes.dim() != 3 or boxes.shape[2] != 4:
-            raise RuntimeError("encode_targets: boxes must be [B, M, 4], got %s" % (tuple(boxes.shape),))
-        B, M = boxes.shape[0], boxes.shape[1]
-        if tuple(classes.shape) != (B, M) or tuple(counts.shape) != (B,):
-            raise RuntimeError("encode_targets: classes %s / counts %s do not match boxes %s"
-                               % (tuple(classes.shape), tuple(counts.shape), tuple(boxes.shape)))
-        boxes = boxes.to(torch.float64).contiguous()
-        classes = classes.to(torch.int32).contiguous()
-        counts = counts.to(torch.int32).clamp(max=M).contiguous()
-        out = _alloc(B, M, num_classes, output_h, output_w, 2, boxes.device)
-        check(lib().cnuda_encode_targets(ptr(boxes), ptr(classes), ptr(counts), ptr(out['hm']), ptr(out['reg_mask']),
-                                         ptr(out['ind']), ptr(out['wh']), ptr(out['reg']), ptr(out['gt_dets']),
-                                         ptr(out['gt_areas']), B, num_classes, output_h, output_w, M, stream()),
-              'encode_targets')
-        return out
-    return _encode_modes(boxes, classes, counts, num_classes, output_h, output_w, corners, keypoints, visibility,
-                         areas)
-
-
-def _encode_modes(boxes, classes, counts, num_classes, output_h, output_w, corners, keypoints, visibility, areas):
     if (boxes is None) == (corners is None):
-        raise RuntimeError("encode_targets: give either boxes or corners (with boxes=None), not %s"
-                           % ("both" if boxes is not None else "neither"))
+        raise RuntimeError("encode_targets: boxes or corners must be given" if boxes is None else
+                           "encode_targets: give either boxes or corners (with boxes=None), not both")
     rotated = corners is not None
     geom = corners if rotated else boxes
     tail = (4, 2) if rotated else (4,)

@@ -596,62 +596,29 @@ def depthwise_conv_transpose2d(x, weight, stride, padding, skip=None):
     return _DwConvT.apply(x, weight, int(stride), int(padding), skip)
 
 
-class _DwConv(Function):
-    """Depthwise convolution (groups == channels), weight [C,1,k,k], no bias."""
+class _DwConvSame(Function):
+    """Depthwise convolution (groups == channels), weight [C,1,k,k], no bias: pads = (top, left, bottom, right) zeros,
+    which may differ per side (TensorFlow's "SAME" padding) or be torch's one `padding`.  Both entry pairs of the library
+    run the same kernels; `same` picks the pair, and with it the argument contract: cnuda_dwconv2d_same_* (stride 1 or 2,
+    every side's padding below k) or cnuda_dwconv2d_* (pads all equal; any stride and padding)."""
 
     @staticmethod
-    def forward(ctx, x, weight, stride, padding):
+    def forward(ctx, x, weight, stride, pads, same=True):
         require_gpu(x, weight)
         x, weight = f32c(x), f32c(weight)
         B, C, H, W = x.shape
         k = weight.shape[2]
         if weight.shape[0] != C or weight.shape[1] != 1 or weight.shape[3] != k:
             raise RuntimeError("depthwise conv2d: weight %s does not fit %d channels" % (tuple(weight.shape), C))
-        Ho, Wo = (H + 2 * padding - k) // stride + 1, (W + 2 * padding - k) // stride + 1
-        y = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device)
-        check(lib().cnuda_dwconv2d_forward(ptr(x), ptr(weight), ptr(y), B, C, H, W, k, stride, padding, stream()),
-              'dwconv2d_forward')
-        ctx.geom = (B, C, H, W, k, stride, padding)
-        ctx.save_for_backward(x, weight)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
-        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        gw_buf, gw = _param_grad(weight, ctx.needs_input_grad[1])
-        L = lib()
-        B, C, _, _, k = ctx.geom[:5]
-        wp, wn = _ws(L.cnuda_dwconv2d_workspace_bytes(B, C, k), x)
-        check(L.cnuda_dwconv2d_backward(ptr(x), ptr(weight), ptr(f32c(gy)), ptr(gx), ptr(gw_buf), *ctx.geom,
-                                        wp, wn, stream()), 'dwconv2d_backward')
-        return gx, gw, None, None
-
-
-def depthwise_conv2d(x, weight, stride=1, padding=0):
-    return _DwConv.apply(x, weight, int(stride), int(padding))
-
-
-class _DwConvSame(Function):
-    """Depthwise convolution with TensorFlow "SAME" padding: pads = (top, left, bottom, right) zeros, which may differ
-    per side; weight [C,1,k,k], no bias (cnuda_dwconv2d_same_*)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, stride, pads):
-        require_gpu(x, weight)
-        x, weight = f32c(x), f32c(weight)
-        B, C, H, W = x.shape
-        k = weight.shape[2]
-        if weight.shape[0] != C or weight.shape[1] != 1 or weight.shape[3] != k:
-            raise RuntimeError("depthwise conv2d (same): weight %s does not fit %d channels" % (tuple(weight.shape), C))
         pt, pl, pb, pr = pads
         Ho, Wo = (H + pt + pb - k) // stride + 1, (W + pl + pr - k) // stride + 1
         if Ho < 1 or Wo < 1:
-            raise RuntimeError("depthwise conv2d (same): a %dx%d map with padding %s is smaller than the kernel" % (H, W, pads))
+            raise RuntimeError("depthwise conv2d: a %dx%d map with padding %s is smaller than the kernel" % (H, W, pads))
         y = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device)
-        ctx.geom = (B, C, H, W, k, stride, pt, pl, Ho, Wo)
-        check(lib().cnuda_dwconv2d_same_forward(ptr(x), ptr(weight), ptr(y), *ctx.geom, stream()), 'dwconv2d_same_forward')
+        ctx.entry = 'dwconv2d_same' if same else 'dwconv2d'
+        ctx.geom = (B, C, H, W, k, stride, pt, pl, Ho, Wo) if same else (B, C, H, W, k, stride, pt)
+        check(getattr(lib(), 'cnuda_%s_forward' % ctx.entry)(ptr(x), ptr(weight), ptr(y), *ctx.geom, stream()),
+              ctx.entry + '_forward')
         ctx.save_for_backward(x, weight)
         return y
 
@@ -663,10 +630,10 @@ class _DwConvSame(Function):
         gw_buf, gw = _param_grad(weight, ctx.needs_input_grad[1])
         L = lib()
         B, C, _, _, k = ctx.geom[:5]
-        wp, wn = _ws(L.cnuda_dwconv2d_same_workspace_bytes(B, C, k), x)
-        check(L.cnuda_dwconv2d_same_backward(ptr(x), ptr(weight), ptr(f32c(gy)), ptr(gx), ptr(gw_buf), *ctx.geom,
-                                             wp, wn, stream()), 'dwconv2d_same_backward')
-        return gx, gw, None, None
+        wp, wn = _ws(getattr(L, 'cnuda_%s_workspace_bytes' % ctx.entry)(B, C, k), x)
+        check(getattr(L, 'cnuda_%s_backward' % ctx.entry)(ptr(x), ptr(weight), ptr(f32c(gy)), ptr(gx), ptr(gw_buf),
+                                                          *ctx.geom, wp, wn, stream()), ctx.entry + '_backward')
+        return gx, gw, None, None, None
 
 
 def same_padding(size, kernel_size, stride):
@@ -674,6 +641,11 @@ def same_padding(size, kernel_size, stride):
     the smaller half in front."""
     total = max((-(-size // stride) - 1) * stride + kernel_size - size, 0)
     return total // 2, total - total // 2
+
+
+def depthwise_conv2d(x, weight, stride=1, padding=0):
+    """nn.Conv2d(C, C, k, stride, padding, groups=C, bias=False)."""
+    return _DwConvSame.apply(x, weight, int(stride), (int(padding),) * 4, False)
 
 
 def depthwise_conv2d_same(x, weight, stride=1, pads=None):

@@ -532,7 +532,10 @@ int cnuda_dwconvt2d_backward(const float* x, const float* w, const float* grad_y
                              void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
 /* Depthwise convolution, weight [C,1,k,k] (k = 3 or 5), no bias -- torchvision MobileNetV2's
  * `nn.Conv2d(hidden, hidden, 3, stride, 1, groups=hidden, bias=False)` inside backends/mobilenetv2.py:31-36's hub
- * trunk.  backward writes grad_x and/or grad_w (either may be NULL); grad_w needs the workspace. */
+ * trunk.  Any stride s >= 1 and padding p >= 0 on every side; the output is (H + 2p - k) / s + 1 rows (floor), likewise
+ * for W.  backward writes grad_x and/or grad_w (either may be NULL); grad_w needs the workspace.  These calls are
+ * cnuda_dwconv2d_same_* below with pad_top = pad_left = p and that output size, on the same kernels with the same
+ * rounding, without that pair's limits on stride and padding. */
 size_t cnuda_dwconv2d_workspace_bytes(int B, int C, int k);
 int cnuda_dwconv2d_forward(const float* x, const float* w, float* y, int B, int C, int H, int W, int k, int s, int p,
                            cnuda_stream_t stream);
@@ -612,14 +615,14 @@ int cnuda_gather_feat(const float* feat, const int64_t* ind, float* out, int B, 
                       cnuda_stream_t stream);
 
 /* ------------------------------------------------------------------------
- * EfficientNet MBConv block (backends/efficientnet.py; csrc/mbconv.hip).  fp32, caller's stream, no float atomics:
- * every reduction has a fixed order and two runs give the same bits.
+ * EfficientNet MBConv block (backends/efficientnet.py; csrc/mbconv.hip, the depthwise convolution csrc/spatial.hip).
+ * fp32, caller's stream, no float atomics: every reduction has a fixed order and two runs give the same bits.
  *
  * Depthwise convolution with TensorFlow "SAME" padding, weight [C,1,k,k] (k = 3 or 5, stride 1 or 2), no bias:
  *   y[b,c,oy,ox] = sum_{r,t} w[c,r,t] * x[b,c, oy*s - pad_top + r, ox*s - pad_left + t], zero outside the map.
  * The bottom / right padding is implied by the output size, (Ho-1)*s + k - pad_top - H (and likewise for W); it must
  * lie in [0, k) like pad_top / pad_left.  backward writes grad_x and/or grad_w (either may be NULL); grad_w needs the
- * workspace (per-image partial sums, added in image order).
+ * workspace (per-image partial sums, added in image order).  The kernels are those of cnuda_dwconv2d_* above.
  * ---------------------------------------------------------------------- */
 size_t cnuda_dwconv2d_same_workspace_bytes(int B, int C, int k);
 int cnuda_dwconv2d_same_forward(const float* x, const float* w, float* y, int B, int C, int H, int W, int k, int s,
@@ -700,14 +703,15 @@ int cnuda_rmsprop_step(float* param, const float* grad, float* square_avg, float
  *   classes [B,M] int32, counts [B] int32 (objects per image, <= M).  Every output is fully overwritten
  *   (zeros where the reference leaves np.zeros): hm [B,C,H,W] f32, reg_mask [B,M] u8, ind [B,M] i64,
  *   wh / reg [B,M,2] f32, gt_dets [B,M,6] f32, gt_areas [B,M] f32 (= w*h: annotations without "area").
+ * cnuda_encode_targets is cnuda_encode_targets_modes below with boxes alone (corners, keypoints, visibility, areas,
+ * kps, gt_kps, kp_reg_mask NULL, J = 0): the same checks, the same kernel; errors carry that call's name.
  * ---------------------------------------------------------------------- */
 int cnuda_encode_targets(const double* boxes, const int* classes, const int* counts,
                          float* hm, unsigned char* reg_mask, long long* ind, float* wh, float* reg,
                          float* gt_dets, float* gt_areas,
                          int B, int C, int H, int W, int M, cnuda_stream_t stream);
-/* The other modes of the dataset's loop (datasets/coco.py:176-184,217-233 keypoints and "area"; 303-376 rotated
- * boxes), one workgroup per (image, slot) like the call above, whose outputs this one reproduces when it is given
- * boxes alone.  Exactly one of boxes / corners is non-NULL.
+/* The encoder with every mode of the dataset's loop (datasets/coco.py:176-184,217-233 keypoints and "area"; 303-376
+ * rotated boxes), one workgroup per (image, slot).  Exactly one of boxes / corners is non-NULL.
  *   corners [B,M,4,2] double: the four corner points in output-map pixels.  Each is clipped to [0,W-1] x [0,H-1] and
  *     rounded to float32; the object becomes the least-area enclosing rectangle with a side along an edge of the
  *     points' convex hull (what the reference asks of cv2.minAreaRect), in double from the float32 points, then

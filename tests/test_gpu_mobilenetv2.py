@@ -17,24 +17,90 @@ T = lambda a: torch.from_numpy(np.ascontiguousarray(a))
 CASES = {'dcn': (dict(use_dcn=True, use_skip=False), 2, 64, 95), 'skip': (dict(use_dcn=False, use_skip=True), 2, 96, 96)}
 
 
-@pytest.mark.parametrize('B,C,H,W,k,s', [(2, 32, 16, 16, 3, 1), (2, 96, 17, 13, 3, 2), (1, 960, 4, 4, 3, 1),
-                                         (3, 5, 9, 7, 3, 2), (2, 8, 12, 12, 5, 1), (1, 16, 2, 2, 3, 2)])
-def test_depthwise_conv2d_matches_torch(B, C, H, W, k, s):
-    from hip_runtime import ops
+def _depthwise_case(B, C, H, W, k, s, p):
+    """-> x, w, gy (CPU float32) and torch's y, grad_x, grad_w for them."""
     rs = np.random.RandomState(C * 7 + H)
     x = T(rs.standard_normal((B, C, H, W)).astype(np.float32))
     w = T((rs.standard_normal((C, 1, k, k)) / k).astype(np.float32))
     xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
-    yr = F.conv2d(xr, wr, None, s, (k - 1) // 2, 1, C)
+    yr = F.conv2d(xr, wr, None, s, p, 1, C)
     gy = T(rs.standard_normal(tuple(yr.shape)).astype(np.float32))
     yr.backward(gy)
+    return x, w, gy, yr.detach(), xr.grad, wr.grad
+
+
+def _depthwise_run(x, w, gy, s, p):
+    from hip_runtime import ops
     xg, wg = x.to(DEV).requires_grad_(True), w.to(DEV).requires_grad_(True)
-    y = ops.depthwise_conv2d(xg, wg, s, (k - 1) // 2)
-    assert y.shape == yr.shape
+    y = ops.depthwise_conv2d(xg, wg, s, p)
     y.backward(gy.to(DEV))
-    _close(y.detach().cpu().numpy(), yr.detach().numpy())
-    _close(xg.grad.cpu().numpy(), xr.grad.numpy())
-    _close(wg.grad.cpu().numpy(), wr.grad.numpy())
+    return y.detach(), xg.grad, wg.grad
+
+
+# the last three: an implied bottom / right padding of -1 (scalar forward, 16-byte input gradient), a stride and a
+# padding that only the plain entry accepts
+@pytest.mark.parametrize('B,C,H,W,k,s,p', [(2, 32, 16, 16, 3, 1, 1), (2, 96, 17, 13, 3, 2, 1), (1, 960, 4, 4, 3, 1, 1),
+                                           (3, 5, 9, 7, 3, 2, 1), (2, 8, 12, 12, 5, 1, 2), (1, 16, 2, 2, 3, 2, 1),
+                                           (2, 5, 8, 12, 3, 2, 0), (1, 4, 9, 10, 3, 3, 1), (1, 4, 5, 5, 3, 1, 3)])
+def test_depthwise_conv2d_matches_torch(B, C, H, W, k, s, p):
+    x, w, gy, yr, gxr, gwr = _depthwise_case(B, C, H, W, k, s, p)
+    y, gx, gw = _depthwise_run(x, w, gy, s, p)
+    assert y.shape == yr.shape
+    _close(y.cpu().numpy(), yr.numpy())
+    _close(gx.cpu().numpy(), gxr.numpy())
+    _close(gw.cpu().numpy(), gwr.numpy())
+
+
+def _depthwise_chain(x, w, gy, s, p):
+    """The kernels' float32 chain restated: acc = 0, then the taps in (r, t) order, every product and every sum rounded
+    to float32 (the library is built without contraction), only taps inside the map added.  -> y, grad_x."""
+    B, C, H, W = x.shape
+    k = w.shape[2]
+    Ho, Wo = gy.shape[2:]
+    y, gx = np.zeros((B, C, Ho, Wo), np.float32), np.zeros((B, C, H, W), np.float32)
+    oy, ox, iy, ix = np.arange(Ho), np.arange(Wo), np.arange(H), np.arange(W)
+    for r in range(k):
+        for t in range(k):
+            wt = w[:, 0, r, t].reshape(1, C, 1, 1)
+            sy, sx = oy * s - p + r, ox * s - p + t                        # the input cell of every output
+            vy, vx = (sy >= 0) & (sy < H), (sx >= 0) & (sx < W)
+            y[:, :, vy[:, None] & vx[None, :]] += (wt * x[:, :, sy[vy]][:, :, :, sx[vx]]).reshape(B, C, -1)
+            ty, tx = iy + p - r, ix + p - t                                # s times the output cell of every input
+            vy, vx = (ty >= 0) & (ty % s == 0) & (ty // s < Ho), (tx >= 0) & (tx % s == 0) & (tx // s < Wo)
+            gx[:, :, vy[:, None] & vx[None, :]] += (wt * gy[:, :, ty[vy] // s][:, :, :, tx[vx] // s]).reshape(B, C, -1)
+    assert y.dtype == np.float32 and gx.dtype == np.float32
+    return y, gx
+
+
+@pytest.mark.parametrize('C,H,W,k,s,p', [(4, 8, 8, 3, 1, 1), (2, 8, 16, 5, 2, 2), (3, 7, 9, 3, 2, 1)])
+def test_depthwise_conv2d_rounds_like_the_plain_chain(C, H, W, k, s, p):
+    """Forward and input gradient bit for bit the (r, t) float32 chain, whichever kernel serves the shape: the 16-byte
+    forward with left padding 1 / with stride 2 and left padding 2 / the scalar kernels.  The weight gradient (an fp64
+    block reduction) against torch as before, and the same bits in two runs."""
+    x, w, gy, _, _, gwr = _depthwise_case(2, C, H, W, k, s, p)
+    y, gx, gw = _depthwise_run(x, w, gy, s, p)
+    want_y, want_gx = _depthwise_chain(x.numpy(), w.numpy(), gy.numpy(), s, p)
+    assert np.array_equal(y.cpu().numpy(), want_y)
+    assert np.array_equal(gx.cpu().numpy(), want_gx)
+    _close(gw.cpu().numpy(), gwr.numpy())
+    assert torch.equal(gw, _depthwise_run(x, w, gy, s, p)[2])
+
+
+def test_depthwise_conv2d_entry_points_called_directly():
+    """cnuda_dwconv2d_forward / _backward through ctypes (symmetric padding, the output size by the floor rule inside)."""
+    import hip_runtime as hr
+    from hip_runtime import ops
+    B, C, H, W, k, s, p = 2, 4, 8, 8, 3, 2, 1
+    x, w, gy = (t.to(DEV) for t in _depthwise_case(B, C, H, W, k, s, p)[:3])
+    want = _depthwise_run(x, w, gy, s, p)
+    L = hr.lib()
+    y, gx, gw = torch.empty_like(gy), torch.empty_like(x), torch.empty_like(w)
+    hr.check(L.cnuda_dwconv2d_forward(hr.ptr(x), hr.ptr(w), hr.ptr(y), B, C, H, W, k, s, p, hr.stream()), 'forward')
+    wp, wn = ops._ws(L.cnuda_dwconv2d_workspace_bytes(B, C, k), x)
+    hr.check(L.cnuda_dwconv2d_backward(hr.ptr(x), hr.ptr(w), hr.ptr(gy), hr.ptr(gx), hr.ptr(gw), B, C, H, W, k, s, p, wp, wn,
+                                       hr.stream()), 'backward')
+    for got, ref in zip((y, gx, gw), want):
+        assert torch.equal(got, ref)
 
 
 @pytest.mark.parametrize('res', [False, True])

@@ -249,8 +249,8 @@ def test_refusals():
 
 
 def test_positional_call_is_unchanged_and_counts_are_clamped():
-    """The plain call still goes through cnuda_encode_targets; boxes-only through the new entry point gives the same
-    bytes; a count above M is clamped."""
+    """The plain call and boxes with keyword arguments are one route: the same single encoder kernel, the same bytes;
+    a count above M is clamped; cnuda_encode_targets called directly gives those bytes too."""
     import hip_runtime as hr
     from datasets import encode_targets
     d = inputs()
@@ -258,12 +258,20 @@ def test_positional_call_is_unchanged_and_counts_are_clamped():
     counts = torch.tensor(COUNTS, dtype=torch.int32, device=DEV)
     with hr.launch_log() as log:
         plain = encode_targets(g('boxes'), g('classes'), counts, C, H, W)
-    assert any('encode_targets_kernel' in n for n in log.names) and not any('modes' in n for n in log.names)
     nan = torch.full((B, M), float('nan'), device=DEV)
-    with hr.launch_log() as log:
+    with hr.launch_log() as log_modes:
         modes = encode_targets(g('boxes'), g('classes'), counts, C, H, W, areas=nan)
         over = encode_targets(g('boxes'), g('classes'), counts + torch.tensor([0, 0, 5], dtype=torch.int32, device=DEV),
                               C, H, W, areas=nan)
-    assert any('encode_targets_modes_kernel' in n for n in log.names)
+    assert len(log.names) == 1 and 'encode_targets_kernel<false>' in log.names[0], log.names
+    assert log_modes.names == log.names and log.counts[log.names[0]] == 1 and log_modes.counts[log.names[0]] == 2
     for k in plain:
         assert torch.equal(plain[k], modes[k]) and torch.equal(plain[k], over[k]), k
+    order = ('hm', 'reg_mask', 'ind', 'wh', 'reg', 'gt_dets', 'gt_areas')
+    assert sorted(plain) == sorted(order)
+    raw = {k: torch.full_like(v, 7) for k, v in plain.items()}                  # every output is fully overwritten
+    boxes, classes = g('boxes'), g('classes')                                  # float64 / int32, contiguous
+    hr.check(hr.lib().cnuda_encode_targets(hr.ptr(boxes), hr.ptr(classes), hr.ptr(counts), *(hr.ptr(raw[k]) for k in order),
+                                           B, C, H, W, M, hr.stream()), 'encode_targets')
+    for k in plain:
+        assert torch.equal(plain[k], raw[k]), k
