@@ -207,12 +207,7 @@ __global__ __launch_bounds__(IG_THREADS, 2) void hconv_kernel(
     }
 
     f32x16 acc[T::TM][T::TN];
-#pragma unroll
-    for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    ig_zero(acc);
 
     f32x4 hreg[HC_MAXCELLS];
     auto halo_load = [&](int g) {

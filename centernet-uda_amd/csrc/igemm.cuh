@@ -51,6 +51,35 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // row m of D tile element `reg` for this lane
 __device__ __forceinline__ int mfma_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 
+// a wave's accumulator tiles: cleared; a running set added into a total with rounded adds and cleared; a total added back
+template <int R, int C>
+__device__ __forceinline__ void ig_zero(f32x16 (&acc)[R][C]) {
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+        for (int j = 0; j < C; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+}
+template <int R, int C>
+__device__ __forceinline__ void ig_fold(f32x16 (&total)[R][C], f32x16 (&acc)[R][C]) {
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+        for (int j = 0; j < C; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { total[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.0f; }
+}
+template <int R, int C>
+__device__ __forceinline__ void ig_add(f32x16 (&acc)[R][C], const f32x16 (&total)[R][C]) {
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+        for (int j = 0; j < C; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] += total[i][j][r];
+}
+
 // One K chunk of MFMAs.  The operand fragments of k-step s+1 are read from LDS BEFORE the MFMAs of step s are
 // issued (explicit two-deep register pipeline): left to itself the compiler emits read -> s_waitcnt lgkmcnt(0) ->
 // MFMA per step, and the ~100-cycle LDS round trip then idles the matrix pipe between steps (measured with
@@ -389,17 +418,15 @@ __device__ __forceinline__ void ig_epilogue_quads(const typename Loader::Params&
     }
 }
 
-// raw-load storage of two-phase loaders (Loader::kHasSideOutput): Loader::Raw, else an empty placeholder
-template <class Loader, bool TWO_PHASE> struct IgRaw { struct type {}; };
-template <class Loader> struct IgRaw<Loader, true> { using type = typename Loader::Raw; };
-
-// Generic forward-type kernel.  Loader contract:
-//   Loader(const Params&, long long n, bool n_valid)   per-thread pixel setup
-//   void load(int k0, int ksub, float (&v)[8])         v[j] = B[k0 + ksub + 2j][n]
-//   or, when Loader::kHasSideOutput: load_raw(k0, ksub, Raw&) issues the loads of a chunk and finish(Raw&, v) turns
-//   them into values one chunk later, when the kernel stores that chunk to LDS
-// Epilogue contract:
-//   void store(const Params&, int m, long long n, float value)
+// The forward-type kernels' ways out for an accumulator tile.  Epilogue contract (Loader::Out):
+//   Out(const Params&, long long n)                                  per-lane pixel setup
+//   void store(const Params&, int m, float value)                    one element of row m at that pixel
+//   kVec4 / vec4_ok(p) / store4, kQuads / store_quad                 the 16-byte forms above
+// Every forward-type kernel ends in the same chain: row quads where the output has them (ig_epilogue_quads); else, when
+// Out::kVec4 and vec4_ok(p) (uniform), 16-byte stores through LDS that holds no operand any more (ig_epilogue_vec4); else
+// one dword per lane and register, the lane owning pixel column (lane & 31) of each tile.  The chain stands in
+// igemm_fwd_body, igemm_fwd_ws_body and ig_shortk_tile: as one helper around the three ways it cost a handful of
+// instances a wave per SIMD (profiles/igemm_dedupe_ab.txt, section 2b).
 // Split-K epilogue (round 6): the accumulator tile as it stands -- no bias, no activation -- into split z's slab
 // [Mp][Np] (Np = n_tiles * 128: every tile whole, no bounds tests); splitk_reduce_kernel adds the slabs in order and runs
 // the loader's own epilogue (Out::store) on the sums.
@@ -417,6 +444,66 @@ __device__ __forceinline__ void ig_store_slab(float* __restrict__ slab, const f3
             for (int r = 0; r < 16; ++r) d[(size_t)(m0 + wm_off + i * 32 + mfma_row(r, lane)) * Np + n] = acc[i][j][r];
     }
 }
+
+// raw-load storage of two-phase loaders (Loader::kHasSideOutput): Loader::Raw, else an empty placeholder
+template <class Loader, bool TWO_PHASE> struct IgRaw { struct type {}; };
+template <class Loader> struct IgRaw<Loader, true> { using type = typename Loader::Raw; };
+
+// The register stage of a forward-type kernel's staging thread (pixel nl of the tile, k parity ksub): load(k0) issues
+// the global loads of the chunk at k0 -- the A cells and NH loader calls -- and store(As, Bs) writes that chunk into one
+// LDS stage a chunk later.  Loader contract:
+//   Loader(const Params&, long long n, bool n_valid)   per-thread pixel setup
+//   void load(int k0, int ksub, float (&v)[8])         v[j] = B[k0 + ksub + 2j][n]
+//   or, when Loader::kHasSideOutput: load_raw(k0, ksub, Raw&) issues the loads of a chunk and finish(Raw&, v) turns
+//   them into values one chunk later, when the kernel stores that chunk to LDS
+// Kp is a multiple of KC (the pack kernels zero-pad); the loaders return 0 past the real K.
+// (The Loader stays the kernel's own object and is borrowed: as a member, the two-phase DCN loader's 64-row instance
+// took six more registers and lost a wave per SIMD.)
+template <int BM, class Loader, int KC, bool X3>
+struct IgFwdStager {
+    static constexpr int NH = KC / IG_BK;           // loader calls per chunk
+    const int tid, nl, ksub;
+    Loader& ld;
+    const IgABuf<BM, KC> abuf;                      // (unused by the X3 variant, whose A cells are pre-split)
+    const float* const A;
+    const int Mp, m0;
+    f32x4 ra[ig_a_per<BM, KC>()];
+    float rb[NH][8];
+    u32x4 ra3[ig_a3_per<BM>()];                     // X3: the pre-split A cells of a chunk
+    typename IgRaw<Loader, Loader::kHasSideOutput>::type raw[NH];   // two-phase loaders keep raw loads here
+    __device__ __forceinline__ IgFwdStager(Loader& ld_, const float* A_, int Mp_, int Kp, int m0_, int tid_)
+        : tid(tid_), nl(tid_ & (IG_BN - 1)), ksub(tid_ >> 7), ld(ld_), abuf(A_, Mp_, Kp, m0_, tid_), A(A_), Mp(Mp_), m0(m0_) {}
+    __device__ __forceinline__ void load(int k0) {
+        if constexpr (X3) ig_load_a_x3<BM>(reinterpret_cast<const u32x4*>(A), Mp, k0, m0, tid, ra3);
+        else abuf.load(k0, ra);
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            if constexpr (Loader::kHasSideOutput) ld.load_raw(k0 + h * IG_BK, ksub, raw[h]);
+            else ld.load(k0 + h * IG_BK, ksub, rb[h]);
+        }
+    }
+    __device__ __forceinline__ void store(float* As, float* Bs) {
+        if constexpr (X3) ig_store_a_x3<BM>(reinterpret_cast<u32x4*>(As), tid, ra3);
+        else ig_store_a<BM, KC>(As, tid, ra);
+        if constexpr (Loader::kHasSideOutput) {
+#pragma unroll
+            for (int h = 0; h < NH; ++h) ld.finish(raw[h], rb[h]);
+        }
+        if constexpr (X3) {
+            static_assert(NH == 1, "X3 stages one 16-deep MFMA step per chunk");
+            unsigned o[3][4];
+            x3_split<8>(rb[0], o);
+#pragma unroll
+            for (int pc = 0; pc < 3; ++pc)
+                reinterpret_cast<u32x4*>(Bs)[(pc * 2 + ksub) * IG_BN + nl] = u32x4{o[pc][0], o[pc][1], o[pc][2], o[pc][3]};
+        } else {
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) Bs[(h * IG_BK + ksub + 2 * j) * IG_BN + nl] = rb[h][j];
+        }
+    }
+};
 
 template <int BM, class Loader, bool X3 = false, bool SPLITK = false>
 __device__ __forceinline__ void igemm_fwd_body(
@@ -438,55 +525,12 @@ __device__ __forceinline__ void igemm_fwd_body(
     const long long n0 = (long long)(wg / m_tiles) * IG_BN;
     const int wm_off = (wid / T::WN) * (T::TM * 32), wn_off = (wid % T::WN) * (T::TN * 32);
 
-    const int nl = tid & (IG_BN - 1), ksub = tid >> 7;  // pixel within tile, k parity
+    const int nl = tid & (IG_BN - 1);
     Loader ld(p, n0 + nl, n0 + nl < N);
     if constexpr (Loader::kHasSideOutput) { if (m0 != 0) ld.disable_col(); }
-
+    IgFwdStager<BM, Loader, IG_KC, X3> stg(ld, A, Mp, Kp, m0, tid);
     f32x16 acc[T::TM][T::TN];
-#pragma unroll
-    for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-    // Kp is a multiple of IG_KC (the pack kernels zero-pad); the loaders return 0 past the real K
-    constexpr int NH = IG_KC / IG_BK;               // loader calls per chunk
-    f32x4 ra[ig_a_per<BM>()];
-    float rb[NH][8];
-    u32x4 ra3[ig_a3_per<BM>()];                     // X3: the pre-split A cells of a chunk
-    typename IgRaw<Loader, Loader::kHasSideOutput>::type raw[NH];   // two-phase loaders keep raw loads here
-    const IgABuf<BM> abuf(A, Mp, Kp, m0, tid);      // (unused by the X3 variant, whose A cells are pre-split)
-    auto stage_store = [&](int buf) {
-        if constexpr (X3) ig_store_a_x3<BM>(reinterpret_cast<u32x4*>(As[buf]), tid, ra3);
-        else ig_store_a<BM>(As[buf], tid, ra);
-        if constexpr (Loader::kHasSideOutput) {
-#pragma unroll
-            for (int h = 0; h < NH; ++h) ld.finish(raw[h], rb[h]);
-        }
-        if constexpr (X3) {
-            static_assert(NH == 1, "X3 stages one 16-deep MFMA step per chunk");
-            unsigned o[3][4];
-            x3_split<8>(rb[0], o);
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc)
-                reinterpret_cast<u32x4*>(Bs[buf])[(pc * 2 + ksub) * IG_BN + nl] = u32x4{o[pc][0], o[pc][1], o[pc][2], o[pc][3]};
-        } else {
-#pragma unroll
-            for (int h = 0; h < NH; ++h)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) Bs[buf][(h * IG_BK + ksub + 2 * j) * IG_BN + nl] = rb[h][j];
-        }
-    };
-    auto stage_load = [&](int k0) {
-        if constexpr (X3) ig_load_a_x3<BM>(reinterpret_cast<const u32x4*>(A), Mp, k0, m0, tid, ra3);
-        else abuf.load(k0, ra);
-#pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            if constexpr (Loader::kHasSideOutput) ld.load_raw(k0 + h * IG_BK, ksub, raw[h]);
-            else ld.load(k0 + h * IG_BK, ksub, rb[h]);
-        }
-    };
+    ig_zero(acc);
     if constexpr (X3) {
         // Fully pipelined: per iteration k a wave (1) issues the LDS reads of chunk k+1's fragments into the spare
         // register set, (2) runs the MFMAs of chunk k from the set read one iteration ago, (3) splits and stores
@@ -502,24 +546,24 @@ __device__ __forceinline__ void igemm_fwd_body(
                                 wm_off, wn_off, lane);
         };
         u32x4 fa0[T::TM][3], fb0[T::TN][3], fa1[T::TM][3], fb1[T::TN][3];
-        stage_load(0);
-        stage_store(0);
-        stage_load(kclamp(1));
+        stg.load(0);
+        stg.store(As[0], Bs[0]);
+        stg.load(kclamp(1));
         __syncthreads();
         frag_read(0, fa0, fb0);
-        stage_store(1);
-        stage_load(kclamp(2));
+        stg.store(As[1], Bs[1]);
+        stg.load(kclamp(2));
         __syncthreads();
         auto step = [&](int c, u32x4 (&ca)[T::TM][3], u32x4 (&cb)[T::TN][3], u32x4 (&na)[T::TM][3], u32x4 (&nb)[T::TN][3]) {
             frag_read((c + 1) & 1, na, nb);
             ig_mma_frag_x3<BM>(ca, cb, acc);
-            stage_store(c & 1);
+            stg.store(As[c & 1], Bs[c & 1]);
 #pragma unroll
             for (int i = 0; i < 6 * T::TM * T::TN; ++i) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                      // one MFMA
                 __builtin_amdgcn_sched_group_barrier(0x002, BM == 128 ? 3 : (BM == 64 ? 5 : 6), 0);   // VALU beside it
             }
-            stage_load(kclamp(c + 3));
+            stg.load(kclamp(c + 3));
             __syncthreads();
         };
         // The bf16 MFMA's accumulate does not round to nearest: every step loses a little toward zero (measured
@@ -528,47 +572,29 @@ __device__ __forceinline__ void igemm_fwd_body(
         // the bias then scales with the partial sum's size and stays below one ulp of the result.
         constexpr int X3_FOLD = 8;
         f32x16 total[T::TM][T::TN];
-#pragma unroll
-        for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-            for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) total[i][j][r] = 0.0f;
-        auto fold = [&]() {
-#pragma unroll
-            for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-                for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { total[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.0f; }
-        };
+        ig_zero(total);
         int c = 0;
         for (; c + 1 < nchunk; c += 2) {
             step(c, fa0, fb0, fa1, fb1);
             step(c + 1, fa1, fb1, fa0, fb0);
-            if (((c + 2) & (X3_FOLD - 1)) == 0) fold();
+            if (((c + 2) & (X3_FOLD - 1)) == 0) ig_fold(total, acc);
         }
         if (c < nchunk) ig_mma_frag_x3<BM>(fa0, fb0, acc);
-#pragma unroll
-        for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-            for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] += total[i][j][r];
+        ig_add(acc, total);
     } else {
     // (SPLITK: blockIdx.y takes the K range [kb, ke), split_k elements each)
     const int kb = SPLITK ? (int)blockIdx.y * split_k : 0;
     const int ke = SPLITK ? (kb + split_k < Kp ? kb + split_k : Kp) : Kp;
-    stage_load(kb);
-    stage_store(0);
-    if (kb + IG_KC < ke) stage_load(kb + IG_KC);
+    stg.load(kb);
+    stg.store(As[0], Bs[0]);
+    if (kb + IG_KC < ke) stg.load(kb + IG_KC);
     __syncthreads();
     int cur = 0;
     for (int k0 = kb; k0 < ke; k0 += IG_KC) {
         ig_mma_chunk<BM>(As[cur], Bs[cur], acc, wm_off, wn_off, lane);
         if (k0 + IG_KC < ke) {
-            stage_store(cur ^ 1);                      // chunk k+1 (its global loads were issued one chunk ago)
-            if (k0 + 2 * IG_KC < ke) stage_load(k0 + 2 * IG_KC);
+            stg.store(As[cur ^ 1], Bs[cur ^ 1]);                      // chunk k+1 (its global loads were issued one chunk ago)
+            if (k0 + 2 * IG_KC < ke) stg.load(k0 + 2 * IG_KC);
         }
         __syncthreads();
         cur ^= 1;
@@ -665,47 +691,22 @@ __device__ __forceinline__ void igemm_fwd_ws_body(
     const int m0 = (wg % m_tiles) * BM;
     const long long n0 = (long long)(wg / m_tiles) * IG_BN;
     if (producer) {
-        const int nl = tid & (IG_BN - 1), ksub = tid >> 7;
-        Loader ld(p, n0 + nl, n0 + nl < N);
-        if constexpr (Loader::kHasSideOutput) { if (m0 != 0) ld.disable_col(); }
         // ONE register stage: the loads of chunk k + 2 are issued right after chunk k + 1 went to LDS.  (A second
         // stage -- loads issued two chunks ahead -- measured 0.4 ms per step slower once buffer addressing made the
         // loads cheap: it costs the third workgroup per CU, 86 instead of <= 80 registers.  DESIGN.md section 10.)
         static_assert(!Loader::kHasSideOutput, "two-phase loaders keep per-chunk state (the current tap's weights)");
-        constexpr int NH = KC / IG_BK;                 // loader calls per chunk
-        struct Regs {
-            f32x4 ra[ig_a_per<BM, KC>()];
-            float rb[NH][8];
-            typename IgRaw<Loader, Loader::kHasSideOutput>::type raw[NH];
-        };
-        Regs r0;
-        const IgABuf<BM, KC> abuf(A, Mp, Kp, m0, tid);
-        auto stage_store = [&](int buf, Regs& r) {
-            ig_store_a<BM, KC>(As[buf], tid, r.ra);
-#pragma unroll
-            for (int h = 0; h < NH; ++h) {
-                if constexpr (Loader::kHasSideOutput) ld.finish(r.raw[h], r.rb[h]);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) Bs[buf][(h * IG_BK + ksub + 2 * j) * IG_BN + nl] = r.rb[h][j];
-            }
-        };
-        auto stage_load = [&](int k0, Regs& r) {
-            abuf.load(k0, r.ra);
-#pragma unroll
-            for (int h = 0; h < NH; ++h) {
-                if constexpr (Loader::kHasSideOutput) ld.load_raw(k0 + h * IG_BK, ksub, r.raw[h]);
-                else ld.load(k0 + h * IG_BK, ksub, r.rb[h]);
-            }
-        };
-        stage_load(kb, r0);
-        stage_store(0, r0);
-        if (kb + KC < ke) stage_load(kb + KC, r0);
+        const int nl = tid & (IG_BN - 1);
+        Loader ld(p, n0 + nl, n0 + nl < N);
+        IgFwdStager<BM, Loader, KC, false> stg(ld, A, Mp, Kp, m0, tid);
+        stg.load(kb);
+        stg.store(As[0], Bs[0]);
+        if (kb + KC < ke) stg.load(kb + KC);
         __syncthreads();
         int c1 = 0;
         for (int k0 = kb; k0 < ke; k0 += KC) {
             if (k0 + KC < ke) {
-                stage_store(c1 ^ 1, r0);
-                if (k0 + 2 * KC < ke) stage_load(k0 + 2 * KC, r0);
+                stg.store(As[c1 ^ 1], Bs[c1 ^ 1]);
+                if (k0 + 2 * KC < ke) stg.load(k0 + 2 * KC);
             }
             __syncthreads();
             c1 ^= 1;
@@ -714,12 +715,7 @@ __device__ __forceinline__ void igemm_fwd_ws_body(
     }
     const int wm_off = (wid / T::WN) * (T::TM * 32), wn_off = (wid % T::WN) * (T::TN * 32);
     f32x16 acc[T::TM][T::TN];
-#pragma unroll
-    for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    ig_zero(acc);
     __syncthreads();
     int cur = 0;
 #ifdef IG_FOLD
@@ -727,37 +723,19 @@ __device__ __forceinline__ void igemm_fwd_ws_body(
     // cut every n chunks -- the running tile is added into a second accumulator set with rounded adds and cleared -- which
     // makes the sum blocked like the CPU reference's (oneDNN), at the price of TM x TN x 16 more registers per consumer wave.
     f32x16 tot[T::TM][T::TN];
-#pragma unroll
-    for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.0f;
+    ig_zero(tot);
     int since = 0;
 #endif
     for (int k0 = kb; k0 < ke; k0 += KC) {
         ig_mma_chunk<BM, KC>(As[cur], Bs[cur], acc, wm_off, wn_off, lane);
 #ifdef IG_FOLD
-        if (++since == IG_FOLD) {
-            since = 0;
-#pragma unroll
-            for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-                for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.0f; }
-        }
+        if (++since == IG_FOLD) { since = 0; ig_fold(tot, acc); }
 #endif
         __syncthreads();
         cur ^= 1;
     }
 #ifdef IG_FOLD
-#pragma unroll
-    for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] += tot[i][j][r];
+    ig_add(acc, tot);
 #endif
     if constexpr (SPLITK) {
         ig_store_slab<BM>(slab, acc, Mp, (long long)n_tiles * IG_BN, m0, n0, wm_off, wn_off, lane);
@@ -801,6 +779,45 @@ __global__ __launch_bounds__(2 * IG_THREADS, (BM == 128 ? 2 : 1)) void igemm_fwd
     igemm_fwd_ws_body<BM, Loader, KC, true>(p, A, Mp, Kp, M, N, n_tiles, m_tiles, slab, split_k);
 }
 
+// One row tile of the short-K kernel below, BMT rows of the A image staged in LDS with row stride LDA (BMT < LDA: the
+// narrower last tile): its KP / 2 k-steps without a barrier in between, then the epilogue, which stages through As.
+template <int BMT, int LDA, class Loader, int KP>
+__device__ __forceinline__ void ig_shortk_tile(const typename Loader::Params& p, float* __restrict__ As,
+                                               const float* __restrict__ Bs, int m0, long long n0, int lane, int wid, int M,
+                                               long long N) {
+    using T = IgTile<BMT>;
+    const int wm_off = (wid / T::WN) * (T::TM * 32), wn_off = (wid % T::WN) * (T::TN * 32);
+    f32x16 acc[T::TM][T::TN];
+    ig_zero(acc);
+#pragma unroll
+    for (int c = 0; c < KP / IG_KC; ++c)
+        ig_mma_chunk<BMT, IG_KC, LDA>(As + c * IG_KC * LDA, Bs + c * IG_KC * IG_BN, acc, wm_off, wn_off, lane);
+    if constexpr (IgHasQuads<typename Loader::Out>::value) {
+        ig_epilogue_quads<BMT, Loader>(p, acc, m0, n0, wm_off, wn_off, lane, M, N);     // (no staging: As is not touched)
+        return;
+    }
+    __syncthreads();                 // every wave has read its last fragments: As becomes the staging area
+    if constexpr (Loader::Out::kVec4) {
+        if (Loader::Out::vec4_ok(p)) {
+            ig_epilogue_vec4<BMT, Loader>(p, As + wid * IG_EPI_WAVE, acc, m0, n0, wm_off, wn_off, lane, M, N);
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < T::TN; ++j) {
+        const long long n = n0 + wn_off + j * 32 + (lane & 31);
+        if (n >= N) continue;
+        typename Loader::Out out(p, n);
+#pragma unroll
+        for (int i = 0; i < T::TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + wm_off + i * 32 + mfma_row(r, lane);
+                if (m < M) out.store(p, m, acc[i][j][r]);
+            }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Short-K variant (Kp <= KP = 64: the DCN column-gradient GEMM, a 1x1 convolution with K = 64 and 9*C = 576 output
 // rows).  With four chunks per tile the pipelined kernels spend as long in prologue and epilogue as in the K loop
@@ -811,13 +828,11 @@ __global__ __launch_bounds__(2 * IG_THREADS, (BM == 128 ? 2 : 1)) void igemm_fwd
 template <int BM, class Loader, int KP>
 __global__ __launch_bounds__(IG_THREADS, 2) void igemm_fwd_shortk_kernel(
     typename Loader::Params p, const float* __restrict__ A, int Mp, int Kp, int M, long long N, int n_tiles, int m_tiles) {
-    using T = IgTile<BM>;
     static_assert(KP % IG_KC == 0 && KP * BM >= 4 * IG_EPI_WAVE, "the A buffer holds the epilogue staging tiles");
     __shared__ __attribute__((aligned(16))) float As[KP * BM];      // reused by the vec4 epilogue
     __shared__ __attribute__((aligned(16))) float Bs[KP * IG_BN];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const long long n0 = (long long)xcd_remap(blockIdx.x, n_tiles) * IG_BN;
-    const int wm_off = (wid / T::WN) * (T::TM * 32), wn_off = (wid % T::WN) * (T::TN * 32);
     {   // B tile: every chunk gathered once
         const int nl = tid & (IG_BN - 1), ksub = tid >> 7;
         Loader ld(p, n0 + nl, n0 + nl < N);
@@ -852,80 +867,16 @@ __global__ __launch_bounds__(IG_THREADS, 2) void igemm_fwd_shortk_kernel(
         // the next row tile's A loads go out BEFORE this tile's stores: vmcnt counts in issue order, so a load issued
         // after the epilogue would wait for every one of its stores to drain
         if (mt + 1 < m_tiles) load_a(mt + 1);
+        // The LAST row tile when at most 64 of its rows exist (M = 9 * 64 = 576 = 4.5 tiles for the 64-channel DCN layers):
+        // computed as a 64 x 128 tile over the four waves -- half the MFMAs of a 128-row tile whose upper half would be
+        // all padding (round 6: a tenth of this kernel's matrix work)
         if constexpr (BM == 128) {
-            // The LAST row tile when at most 64 of its rows exist (M = 9 * 64 = 576 = 4.5 tiles for the 64-channel DCN layers):
-            // computed as a 64 x 128 tile over the four waves -- half the MFMAs of a 128-row tile whose upper half would be
-            // all padding (round 6: a tenth of this kernel's matrix work)
             if (M - m0 <= 64) {
-                using T2 = IgTile<64>;
-                const int wm2 = (wid / T2::WN) * (T2::TM * 32), wn2 = (wid % T2::WN) * (T2::TN * 32);
-                f32x16 acc2[T2::TM][T2::TN];
-#pragma unroll
-                for (int i = 0; i < T2::TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < T2::TN; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc2[i][j][r] = 0.0f;
-#pragma unroll
-                for (int c = 0; c < KP / IG_KC; ++c)
-                    ig_mma_chunk<64, IG_KC, BM>(As + c * IG_KC * BM, Bs + c * IG_KC * IG_BN, acc2, wm2, wn2, lane);
-                if constexpr (IgHasQuads<typename Loader::Out>::value) {
-                    ig_epilogue_quads<64, Loader>(p, acc2, m0, n0, wm2, wn2, lane, M, N);     // (no staging: As is not touched)
-                } else {
-                __syncthreads();
-                if (Loader::Out::vec4_ok(p)) {
-                    ig_epilogue_vec4<64, Loader>(p, As + wid * IG_EPI_WAVE, acc2, m0, n0, wm2, wn2, lane, M, N);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < T2::TN; ++j) {
-                        const long long n = n0 + wn2 + j * 32 + (lane & 31);
-                        if (n >= N) continue;
-                        typename Loader::Out out(p, n);
-#pragma unroll
-                        for (int i = 0; i < T2::TM; ++i)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                const int m = m0 + wm2 + i * 32 + mfma_row(r, lane);
-                                if (m < M) out.store(p, m, acc2[i][j][r]);
-                            }
-                    }
-                }
-                }
+                ig_shortk_tile<64, BM, Loader, KP>(p, As, Bs, m0, n0, lane, wid, M, N);
                 continue;
             }
         }
-        f32x16 acc[T::TM][T::TN];
-#pragma unroll
-        for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-            for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-#pragma unroll
-        for (int c = 0; c < KP / IG_KC; ++c)
-            ig_mma_chunk<BM>(As + c * IG_KC * BM, Bs + c * IG_KC * IG_BN, acc, wm_off, wn_off, lane);
-        if constexpr (IgHasQuads<typename Loader::Out>::value) {
-            ig_epilogue_quads<BM, Loader>(p, acc, m0, n0, wm_off, wn_off, lane, M, N);      // (no staging: As is not touched)
-        } else {
-        __syncthreads();                 // every wave has read its last fragments: As becomes the staging area
-        if (Loader::Out::vec4_ok(p)) {
-            ig_epilogue_vec4<BM, Loader>(p, As + wid * IG_EPI_WAVE, acc, m0, n0, wm_off, wn_off, lane, M, N);
-        } else {
-#pragma unroll
-            for (int j = 0; j < T::TN; ++j) {
-                const long long n = n0 + wn_off + j * 32 + (lane & 31);
-                if (n >= N) continue;
-                typename Loader::Out out(p, n);
-#pragma unroll
-                for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int m = m0 + wm_off + i * 32 + mfma_row(r, lane);
-                        if (m < M) out.store(p, m, acc[i][j][r]);
-                    }
-            }
-        }
-        }
+        ig_shortk_tile<BM, BM, Loader, KP>(p, As, Bs, m0, n0, lane, wid, M, N);
     }
 }
 
@@ -1008,119 +959,152 @@ __device__ __forceinline__ void ig_wgrad_store_bias(float (&bs)[NG], float* __re
     }
 }
 
-// BM x BJ = 64 x 128 (waves 2 x 2, two accumulator tiles each: when the column count is a multiple of 128),
-// 64 x 64 (waves 2 x 2) or 32 x 128 (waves 1 x 4, for layers with <= 32 output channels:
-// the 16-channel stem / level-0 convs and the 27-channel DCN offset convs would waste 2-4x on a 64-row tile)
-template <class WLoader, int BM, int BJ>
-__global__ __launch_bounds__(IG_THREADS) void igemm_wgrad_kernel(
-    typename WLoader::Params p, float* __restrict__ slabs, int Mp, int Jp, long long N, long long pix_per_split,
-    float* __restrict__ bslab) {
-    constexpr int GLD = BM + 1, BLD = BJ + 1;          // odd row strides: conflict-free pixel-major stores
-    constexpr int STEP = IG_THREADS / WG_BP;            // rows (channels / columns) covered per pass
+// Tile constants of the weight-gradient kernels.  BM x BJ = 64 x 128 (waves 2 x 2, two accumulator tiles each: when the
+// column count is a multiple of 128), 64 x 64 (waves 2 x 2) or 32 x 128 (waves 1 x 4, for layers with <= 32 output
+// channels: the 16-channel stem / level-0 convs and the 27-channel DCN offset convs would waste 2-4x on a 64-row tile)
+template <int BM, int BJ>
+struct IgWgradTile {
+    static constexpr int GLD = BM + 1, BLD = BJ + 1;          // odd row strides: conflict-free pixel-major stores
+    static constexpr int STEP = IG_THREADS / WG_BP;            // rows (channels / columns) covered per pass
     // 32x32 accumulator tiles per wave: TM x TJ (2 x 2 for the 128 x 128 tile: 4 fragment dwords per 4 MFMAs; else one
     // row of tiles side by side along j)
-    constexpr int TM = (BM == 128 && BJ == 128) ? 2 : 1, TJ = (BM / 32) * (BJ / 32) / 4 / TM;
-    constexpr int WJ = BJ / 32 / TJ, NG = BM / STEP, NB = BJ / STEP;
+    static constexpr int TM = (BM == 128 && BJ == 128) ? 2 : 1, TJ = (BM / 32) * (BJ / 32) / 4 / TM;
+    static constexpr int WJ = BJ / 32 / TJ, NG = BM / STEP, NB = BJ / STEP;
     static_assert((BM / 32 / TM) * WJ == 4, "four waves tile the block");
-    // two LDS stages, one barrier per pixel chunk (32 pixels): chunk k+1 is stored while chunk k is consumed
-    __shared__ float Gs[2][WG_BP * GLD];
-    __shared__ float Bs[2][WG_BP * BLD];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int j0 = blockIdx.x * BJ, m0 = blockIdx.y * BM;
-    const long long n_begin = (long long)blockIdx.z * pix_per_split;
-    long long n_end = n_begin + pix_per_split;
-    if (n_end > N) n_end = N;
-    const int pl = tid % WG_BP, sub = tid / WG_BP;  // pixel within chunk, row phase (0..STEP-1)
-    const int wm_off = (wid / WJ) * 32 * TM, wj_off = (wid % WJ) * 32 * TJ;
-    WLoader ld(p, n_begin + pl, n_end);
-    f32x16 acc[TM][TJ];
+};
+
+// The register stage of a weight-gradient staging thread (pixel pl of the chunk, row phase sub = 0..STEP-1): load()
+// reads the cursor's pixel of the G and B rows it owns, store(Gs, Bs) writes them into one LDS stage.
+// Bias gradient (do_bias: bslab != nullptr, first column tile): the row sums of G over this split's pixels, taken from
+// the values staged anyway -- the G tile passes through these registers once per chunk, so the separate pass over grad_y
+// (channel_sum_*: 38 launch pairs and 0.7 ms per benched step) is not needed.  Fixed order: a thread's chunks in
+// sequence, then a butterfly over its 32 pixel lanes; the splits are summed by slab_reduce_*.
+template <class WLoader, int BM, int BJ>
+struct IgWgradStager {
+    using W = IgWgradTile<BM, BJ>;
+    const int pl, sub, m0, j0;
+    WLoader ld;
+    const bool do_bias;
+    float rg[W::NG], rb[W::NB], bs[W::NG];
+    __device__ __forceinline__ IgWgradStager(const typename WLoader::Params& p, long long n_begin, long long n_end, int m0_,
+                                             int j0_, int tid, bool do_bias_)
+        : pl(tid % WG_BP), sub(tid / WG_BP), m0(m0_), j0(j0_), ld(p, n_begin + pl, n_end), do_bias(do_bias_) {
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < W::NG; ++i) bs[i] = 0.0f;
+    }
+    __device__ __forceinline__ void load() {
+        ld.template load_g<W::NG, W::STEP>(m0, sub, rg);
+        ld.template load_b<W::NB, W::STEP>(j0, sub, rb);
+    }
+    __device__ __forceinline__ void advance_load() { ld.advance(); load(); }
+    __device__ __forceinline__ void store(float* Gs, float* Bs) {
 #pragma unroll
-        for (int t = 0; t < TJ; ++t)
+        for (int i = 0; i < W::NG; ++i) Gs[pl * W::GLD + sub + W::STEP * i] = rg[i];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][t][r] = 0.0f;
-    float rg[NG], rb[NB];
-    // bias gradient (bslab != nullptr): the row sums of G over this split's pixels, taken by the workgroups of the first
-    // column tile from the values they stage anyway -- the G tile passes through these registers once per chunk, so the
-    // separate pass over grad_y (channel_sum_*: 38 launch pairs and 0.7 ms per benched step) is not needed.  Fixed order:
-    // a thread's chunks in sequence, then a butterfly over its 32 pixel lanes; the splits are summed by slab_reduce_*.
-    const bool do_bias = bslab != nullptr && blockIdx.x == 0;
-    float bs[NG];
-#pragma unroll
-    for (int i = 0; i < NG; ++i) bs[i] = 0.0f;
-    auto stage_store = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NG; ++i) Gs[buf][pl * GLD + sub + STEP * i] = rg[i];
-#pragma unroll
-        for (int i = 0; i < NB; ++i) Bs[buf][pl * BLD + sub + STEP * i] = rb[i];
+        for (int i = 0; i < W::NB; ++i) Bs[pl * W::BLD + sub + W::STEP * i] = rb[i];
         if (do_bias) {
 #pragma unroll
-            for (int i = 0; i < NG; ++i) bs[i] += rg[i];
+            for (int i = 0; i < W::NG; ++i) bs[i] += rg[i];
         }
-    };
-    auto stage_load = [&]() {
-        ld.template load_g<NG, STEP>(m0, sub, rg);
-        ld.template load_b<NB, STEP>(j0, sub, rb);
-    };
-    stage_load();
-    stage_store(0);
-    if (n_begin + WG_BP < n_end) { ld.advance(); stage_load(); }
-    __syncthreads();
-    int cur = 0;
-    const int kl = lane >> 5, il = lane & 31;
-    for (long long nb = n_begin; nb < n_end; nb += WG_BP) {
-        {   // fragments of the next two k-steps are in flight while this pair's MFMAs run (see ig_mma_chunk)
-            const float* gp = Gs[cur] + kl * GLD + wm_off + il;
-            const float* bp = Bs[cur] + kl * BLD + wj_off + il;
-            float a[2][2][TM], b[2][2][TJ];
-            auto frag = [&](int kk, float (&fa)[2][TM], float (&fb)[2][TJ]) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) { fa[0][i] = gp[kk * GLD + i * 32]; fa[1][i] = gp[(kk + 2) * GLD + i * 32]; }
-#pragma unroll
-                for (int t = 0; t < TJ; ++t) { fb[0][t] = bp[kk * BLD + t * 32]; fb[1][t] = bp[(kk + 2) * BLD + t * 32]; }
-            };
-            auto mma = [&](const float (&fa)[2][TM], const float (&fb)[2][TJ]) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int t = 0; t < TJ; ++t)
-                            acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[h][i], fb[h][t], acc[i][t], 0, 0, 0);
-            };
-            frag(0, a[0], b[0]);
-#pragma unroll
-            for (int kk = 0; kk < WG_BP; kk += 8) {
-                frag(kk + 4, a[1], b[1]);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(a[0], b[0]);
-                __builtin_amdgcn_sched_barrier(0);
-                if (kk + 8 < WG_BP) frag(kk + 8, a[0], b[0]);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(a[1], b[1]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if (nb + WG_BP < n_end) {
-            stage_store(cur ^ 1);
-            if (nb + 2 * WG_BP < n_end) { ld.advance(); stage_load(); }
-        }
-        __syncthreads();
-        cur ^= 1;
     }
+    __device__ __forceinline__ void store_bias(float* __restrict__ bslab, int Mp) {       // rows m0.. of this split's sums
+        if (do_bias) ig_wgrad_store_bias<W::NG, W::STEP>(bs, bslab + (size_t)blockIdx.z * Mp + m0, pl, sub);
+    }
+};
+
+// One 32-pixel chunk of MFMAs from an LDS stage: the fragments of the next two k-steps are in flight while this pair's
+// MFMAs run (see ig_mma_chunk)
+template <int BM, int BJ>
+__device__ __forceinline__ void ig_wgrad_mma_chunk(const float* Gs, const float* Bs,
+                                                   f32x16 (&acc)[IgWgradTile<BM, BJ>::TM][IgWgradTile<BM, BJ>::TJ],
+                                                   int wm_off, int wj_off, int lane) {
+    using W = IgWgradTile<BM, BJ>;
+    constexpr int TM = W::TM, TJ = W::TJ, GLD = W::GLD, BLD = W::BLD;
+    const int kl = lane >> 5, il = lane & 31;
+    const float* gp = Gs + kl * GLD + wm_off + il;
+    const float* bp = Bs + kl * BLD + wj_off + il;
+    float a[2][2][TM], b[2][2][TJ];
+    auto frag = [&](int kk, float (&fa)[2][TM], float (&fb)[2][TJ]) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) { fa[0][i] = gp[kk * GLD + i * 32]; fa[1][i] = gp[(kk + 2) * GLD + i * 32]; }
+#pragma unroll
+        for (int t = 0; t < TJ; ++t) { fb[0][t] = bp[kk * BLD + t * 32]; fb[1][t] = bp[(kk + 2) * BLD + t * 32]; }
+    };
+    auto mma = [&](const float (&fa)[2][TM], const float (&fb)[2][TJ]) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int t = 0; t < TJ; ++t)
+                    acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[h][i], fb[h][t], acc[i][t], 0, 0, 0);
+    };
+    frag(0, a[0], b[0]);
+#pragma unroll
+    for (int kk = 0; kk < WG_BP; kk += 8) {
+        frag(kk + 4, a[1], b[1]);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(a[0], b[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (kk + 8 < WG_BP) frag(kk + 8, a[0], b[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(a[1], b[1]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// a wave's accumulator tiles into this pixel split's slab [Mp][Jp] (whole tiles: the slab is padded)
+template <int BM, int BJ>
+__device__ __forceinline__ void ig_wgrad_store_slab(float* __restrict__ slabs,
+                                                    const f32x16 (&acc)[IgWgradTile<BM, BJ>::TM][IgWgradTile<BM, BJ>::TJ],
+                                                    int Mp, int Jp, int m0, int j0, int wm_off, int wj_off, int lane) {
+    using W = IgWgradTile<BM, BJ>;
     float* slab = slabs + (size_t)blockIdx.z * Mp * Jp;
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+    for (int i = 0; i < W::TM; ++i)
 #pragma unroll
-        for (int t = 0; t < TJ; ++t)
+        for (int t = 0; t < W::TJ; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm_off + i * 32 + mfma_row(r, lane);
                 const int j = j0 + wj_off + t * 32 + (lane & 31);
                 slab[(size_t)m * Jp + j] = acc[i][t][r];
             }
-    if (do_bias) ig_wgrad_store_bias<NG, STEP>(bs, bslab + (size_t)blockIdx.z * Mp + m0, pl, sub);
+}
+
+template <class WLoader, int BM, int BJ>
+__global__ __launch_bounds__(IG_THREADS) void igemm_wgrad_kernel(
+    typename WLoader::Params p, float* __restrict__ slabs, int Mp, int Jp, long long N, long long pix_per_split,
+    float* __restrict__ bslab) {
+    using W = IgWgradTile<BM, BJ>;
+    // two LDS stages, one barrier per pixel chunk (32 pixels): chunk k+1 is stored while chunk k is consumed
+    __shared__ float Gs[2][WG_BP * W::GLD];
+    __shared__ float Bs[2][WG_BP * W::BLD];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int j0 = blockIdx.x * BJ, m0 = blockIdx.y * BM;
+    const long long n_begin = (long long)blockIdx.z * pix_per_split;
+    long long n_end = n_begin + pix_per_split;
+    if (n_end > N) n_end = N;
+    const int wm_off = (wid / W::WJ) * 32 * W::TM, wj_off = (wid % W::WJ) * 32 * W::TJ;
+    IgWgradStager<WLoader, BM, BJ> stg(p, n_begin, n_end, m0, j0, tid, bslab != nullptr && blockIdx.x == 0);
+    f32x16 acc[W::TM][W::TJ];
+    ig_zero(acc);
+    stg.load();
+    stg.store(Gs[0], Bs[0]);
+    if (n_begin + WG_BP < n_end) stg.advance_load();
+    __syncthreads();
+    int cur = 0;
+    for (long long nb = n_begin; nb < n_end; nb += WG_BP) {
+        ig_wgrad_mma_chunk<BM, BJ>(Gs[cur], Bs[cur], acc, wm_off, wj_off, lane);
+        if (nb + WG_BP < n_end) {
+            stg.store(Gs[cur ^ 1], Bs[cur ^ 1]);
+            if (nb + 2 * WG_BP < n_end) stg.advance_load();
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    ig_wgrad_store_slab<BM, BJ>(slabs, acc, Mp, Jp, m0, j0, wm_off, wj_off, lane);
+    stg.store_bias(bslab, Mp);
 }
 
 // Wave-specialised weight-gradient kernel (see igemm_fwd_ws_kernel): threads 256..511 run the two loaders and the
@@ -1130,13 +1114,9 @@ template <class WLoader, int BM, int BJ>
 __global__ __launch_bounds__(2 * IG_THREADS) void igemm_wgrad_ws_kernel(
     typename WLoader::Params p, float* __restrict__ slabs, int Mp, int Jp, long long N, long long pix_per_split,
     float* __restrict__ bslab) {
-    constexpr int GLD = BM + 1, BLD = BJ + 1;
-    constexpr int STEP = IG_THREADS / WG_BP;
-    constexpr int TM = (BM == 128 && BJ == 128) ? 2 : 1, TJ = (BM / 32) * (BJ / 32) / 4 / TM;     // see igemm_wgrad_kernel
-    constexpr int WJ = BJ / 32 / TJ, NG = BM / STEP, NB = BJ / STEP;
-    static_assert((BM / 32 / TM) * WJ == 4, "four waves tile the block");
-    __shared__ float Gs[2][WG_BP * GLD];
-    __shared__ float Bs[2][WG_BP * BLD];
+    using W = IgWgradTile<BM, BJ>;
+    __shared__ float Gs[2][WG_BP * W::GLD];
+    __shared__ float Bs[2][WG_BP * W::BLD];
     const bool producer = threadIdx.x >= IG_THREADS;            // wave-uniform
     const int tid = threadIdx.x & (IG_THREADS - 1), lane = tid & 63, wid = tid >> 6;
     const int j0 = blockIdx.x * BJ, m0 = blockIdx.y * BM;
@@ -1144,101 +1124,36 @@ __global__ __launch_bounds__(2 * IG_THREADS) void igemm_wgrad_ws_kernel(
     long long n_end = n_begin + pix_per_split;
     if (n_end > N) n_end = N;
     if (producer) {
-        const int pl = tid % WG_BP, sub = tid / WG_BP;
-        WLoader ld(p, n_begin + pl, n_end);
-        struct Regs { float rg[NG], rb[NB]; };
-        const bool do_bias = bslab != nullptr && blockIdx.x == 0;       // (see igemm_wgrad_kernel: bias row sums)
-        float bs[NG];
-#pragma unroll
-        for (int i = 0; i < NG; ++i) bs[i] = 0.0f;
-        auto stage_store = [&](int buf, const Regs& r) {
-#pragma unroll
-            for (int i = 0; i < NG; ++i) Gs[buf][pl * GLD + sub + STEP * i] = r.rg[i];
-#pragma unroll
-            for (int i = 0; i < NB; ++i) Bs[buf][pl * BLD + sub + STEP * i] = r.rb[i];
-            if (do_bias) {
-#pragma unroll
-                for (int i = 0; i < NG; ++i) bs[i] += r.rg[i];
-            }
-        };
-        auto stage_load = [&](Regs& r) {
-            ld.template load_g<NG, STEP>(m0, sub, r.rg);
-            ld.template load_b<NB, STEP>(j0, sub, r.rb);
-        };
+        // one register stage (a second one measured +0.7 ms per step: DESIGN.md section 10)
+        IgWgradStager<WLoader, BM, BJ> stg(p, n_begin, n_end, m0, j0, tid, bslab != nullptr && blockIdx.x == 0);
         const int nchunk = (int)((n_end - n_begin + WG_BP - 1) / WG_BP);
-        Regs r0;    // one register stage (a second one measured +0.7 ms per step: DESIGN.md section 10)
-        stage_load(r0);
-        stage_store(0, r0);
-        if (1 < nchunk) { ld.advance(); stage_load(r0); }
+        stg.load();
+        stg.store(Gs[0], Bs[0]);
+        if (1 < nchunk) stg.advance_load();
         __syncthreads();
         int cur = 0;
         for (int c = 0; c < nchunk; ++c) {
             if (c + 1 < nchunk) {
-                stage_store(cur ^ 1, r0);
-                if (c + 2 < nchunk) { ld.advance(); stage_load(r0); }
+                stg.store(Gs[cur ^ 1], Bs[cur ^ 1]);
+                if (c + 2 < nchunk) stg.advance_load();
             }
             __syncthreads();
             cur ^= 1;
         }
-        if (do_bias) ig_wgrad_store_bias<NG, STEP>(bs, bslab + (size_t)blockIdx.z * Mp + m0, pl, sub);
+        stg.store_bias(bslab, Mp);
         return;
     }
-    const int wm_off = (wid / WJ) * 32 * TM, wj_off = (wid % WJ) * 32 * TJ;
-    f32x16 acc[TM][TJ];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int t = 0; t < TJ; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][t][r] = 0.0f;
+    const int wm_off = (wid / W::WJ) * 32 * W::TM, wj_off = (wid % W::WJ) * 32 * W::TJ;
+    f32x16 acc[W::TM][W::TJ];
+    ig_zero(acc);
     __syncthreads();
     int cur = 0;
-    const int kl = lane >> 5, il = lane & 31;
     for (long long nb = n_begin; nb < n_end; nb += WG_BP) {
-        const float* gp = Gs[cur] + kl * GLD + wm_off + il;
-        const float* bp = Bs[cur] + kl * BLD + wj_off + il;
-        float a[2][2][TM], b[2][2][TJ];
-        auto frag = [&](int kk, float (&fa)[2][TM], float (&fb)[2][TJ]) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) { fa[0][i] = gp[kk * GLD + i * 32]; fa[1][i] = gp[(kk + 2) * GLD + i * 32]; }
-#pragma unroll
-            for (int t = 0; t < TJ; ++t) { fb[0][t] = bp[kk * BLD + t * 32]; fb[1][t] = bp[(kk + 2) * BLD + t * 32]; }
-        };
-        auto mma = [&](const float (&fa)[2][TM], const float (&fb)[2][TJ]) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int t = 0; t < TJ; ++t)
-                        acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[h][i], fb[h][t], acc[i][t], 0, 0, 0);
-        };
-        frag(0, a[0], b[0]);
-#pragma unroll
-        for (int kk = 0; kk < WG_BP; kk += 8) {
-            frag(kk + 4, a[1], b[1]);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(a[0], b[0]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kk + 8 < WG_BP) frag(kk + 8, a[0], b[0]);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(a[1], b[1]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        ig_wgrad_mma_chunk<BM, BJ>(Gs[cur], Bs[cur], acc, wm_off, wj_off, lane);
         __syncthreads();
         cur ^= 1;
     }
-    float* slab = slabs + (size_t)blockIdx.z * Mp * Jp;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int t = 0; t < TJ; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm_off + i * 32 + mfma_row(r, lane);
-                const int j = j0 + wj_off + t * 32 + (lane & 31);
-                slab[(size_t)m * Jp + j] = acc[i][t][r];
-            }
+    ig_wgrad_store_slab<BM, BJ>(slabs, acc, Mp, Jp, m0, j0, wm_off, wj_off, lane);
 }
 
 }  // namespace cnuda

@@ -285,6 +285,29 @@ def test_conv2d_forward_with_quad_interleaved_output_rows(name):
     assert L.cnuda_conv2d_rowquads_supported(B, K, H, W, M + 2, 1, 1, 1, 1, 0, 0) == 0
 
 
+def test_short_k_kernel_stores_a_plane_that_is_no_multiple_of_four_pixels():
+    """igemm_fwd_shortk_kernel's one-dword-per-lane epilogue, for its full 128-row tiles and for the 64-row tail tile
+    (576 rows = 4.5 tiles): a 63 x 65 plane is no multiple of four pixels, so Out::vec4_ok refuses the 16-byte stores
+    that every other short-K case (64 x 64 planes, row quads) leaves through.  128 pixel tiles x 5 row tiles keep the
+    128-row tile (pick_bm: >= 512 tiles); the last pixel tile is partial (16,380 pixels).  Values: the convolution
+    restated in fp64."""
+    import hip_runtime as hr
+    from hip_runtime import ops
+    from test_zz_kernel_coverage import short
+    B, K, H, W, M = 4, 64, 63, 65, 576
+    g = torch.Generator().manual_seed(12)
+    x = torch.randn(B, K, H, W, generator=g)
+    w = torch.randn(M, K, 1, 1, generator=g) / K ** 0.5
+    want = F.conv2d(x.double(), w.double())
+    with hr.launch_log() as log, torch.no_grad():
+        got = ops.conv2d(x.to(DEV), w.to(DEV), None, 1, 0, -1.0)
+    names = sorted(short(n) for n in log.names)
+    print(names)
+    if hr.get_matrix_mode() == 0 and os.environ.get('CNUDA_SHORTK') != '0':
+        assert any(n.startswith('igemm_fwd_shortk_kernel<128, ConvFwd') for n in names), names
+    _close(got, want)
+
+
 @pytest.mark.parametrize('relu,res', [(False, False), (True, False), (True, True), (False, True)])
 @pytest.mark.parametrize('shape', [(2, 16, 10, 12), (3, 5, 7, 7), (1, 64, 2, 2), (16, 512, 4, 4)])   # (last: 4 images per workgroup)
 def test_batch_norm_train_fwd_bwd_and_running_stats(shape, relu, res):
