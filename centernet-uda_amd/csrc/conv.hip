@@ -951,9 +951,18 @@ const char* wgrad_loader_name(WgradPath w) {
 }
 
 // taps of a kh x kw / stride (sh, sw) kernel that reach the input pixels of parity (py, px): (iy + ph - r) must be a
-// multiple of sh for every iy = py + sh * qy -- decided by py alone (C++ % keeps the dividend's sign; zero is zero either way)
-bool class_tap(const ConvGeom& g, int py, int px, int r, int t) {
-    return (py + g.ph - r) % g.sh == 0 && (px + g.pw - t) % g.sw == 0;
+// multiple of sh for every iy = py + sh * qy -- decided by py alone (C++ % keeps the dividend's sign; zero is zero either way).
+// In packed-K order into cp.tap_r / tap_s / tap_dy / tap_dx and, for launch_pack_taps, flat[]; -> cp.ntaps (make_plan: at most 9)
+int class_taps(const ConvGeom& g, int py, int px, ConvDgradClassParams& cp, int* flat) {
+    cp.ntaps = 0;
+    for (int r = 0; r < g.kh; ++r)
+        for (int t = 0; t < g.kw; ++t)
+            if ((py + g.ph - r) % g.sh == 0 && (px + g.pw - t) % g.sw == 0) {
+                cp.tap_r[cp.ntaps] = r; cp.tap_s[cp.ntaps] = t; flat[cp.ntaps] = r * g.kw + t;
+                cp.tap_dy[cp.ntaps] = (py + g.ph - r) / g.sh; cp.tap_dx[cp.ntaps] = (px + g.pw - t) / g.sw;
+                ++cp.ntaps;
+            }
+    return cp.ntaps;
 }
 // K of a parity class's GEMM (ntaps == 0, a class no tap reaches: K is all padding, the kernel writes zeros)
 int class_kp(int ntaps, int Co) { return round_up(ntaps > 0 ? ntaps * Co : IG_KC, IG_KC); }
@@ -976,8 +985,8 @@ struct ConvPlan {
     int Kf, Kpf, bmf, Mpf;   // forward:  K = T*C,  M = Co
     int Kd, Kpd, bmd, Mpd;   // dgrad:    K = T*Co, M = C
     SplitK skf, skd;         // split-K plans of the two (z == 1: none)
-    int Mpw, Jp, Z, wbm, wbj; // wgrad slabs and tile shape
-    long long Nf, Nd, pix_per_split;
+    WgradShape wg;            // wgrad slabs and tile shape (the halo paths: Z = their own splits)
+    long long Nf, Nd;
     size_t fwd_bytes, dgrad_bytes, wgrad_bytes;
     size_t max_bytes;         // cnuda_conv2d_workspace_bytes: enough for every call of this geometry
 };
@@ -999,21 +1008,16 @@ ConvPlan make_plan(const ConvGeom& g) {
     if (q.skd.on()) q.bmd = q.skd.bm;
     q.Mpf = round_up(g.Co, q.bmf);
     q.Mpd = round_up(g.C, q.bmd);
-    q.wbj = (g.Co <= 32 || (g.C % 64 == 0 && q.Kf % 128 == 0)) ? 128 : 64;   // 64 x 128: +8-13 % where nothing is padded
+    const int wbj = (g.Co <= 32 || (g.C % 64 == 0 && q.Kf % 128 == 0)) ? 128 : 64;   // 64 x 128: +8-13 % where nothing is padded
     // 128 x 64 where the columns do not fill 128 (K = 9 * 64) but the output channels do: the same two accumulator
     // tiles per wave and loads per MFMA as 64 x 128 (the 64 -> 256 head convolutions at 128 x 128)
     const bool wbuf = wgrad_buffer_ok(g);     // (ConvWBufLoader only)
-    q.wbm = g.Co <= 32 ? 32 : ((wbuf && q.wbj == 64 && g.C % 64 == 0 && g.Co % 128 == 0) ? 128 : 64);
+    int wbm = g.Co <= 32 ? 32 : ((wbuf && wbj == 64 && g.C % 64 == 0 && g.Co % 128 == 0) ? 128 : 64);
     // 128 x 128 (2 x 2 accumulator tiles per wave: one fragment dword per MFMA instead of 1.5, 32 loads per 64 MFMAs
     // instead of 24 per 32 -- the 64 x 128 tile runs into the LDS: ~2300 LDS cycles per 2048-cycle chunk with three
     // workgroups per CU) where both extents allow it
-    if (wbuf && q.wbm == 64 && q.wbj == 128 && g.C % 64 == 0 && g.Co % 128 == 0) q.wbm = 128;
-    q.Mpw = round_up(g.Co, q.wbm);
-    q.Jp = round_up(q.Kf, q.wbj);
-    const long long tiles = (long long)(q.Mpw / q.wbm) * (q.Jp / q.wbj);
-    const long long z = wgrad_splits(tiles, q.wbm, q.wbj, (q.Nf + WG_BP - 1) / WG_BP);
-    q.pix_per_split = ((q.Nf + z - 1) / z + WG_BP - 1) / WG_BP * WG_BP;
-    q.Z = (int)((q.Nf + q.pix_per_split - 1) / q.pix_per_split);
+    if (wbuf && wbm == 64 && wbj == 128 && g.C % 64 == 0 && g.Co % 128 == 0) wbm = 128;
+    q.wg = make_wgrad_shape(g.Co, q.Kf, q.Nf, wbm, wbj, WG_BP);
     q.hw = hwgrad_ok(g);
     q.hw_s2 = !q.hw && hwgrad_s2_ok(g);
     q.hw_tiles = q.hw_tiles_per_split = 0;
@@ -1024,7 +1028,7 @@ ConvPlan make_plan(const ConvGeom& g) {
         int zz = std::max(1, 512 / groups);
         if (zz > q.hw_tiles) zz = q.hw_tiles;
         q.hw_tiles_per_split = (q.hw_tiles + zz - 1) / zz;
-        q.Z = (q.hw_tiles + q.hw_tiles_per_split - 1) / q.hw_tiles_per_split;
+        q.wg.Z = (q.hw_tiles + q.hw_tiles_per_split - 1) / q.hw_tiles_per_split;
     }
     q.fwd_bytes = carve_bytes(ig_a_bytes(q.Kpf, q.Mpf), 1) + carve_bytes(splitk_slab_bytes(q.skf, g.Co, q.Nf), 1) + 256;
     q.dgrad_bytes = carve_bytes(ig_a_bytes(q.Kpd, q.Mpd), 1) + carve_bytes(splitk_slab_bytes(q.skd, g.C, q.Nd), 1) + 256;
@@ -1041,8 +1045,8 @@ ConvPlan make_plan(const ConvGeom& g) {
         if (need > q.dgrad_bytes) q.dgrad_bytes = need;
     }
     // (slabs, then the bias row sums per split: [Z][Mpw] -- never less than the [Co][B] scratch of the channel-sum kernels)
-    q.wgrad_bytes = carve_bytes((size_t)q.Z * q.Mpw * q.Jp, 4) +
-                    carve_bytes(std::max((size_t)g.Co * g.B, (size_t)q.Z * q.Mpw), 4) + 256;
+    q.wgrad_bytes = carve_bytes((size_t)q.wg.Z * q.wg.Mpw * q.wg.Jp, 4) +
+                    carve_bytes(std::max((size_t)g.Co * g.B, (size_t)q.wg.Z * q.wg.Mpw), 4) + 256;
 
     // ---- the paths.  Each list is in order of precedence: the first rule that holds names the kernel.
     q.fwd_gemm = q.skf.on() ? FwdPath::BufSplitK
@@ -1062,10 +1066,9 @@ ConvPlan make_plan(const ConvGeom& g) {
         bool any_split = false;
         for (int py = 0; py < g.sh && q.dgrad_buf && !any_split; ++py)
             for (int px = 0; px < g.sw && !any_split; ++px) {
-                int ntaps = 0;
-                for (int r = 0; r < g.kh; ++r)
-                    for (int t = 0; t < g.kw; ++t) ntaps += class_tap(g, py, px, r, t);
-                any_split = pick_splitk(g.C, Nc, class_kp(ntaps, g.Co)).on();
+                ConvDgradClassParams cp;
+                int flat[9];
+                any_split = pick_splitk(g.C, Nc, class_kp(class_taps(g, py, px, cp, flat), g.Co)).on();
             }
         q.dgrad_gemm = (q.dgrad_buf && !any_split && g.sh * g.sw <= MAX_CLASSES && matrix_mode() == 0) ? DgradPath::Classes
                                                                                                     : DgradPath::ClassLoop;
@@ -1082,11 +1085,11 @@ ConvPlan make_plan(const ConvGeom& g) {
     q.wgrad = smallc_supported(g.C, g.Co, g.kh, g.kw, g.sh, g.sw) ? WgradPath::SmallC
             : q.hw_s2 ? WgradPath::HaloS2
             : q.hw ? WgradPath::Halo
-            : (!fast && g.C % 8 == 0 && wbuf && (q.wbm == 32 || (q.wbm == 64 && q.wbj == 64))) ? WgradPath::BufC8
+            : (!fast && g.C % 8 == 0 && wbuf && (wbm == 32 || (wbm == 64 && wbj == 64))) ? WgradPath::BufC8
             : (fast && wbuf) ? WgradPath::Buf
-            : (fast && wave_specialised() && q.wbm == 64) ? WgradPath::PtrFastWs
+            : (fast && wave_specialised() && wbm == 64) ? WgradPath::PtrFastWs
             : fast ? WgradPath::PtrFast : WgradPath::Ptr;
-    q.wgrad_ws = wave_specialised() && q.wbm >= 64 && (q.wgrad == WgradPath::Buf || q.wgrad == WgradPath::PtrFastWs);
+    q.wgrad_ws = wave_specialised() && wbm >= 64 && (q.wgrad == WgradPath::Buf || q.wgrad == WgradPath::PtrFastWs);
     q.max_bytes = std::max(q.fwd_bytes, std::max(q.dgrad_bytes, q.wgrad_bytes));
     if (q.fwd == FwdPath::SmallC || smallc_supported(g.Co, g.C, g.kh, g.kw, g.sh, g.sw))     // (either direction on the LDS-tile kernels)
         q.max_bytes = std::max(q.max_bytes, smallc_workspace_bytes(g.B, g.C, g.H, g.W, g.Co, g.kh, g.kw, g.sh, g.ph, g.pw) +
@@ -1313,30 +1316,225 @@ int launch_fwd(int bm, const typename Loader::Params& p, const float* A, int Mp,
     return check_launch(who);
 }
 
-// The weight-gradient GEMM of one loader: `Tiles` lists the (row, column) tile shapes compiled for it, WS picks the
-// wave-specialised kernel.  false: the plan's tile is not among them.
-template <class Loader, bool WS, class... Tiles, class P>
-bool launch_wgrad(const ConvPlan& q, const P& p, float* slabs, float* bsl, hipStream_t st) {
-    const dim3 grid(q.Jp / q.wbj, q.Mpw / q.wbm, q.Z), blk((WS ? 2 : 1) * IG_THREADS);
-    return with_tiles<Tiles...>(q.wbm, q.wbj, [&](auto BM, auto BJ) {
-        if constexpr (WS)
-            CNUDA_LAUNCH((igemm_wgrad_ws_kernel<Loader, BM(), BJ()>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp, q.Nf, q.pix_per_split, bsl);
-        else
-            CNUDA_LAUNCH((igemm_wgrad_kernel<Loader, BM(), BJ()>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp, q.Nf, q.pix_per_split, bsl);
-    });
-}
 // the tile variants of the buffer-addressed weight-gradient GEMM (ConvWBufLoader; ConvWCatLoader)
 template <class Loader>
 bool launch_wgrad_buf(const ConvPlan& q, const typename Loader::Params& p, float* slabs, float* bsl, hipStream_t st) {
-    return q.wgrad_ws ? launch_wgrad<Loader, true, Tile<128, 128>, Tile<128, 64>, Tile<64, 128>, Tile<64, 64>>(q, p, slabs, bsl, st)
-                      : launch_wgrad<Loader, false, Tile<128, 128>, Tile<128, 64>, Tile<64, 128>, Tile<64, 64>, Tile<32, 128>>(q, p, slabs, bsl, st);
+    return q.wgrad_ws ? launch_wgrad<Loader, true, Tile<128, 128>, Tile<128, 64>, Tile<64, 128>, Tile<64, 64>>(q.wg, p, slabs, bsl, st)
+                      : launch_wgrad<Loader, false, Tile<128, 128>, Tile<128, 64>, Tile<64, 128>, Tile<64, 64>, Tile<32, 128>>(q.wg, p, slabs, bsl, st);
+}
+
+// The *_supported queries on a plan (as plan_stats_block): the exported query is fill_geom, make_plan and this form
+// (plan_query); the entry point asks the plan its call already has (ConvCall::open).
+using PlanQuery = bool (*)(const ConvGeom&, const ConvPlan&);
+// the concatenating loaders are forms of the buffer-addressed GEMMs without a K split, in all three directions; their
+// forward epilogue stores four pixels at a time
+bool plan_cat_ok(const ConvGeom& g, const ConvPlan& q) {
+    return q.fwd == FwdPath::Buf && q.dgrad == DgradPath::Buf && q.wgrad == WgradPath::Buf && ((g.H * g.W) & 3) == 0;
+}
+// (a form of the buffer-addressed GEMM, also where the plain forward would take halo tiles)
+bool plan_rowquads_ok(const ConvGeom& g, const ConvPlan& q) { return g.Co % 4 == 0 && q.fwd != FwdPath::SmallC && q.fwd != FwdPath::BufSplitK && q.fwd_buf; }
+bool plan_rowsig_ok(const ConvGeom& g, const ConvPlan& q) { return g.Co <= 32 && matrix_mode() == 0 && q.fwd != FwdPath::SmallC && q.fwd_buf && q.y_buf; }
+int plan_query(PlanQuery ok, const char* who, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw) {
+    ConvGeom g;
+    if (fill_geom(g, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, who)) return 0;
+    return ok(g, make_plan(g)) ? 1 : 0;
+}
+
+// One call of a convolution entry point (as DcnCall in dcn.hip): the geometry, the plan made from it -- once per call --
+// the stream, the Carver over the caller's workspace and the exported function's name as its messages give it.
+enum class ConvDir { Fwd = 0, Dgrad = 1, Wgrad = 2 };
+struct ConvCall {
+    const char* who;
+    hipStream_t st;
+    void* workspace;  size_t workspace_bytes;
+    Carver cv;
+    bool gemm_only = false;   // the call has no form on the LDS-tile kernels (a residual; an addend that aliases grad_x)
+    ConvGeom g;
+    ConvPlan q;
+    ConvCall(const char* who_, void* ws, size_t bytes, cnuda_stream_t stream)
+        : who(who_), st((hipStream_t)stream), workspace(ws), workspace_bytes(bytes), cv(ws, bytes) {}
+    FwdPath fwd() const { return gemm_only ? q.fwd_gemm : q.fwd; }
+    DgradPath dgrad() const { return gemm_only ? q.dgrad_gemm : q.dgrad; }
+    // Geometry, plan, and the workspace against the bytes of `dir` (not where the LDS-tile kernels take the call: they check
+    // their own).  `ok`: the entry point's *_supported query -- no geometry, or a plan it refuses, is the call's `unsupported`.
+    int open(ConvDir dir, bool gemm_only_, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+             PlanQuery ok = nullptr, const char* unsupported = nullptr) {
+        gemm_only = gemm_only_;
+        const int bad = fill_geom(g, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, who);
+        if (!bad) q = make_plan(g);
+        if (ok) CNUDA_REQUIRE(!bad && ok(g, q), "%s: %s", who, unsupported);
+        if (bad) return bad;
+        const bool lds_tiles[] = {fwd() == FwdPath::SmallC, dgrad() == DgradPath::SmallC, q.wgrad == WgradPath::SmallC};
+        const size_t need[] = {q.fwd_bytes, q.dgrad_bytes, q.wgrad_bytes};
+        CNUDA_REQUIRE(lds_tiles[(int)dir] || (workspace && workspace_bytes >= need[(int)dir]), "%s: workspace too small", who);
+        return 0;
+    }
+    void rewind() { cv = Carver(workspace, workspace_bytes); }
+    // room for a packed [Kp][Mp] matrix; the slabs of a split-K plan (null without one)
+    float* a_room(int Kp, int Mp) { return reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(Kp, Mp))); }
+    float* splitk_slabs(const SplitK& sk, int M, long long N) {
+        return sk.on() ? reinterpret_cast<float*>(cv.take<char>(splitk_slab_bytes(sk, M, N))) : nullptr;
+    }
+    // the weights packed in the plan's room: forward-shaped [Kpf][Mpf] or, for the two input-gradient modes, [Kpd][Mpd]
+    // (halo tiles: K = 9 C is already a multiple of the chunk -- the same packed size, another K order)
+    const float* pack(const float* weight, PackMode mode) {
+        const bool dg = mode == PACK_DGRAD || mode == PACK_HALO_DGRAD;
+        const int Kp = dg ? q.Kpd : q.Kpf, Mp = dg ? q.Mpd : q.Mpf;
+        return launch_pack(weight, a_room(Kp, Mp), ig_a_bytes(Kp, Mp), g.Co, g.C, q.T, mode, Kp, Mp, mode == PACK_DGRAD ? round_up(g.Co, IG_BK) : 0, st);
+    }
+    // launch_fwd on the plan's forward / input-gradient GEMM; `as`: the name its messages carry
+    template <class Loader, class P> int fwd_gemm(const P& p, const float* A, const char* as, const SplitK& sk = SplitK(), float* slab = nullptr) {
+        return launch_fwd<Loader>(q.bmf, p, A, q.Mpf, q.Kpf, g.Co, q.Nf, st, as, sk, slab);
+    }
+    template <class Loader, class P> int dgrad_gemm(const P& p, const float* A, const char* as, const SplitK& sk = SplitK(), float* slab = nullptr) {
+        return launch_fwd<Loader>(q.bmd, p, A, q.Mpd, q.Kpd, g.C, q.Nd, st, as, sk, slab);
+    }
+};
+
+// ---- the input gradient: one function per kernel family (cnuda_conv2d_backward_data_add switches over DgradPath) ----
+struct DgradArgs { const float *gy, *weight, *add, *add2; float* gx; };   // add, add2: nullable, shaped like gx (may BE gx on the GEMM paths)
+// the LDS-tile kernels of the 3- / 16-channel layers with the roles swapped; they have no addend: one elementwise pass each
+int dgrad_lds_tiles(ConvCall& c, const DgradArgs& a) {
+    const ConvGeom& g = c.g;
+    const long long n = (long long)g.B * g.C * g.H * g.W;
+    if (int rc = smallc_forward(a.gy, a.weight, nullptr, a.gx, g.B, g.Co, g.Ho, g.Wo, g.C, g.kh, g.kw, 1, g.kh - 1 - g.ph,
+                                g.kw - 1 - g.pw, -1.0f, 1, c.workspace, c.workspace_bytes, c.st))
+        return rc;
+    if (a.add) if (int rc = cnuda_add(a.gx, a.add, a.gx, n, (cnuda_stream_t)c.st)) return rc;
+    return a.add2 ? cnuda_add(a.gx, a.add2, a.gx, n, (cnuda_stream_t)c.st) : 0;
+}
+int dgrad_s2_c16(ConvCall& c, const DgradArgs& a) {
+    const ConvGeom& g = c.g;
+    float* wt = c.a_room(c.q.Kpd, c.q.Mpd);
+    CNUDA_LAUNCH(dgrad_s2_c16_pack_kernel, dim3((g.Co * 144 + 255) / 256), dim3(256), 0, c.st, a.weight, wt, g.Co);
+    DgradS2Params dp{a.gy, wt, a.gx, a.add, a.add2, g.B, g.Co, g.H, g.W, g.Ho, g.Wo, (g.H + 1) / 2, (g.W + 1) / 2};
+    ProfScope prof(c.st);
+    prof.name("dgrad_s2_c16_kernel");
+    CNUDA_LAUNCH(dgrad_s2_c16_kernel, dim3((dp.QW + 63) / 64, (dp.QH + 3) / 4, g.B), dim3(256), 0, c.st, dp);
+    return check_launch("cnuda_conv2d_backward_data(stride 2, 16 channels)");
+}
+// The parity classes, as one launch (DgradPath::Classes) or as one launch per class (ClassLoop: buffer-addressed, each
+// with its own split-K plan, or the pointer loader).  Both forms read one table of the classes.
+int dgrad_classes(ConvCall& c, const DgradArgs& a) {
+    const ConvGeom& g = c.g;  const ConvPlan& q = c.q;  hipStream_t st = c.st;
+    ProfScope prof(st);   // brackets the whole class group (inner scopes find nothing armed)
+    prof.name("igemm_fwd*_kernel<*, ConvDgradClassLoader> x %d parity classes", g.sh * g.sw);
+    const long long Nc = (long long)g.B * (g.H / g.sh) * (g.W / g.sw);
+    ConvDgradClassParams cps[16];
+    int Kpcs[16], taps_all[16][9], ncls = 0;
+    for (int py = 0; py < g.sh; ++py)
+        for (int px = 0; px < g.sw; ++px) {
+            CNUDA_REQUIRE(ncls < 16, "cnuda_conv2d_backward_data: more than 16 parity classes");
+            ConvDgradClassParams& cp = cps[ncls];
+            cp.g = g; cp.gy = a.gy; cp.gx = a.gx; cp.py = py; cp.px = px; cp.Hc = g.H / g.sh; cp.Wc = g.W / g.sw;
+            cp.add = a.add; cp.add2 = a.add2;
+            Kpcs[ncls] = class_kp(class_taps(g, py, px, cp, taps_all[ncls]), g.Co);
+            ++ncls;
+        }
+    if (c.dgrad() == DgradPath::Classes) {
+        const int bm = conv_pick_bm(g.C, Nc * ncls), Mp = round_up(g.C, bm);      // (the grid is ncls times one class's)
+        // classes in order of decreasing K: the long ones start first
+        int order[MAX_CLASSES];
+        for (int i = 0; i < ncls; ++i) order[i] = i;
+        std::stable_sort(order, order + ncls, [&](int a1, int b1) { return Kpcs[a1] > Kpcs[b1]; });
+        ConvDgradClassSet set;
+        for (int i = 0; i < ncls; ++i) {       // their packed matrices side by side
+            const int k = order[i];
+            float* dst = c.a_room(Kpcs[k], Mp);
+            CNUDA_REQUIRE(c.cv.ok(), "cnuda_conv2d_backward_data: workspace");
+            set.cls[i] = cps[k];
+            set.Kp[i] = Kpcs[k];
+            set.A[i] = launch_pack_taps(a.weight, dst, ig_a_bytes(Kpcs[k], Mp), g.Co, g.C, q.T, taps_all[k], cps[k].ntaps, Kpcs[k], Mp, st);
+        }
+        for (int i = ncls; i < MAX_CLASSES; ++i) { set.cls[i] = set.cls[0]; set.Kp[i] = set.Kp[0]; set.A[i] = set.A[0]; }
+        CNUDA_REQUIRE(Nc < (1ll << 31) - IG_BN, "cnuda_conv2d_backward_data: more than 2^31 pixels per call");
+        const int n_tiles = ceil_div(Nc, IG_BN), m_tiles = Mp / bm;
+        const dim3 grid(n_tiles * m_tiles, ncls);
+        const bool found = (wave_specialised() && bm >= 64)
+            ? with_tile<64, 128>(bm, [&](auto BM) {
+                  CNUDA_LAUNCH((igemm_fwd_ws_classes_kernel<BM()>), grid, dim3(2 * IG_THREADS), 0, st, set, Mp, g.C, Nc, n_tiles, m_tiles);
+              })
+            : with_tile<32, 64, 128>(bm, [&](auto BM) {
+                  CNUDA_LAUNCH((igemm_fwd_classes_kernel<BM()>), grid, dim3(IG_THREADS), 0, st, set, Mp, g.C, Nc, n_tiles, m_tiles);
+              });
+        CNUDA_REQUIRE(found, "cnuda_conv2d_backward_data: no parity-class kernel instance for a %d-row tile", bm);
+        return check_launch("cnuda_conv2d_backward_data(classes)");
+    }
+    for (int ci = 0; ci < ncls; ++ci) {
+        const ConvDgradClassParams& cp = cps[ci];  const int Kpc = Kpcs[ci];
+        const SplitK sc = q.dgrad_buf ? pick_splitk(g.C, Nc, Kpc) : SplitK();
+        const int bm = sc.on() ? sc.bm : conv_pick_bm(g.C, Nc), Mp = round_up(g.C, bm);
+        c.rewind();           // every class packs at the head of the workspace, its slabs behind its own matrix
+        float* dst = c.a_room(Kpc, Mp);
+        float* slab = c.splitk_slabs(sc, g.C, Nc);
+        CNUDA_REQUIRE(c.cv.ok(), "cnuda_conv2d_backward_data: workspace");
+        const float* A = launch_pack_taps(a.weight, dst, ig_a_bytes(Kpc, Mp), g.Co, g.C, q.T, taps_all[ci], cp.ntaps, Kpc, Mp, st);
+        if (int rc = q.dgrad_buf ? launch_fwd<ConvDgradClassBufLoader>(bm, cp, A, Mp, Kpc, g.C, Nc, st, "cnuda_conv2d_backward_data(class)", sc, slab)
+                                 : launch_fwd<ConvDgradClassLoader>(bm, cp, A, Mp, Kpc, g.C, Nc, st, "cnuda_conv2d_backward_data(class)"))
+            return rc;
+    }
+    return 0;
+}
+int dgrad_halo(ConvCall& c, const DgradArgs& a) {
+    const ConvGeom& g = c.g;
+    const float* A = c.pack(a.weight, PACK_HALO_DGRAD);
+    ConvDgradParams p{g, a.gy, a.gx, g.Co, a.add, a.add2};
+    return launch_hconv<HconvDgrad>(c.q.bmd, p, a.gy, g.Co, g, A, c.q.Mpd, c.q.Kpd, g.C, c.q.Nd, c.st, "cnuda_conv2d_backward_data");
+}
+// the plain GEMMs: buffer-addressed (with or without a K split) or pointer-addressed
+int dgrad_gemm(ConvCall& c, const DgradArgs& a) {
+    const ConvGeom& g = c.g;
+    const float* A = c.pack(a.weight, PACK_DGRAD);
+    ConvDgradParams p{g, a.gy, a.gx, round_up(g.Co, IG_BK), a.add, a.add2};
+    if (c.dgrad() == DgradPath::Ptr) return c.dgrad_gemm<ConvDgradLoader>(p, A, "cnuda_conv2d_backward_data");
+    return c.dgrad_gemm<ConvDgradBufLoader>(p, A, "cnuda_conv2d_backward_data", c.q.skd, c.splitk_slabs(c.q.skd, g.C, c.q.Nd));
+}
+
+// the weight gradient on the LDS-tile kernels (with or without apply on load); the bias gradient is a channel sum of grad_y
+int wgrad_lds_tiles(const ConvGeom& g, const float* x, const float* gy, float* gw, float* gb, void* ws, size_t ws_bytes,
+                    hipStream_t st, const SmallNorm* norm, const char* who) {
+    if (int rc = smallc_backward_weight(x, gy, gw, g.B, g.C, g.H, g.W, g.Co, g.kh, g.kw, g.sh, g.ph, g.pw, ws, ws_bytes, st, norm)) return rc;
+    if (gb) launch_channel_sum(gy, gb, g.B, g.Co, (long long)g.Ho * g.Wo, st);
+    return check_launch(who);
+}
+
+// ---- the 1x1 convolution over a channel concatenation (ConvCat; DLA's Root) ------------------------------------------------
+int fill_cat(ConvCat& cat, const float* const* xs, const int* cs, int n, const char* who) {
+    CNUDA_REQUIRE(xs && cs && n >= 2 && n <= CAT_MAX, "%s: 2 .. %d sources", who, CAT_MAX);
+    int k = 0;
+    for (int i = 0; i < CAT_MAX; ++i) {
+        cat.x[i] = i < n ? xs[i] : nullptr;
+        cat.c[i] = i < n ? cs[i] : 0;
+        cat.k0[i] = k;
+        if (i < n) {
+            CNUDA_REQUIRE(xs[i] && cs[i] > 0 && cs[i] % 64 == 0, "%s: source %d: null or not a multiple of 64 channels", who, i);
+            k += cs[i];
+        }
+    }
+    cat.k0[CAT_MAX] = k;
+    for (int i = n; i < CAT_MAX; ++i) cat.k0[i] = k;
+    cat.n = n;
+    return 0;
+}
+// the sources' channel counts as the concatenating loaders need them; -> all channels (0: no such concatenation)
+int cat_channels(const int* cs, int n) {
+    if (!cs || n < 2 || n > CAT_MAX || matrix_mode() != 0) return 0;
+    int k = 0;
+    for (int i = 0; i < n; ++i) {
+        if (cs[i] <= 0 || cs[i] % 64 != 0) return 0;
+        k += cs[i];
+    }
+    return k;
+}
+// ConvCall::open for the three concatenation entry points: what cnuda_conv2d_cat_supported refuses (no channels: no geometry)
+int open_cat(ConvCall& c, ConvDir dir, const int* cs, int n, int B, int H, int W, int Cout) {
+    return c.open(dir, false, B, cat_channels(cs, n), H, W, Cout, 1, 1, 1, 1, 0, 0, plan_cat_ok, "unsupported (cnuda_conv2d_cat_supported)");
 }
 
 }  // namespace
 }  // namespace cnuda
 
 using namespace cnuda;
-
 
 extern "C" int cnuda_conv_set_splitk_policy(int max_tiles) {
     const int prev = g_splitk_max_tiles;
@@ -1389,82 +1587,29 @@ extern "C" int cnuda_conv2d_forward_stats(const float* x, const float* weight, c
                                           int sh, int sw, int ph, int pw, float act_slope, void* workspace,
                                           size_t workspace_bytes, cnuda_stream_t stream) {
     CNUDA_REQUIRE(x && weight && y, "cnuda_conv2d_forward: null pointer");
-    ConvGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_forward")) return rc;
-    const ConvPlan q = make_plan(g);
-    CNUDA_REQUIRE(!stats || (!residual && act_slope < 0.0f && plan_stats_block(g, q, nullptr, nullptr) != 0),
+    ConvCall c("cnuda_conv2d_forward", workspace, workspace_bytes, stream);
+    if (int rc = c.open(ConvDir::Fwd, residual != nullptr, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw)) return rc;   // (the LDS-tile kernels have no residual)
+    CNUDA_REQUIRE(!stats || (!residual && act_slope < 0.0f && plan_stats_block(c.g, c.q, nullptr, nullptr) != 0),
                   "cnuda_conv2d_forward_stats: no statistics for this call (cnuda_conv2d_stats_block says which)");
-    const FwdPath path = residual ? q.fwd_gemm : q.fwd;       // (the LDS-tile kernels have no residual)
-    if (path == FwdPath::SmallC)
+    if (c.fwd() == FwdPath::SmallC)
         return smallc_forward(x, weight, bias, y, B, C, H, W, Cout, kh, kw, sh, ph, pw, act_slope, 0, workspace,
-                              workspace_bytes, (hipStream_t)stream, stats);
-    CNUDA_REQUIRE(workspace && workspace_bytes >= q.fwd_bytes, "cnuda_conv2d_forward: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    Carver cv(workspace, workspace_bytes);
-    ConvFwdParams p{g, x, bias, y, act_slope, residual};
-    // (halo tiles: K = 9 C is already a multiple of the chunk -- the same packed size, another K order)
-    const float* A = launch_pack(weight, reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpf, q.Mpf))), ig_a_bytes(q.Kpf, q.Mpf),
-                                 Cout, C, q.T, path == FwdPath::Halo ? PACK_HALO_FWD : PACK_FWD, q.Kpf, q.Mpf, 0, st);
-    switch (path) {
-        case FwdPath::Halo:
-            return launch_hconv<HconvFwd>(q.bmf, p, x, C, g, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
-        case FwdPath::BufSplitK: {
-            float* slab = reinterpret_cast<float*>(cv.take<char>(splitk_slab_bytes(q.skf, Cout, q.Nf)));
-            return launch_fwd<ConvFwdBufLoader>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward", q.skf, slab);
-        }
-        case FwdPath::Buf:
-            if (stats) {            // (plan_stats_block vouched for this path)
-                ConvFwdStatsParams ps;
-                static_cast<ConvFwdParams&>(ps) = p;
-                ps.stats = stats;
-                ps.stats_mp = q.Mpf;
-                return launch_fwd<ConvFwdBufStatsLoader>(q.bmf, ps, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward_stats");
-            }
-            return launch_fwd<ConvFwdBufLoader>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
-        case FwdPath::PtrFast:
-            return launch_fwd<ConvFwdLoader<true>>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
-        default:
-            return launch_fwd<ConvFwdLoader<false>>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward");
+                              workspace_bytes, c.st, stats);
+    ConvFwdParams p{c.g, x, bias, y, act_slope, residual};
+    const float* A = c.pack(weight, c.fwd() == FwdPath::Halo ? PACK_HALO_FWD : PACK_FWD);
+    switch (c.fwd()) {
+        case FwdPath::Halo: return launch_hconv<HconvFwd>(c.q.bmf, p, x, C, c.g, A, c.q.Mpf, c.q.Kpf, Cout, c.q.Nf, c.st, c.who);
+        case FwdPath::BufSplitK: case FwdPath::Buf:
+            if (stats)              // (plan_stats_block vouched for this path: Buf)
+                return c.fwd_gemm<ConvFwdBufStatsLoader>(ConvFwdStatsParams{p, stats, c.q.Mpf}, A, "cnuda_conv2d_forward_stats");
+            return c.fwd_gemm<ConvFwdBufLoader>(p, A, c.who, c.q.skf, c.splitk_slabs(c.q.skf, Cout, c.q.Nf));
+        case FwdPath::PtrFast: return c.fwd_gemm<ConvFwdLoader<true>>(p, A, c.who);
+        default: return c.fwd_gemm<ConvFwdLoader<false>>(p, A, c.who);
     }
 }
-
-// ---- the 1x1 convolution over a channel concatenation (ConvCat; DLA's Root) ------------------------------------------------
-namespace {
-int fill_cat(ConvCat& cat, const float* const* xs, const int* cs, int n, const char* who) {
-    CNUDA_REQUIRE(xs && cs && n >= 2 && n <= CAT_MAX, "%s: 2 .. %d sources", who, CAT_MAX);
-    int k = 0;
-    for (int i = 0; i < CAT_MAX; ++i) {
-        cat.x[i] = i < n ? xs[i] : nullptr;
-        cat.c[i] = i < n ? cs[i] : 0;
-        cat.k0[i] = k;
-        if (i < n) {
-            CNUDA_REQUIRE(xs[i] && cs[i] > 0 && cs[i] % 64 == 0, "%s: source %d: null or not a multiple of 64 channels", who, i);
-            k += cs[i];
-        }
-    }
-    cat.k0[CAT_MAX] = k;
-    for (int i = n; i < CAT_MAX; ++i) cat.k0[i] = k;
-    cat.n = n;
-    return 0;
-}
-int cat_channels(const int* cs, int n) {
-    int k = 0;
-    for (int i = 0; i < n; ++i) k += cs[i];
-    return k;
-}
-}  // namespace
 
 extern "C" int cnuda_conv2d_cat_supported(const int* cs, int n, int B, int H, int W, int Cout) {
-    if (!cs || n < 2 || n > CAT_MAX || matrix_mode() != 0) return 0;
-    for (int i = 0; i < n; ++i)
-        if (cs[i] <= 0 || cs[i] % 64 != 0) return 0;
     const int C = cat_channels(cs, n);
-    ConvGeom g;
-    if (fill_geom(g, B, C, H, W, Cout, 1, 1, 1, 1, 0, 0, "cnuda_conv2d_cat_supported")) return 0;
-    // the concatenating loaders are forms of the buffer-addressed GEMMs without a K split, in all three directions; their
-    // forward epilogue stores four pixels at a time
-    const ConvPlan q = make_plan(g);
-    return q.fwd == FwdPath::Buf && q.dgrad == DgradPath::Buf && q.wgrad == WgradPath::Buf && ((H * W) & 3) == 0;
+    return C > 0 ? plan_query(plan_cat_ok, "cnuda_conv2d_cat_supported", B, C, H, W, Cout, 1, 1, 1, 1, 0, 0) : 0;
 }
 
 extern "C" int cnuda_conv2d_cat_forward(const float* const* xs, const int* cs, int n, const float* weight, const float* bias,
@@ -1472,22 +1617,11 @@ extern "C" int cnuda_conv2d_cat_forward(const float* const* xs, const int* cs, i
                                         void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
     CNUDA_REQUIRE(weight && y, "cnuda_conv2d_cat_forward: null pointer");
     CNUDA_REQUIRE(!stats || act_slope < 0.0f, "cnuda_conv2d_cat_forward: statistics are those of the plain convolution");
-    CNUDA_REQUIRE(cnuda_conv2d_cat_supported(cs, n, B, H, W, Cout), "cnuda_conv2d_cat_forward: unsupported (cnuda_conv2d_cat_supported)");
-    ConvFwdCatParams p;
-    if (int rc = fill_cat(p.cat, xs, cs, n, "cnuda_conv2d_cat_forward")) return rc;
-    const int C = p.cat.k0[CAT_MAX];
-    ConvGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, 1, 1, 1, 1, 0, 0, "cnuda_conv2d_cat_forward")) return rc;
-    const ConvPlan q = make_plan(g);
-    CNUDA_REQUIRE(workspace && workspace_bytes >= q.fwd_bytes, "cnuda_conv2d_cat_forward: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    Carver cv(workspace, workspace_bytes);
-    static_cast<ConvFwdParams&>(p) = ConvFwdParams{g, nullptr, bias, y, act_slope, nullptr};
-    p.stats = stats;
-    p.stats_mp = q.Mpf;
-    const float* A = launch_pack(weight, reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpf, q.Mpf))),
-                                 ig_a_bytes(q.Kpf, q.Mpf), Cout, C, q.T, PACK_FWD, q.Kpf, q.Mpf, 0, st);
-    return launch_fwd<ConvFwdCatLoader>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_cat_forward");
+    ConvCall c("cnuda_conv2d_cat_forward", workspace, workspace_bytes, stream);
+    if (int rc = open_cat(c, ConvDir::Fwd, cs, n, B, H, W, Cout)) return rc;
+    ConvFwdCatParams p{{{c.g, nullptr, bias, y, act_slope, nullptr}, stats, c.q.Mpf}, {}};
+    if (int rc = fill_cat(p.cat, xs, cs, n, c.who)) return rc;
+    return c.fwd_gemm<ConvFwdCatLoader>(p, c.pack(weight, PACK_FWD), c.who);
 }
 
 // grad_xs[i] = input gradient of source i (+ adds[i] + add2s[i], nullable, shaped like it; either may BE grad_xs[i]); a null
@@ -1497,19 +1631,10 @@ extern "C" int cnuda_conv2d_cat_backward_data(const float* grad_y, const float* 
                                               int B, int H, int W, int Cout, void* workspace, size_t workspace_bytes,
                                               cnuda_stream_t stream) {
     CNUDA_REQUIRE(grad_y && weight && grad_xs, "cnuda_conv2d_cat_backward_data: null pointer");
-    CNUDA_REQUIRE(cnuda_conv2d_cat_supported(cs, n, B, H, W, Cout), "cnuda_conv2d_cat_backward_data: unsupported (cnuda_conv2d_cat_supported)");
-    const int C = cat_channels(cs, n);
-    ConvGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, 1, 1, 1, 1, 0, 0, "cnuda_conv2d_cat_backward_data")) return rc;
-    const ConvPlan q = make_plan(g);
-    CNUDA_REQUIRE(workspace && workspace_bytes >= q.dgrad_bytes, "cnuda_conv2d_cat_backward_data: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    Carver cv(workspace, workspace_bytes);
-    float* Aws = reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpd, q.Mpd)));
-    const float* A = launch_pack(weight, Aws, ig_a_bytes(q.Kpd, q.Mpd), Cout, C, q.T, PACK_DGRAD, q.Kpd, q.Mpd,
-                                 round_up(Cout, IG_BK), st);
-    ConvDgradCatParams p;
-    static_cast<ConvDgradParams&>(p) = ConvDgradParams{g, grad_y, nullptr, round_up(Cout, IG_BK), nullptr, nullptr};
+    ConvCall c("cnuda_conv2d_cat_backward_data", workspace, workspace_bytes, stream);
+    if (int rc = open_cat(c, ConvDir::Dgrad, cs, n, B, H, W, Cout)) return rc;
+    const float* A = c.pack(weight, PACK_DGRAD);
+    ConvDgradCatParams p{{c.g, grad_y, nullptr, round_up(Cout, IG_BK), nullptr, nullptr}};
     for (int i = 0; i < CAT_MAX; ++i) {
         p.gxs[i] = i < n ? grad_xs[i] : nullptr;
         p.adds[i] = (i < n && adds) ? adds[i] : nullptr;
@@ -1519,35 +1644,26 @@ extern "C" int cnuda_conv2d_cat_backward_data(const float* grad_y, const float* 
         CNUDA_REQUIRE(i >= n || p.gxs[i], "cnuda_conv2d_cat_backward_data: source %d without a gradient tensor", i);
     }
     p.n = n;
-    return launch_fwd<ConvDgradCatLoader>(q.bmd, p, A, q.Mpd, q.Kpd, C, q.Nd, st, "cnuda_conv2d_cat_backward_data");
+    return c.dgrad_gemm<ConvDgradCatLoader>(p, A, c.who);
 }
 
 extern "C" int cnuda_conv2d_cat_backward_weight(const float* const* xs, const int* cs, int n, const float* grad_y,
                                                 float* grad_weight, int B, int H, int W, int Cout, void* workspace,
                                                 size_t workspace_bytes, cnuda_stream_t stream) {
     CNUDA_REQUIRE(grad_y && grad_weight, "cnuda_conv2d_cat_backward_weight: null pointer");
-    CNUDA_REQUIRE(cnuda_conv2d_cat_supported(cs, n, B, H, W, Cout), "cnuda_conv2d_cat_backward_weight: unsupported (cnuda_conv2d_cat_supported)");
-    ConvWCatParams p;
-    if (int rc = fill_cat(p.cat, xs, cs, n, "cnuda_conv2d_cat_backward_weight")) return rc;
-    const int C = p.cat.k0[CAT_MAX];
-    ConvGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, 1, 1, 1, 1, 0, 0, "cnuda_conv2d_cat_backward_weight")) return rc;
-    const ConvPlan q = make_plan(g);
-    CNUDA_REQUIRE(workspace && workspace_bytes >= q.wgrad_bytes, "cnuda_conv2d_cat_backward_weight: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    Carver cv(workspace, workspace_bytes);
-    float* slabs = cv.take<float>((size_t)q.Z * q.Mpw * q.Jp);
-    static_cast<ConvWParams&>(p) = ConvWParams{g, nullptr, grad_y};
-    {
-        ProfScope prof(st);
+    ConvCall c("cnuda_conv2d_cat_backward_weight", workspace, workspace_bytes, stream);
+    if (int rc = open_cat(c, ConvDir::Wgrad, cs, n, B, H, W, Cout)) return rc;
+    ConvWCatParams p{{c.g, nullptr, grad_y}, {}};
+    if (int rc = fill_cat(p.cat, xs, cs, n, c.who)) return rc;
+    const ConvPlan& q = c.q;
+    return wgrad_then_reduce(q.wg, c.cv, 0, grad_weight, nullptr, Cout, c.g.C, q.T, c.st, 0, "cnuda_conv2d_cat_backward_weight",
+                             "cnuda_conv2d_cat_backward_weight(reduce)", [&](ProfScope& prof, float* slabs, float* bsl) -> int {
         prof.name(q.wgrad_ws ? "igemm_wgrad_ws_kernel<ConvWCatLoader, %d, %d>" : "igemm_wgrad_kernel<ConvWCatLoader, %d, %d>",
-                  q.wbm, q.wbj);
-        CNUDA_REQUIRE(launch_wgrad_buf<ConvWCatLoader>(q, p, slabs, nullptr, st),
-                      "cnuda_conv2d_cat_backward_weight: no kernel instance for a %d x %d tile", q.wbm, q.wbj);
-    }
-    if (int rc = check_launch("cnuda_conv2d_cat_backward_weight")) return rc;
-    launch_slab_reduce(slabs, grad_weight, q.Z, q.Mpw, q.Jp, Cout, C, q.T, st, nullptr, nullptr);
-    return check_launch("cnuda_conv2d_cat_backward_weight(reduce)");
+                  q.wg.bm, q.wg.bj);
+        CNUDA_REQUIRE(launch_wgrad_buf<ConvWCatLoader>(q, p, slabs, bsl, c.st),
+                      "cnuda_conv2d_cat_backward_weight: no kernel instance for a %d x %d tile", q.wg.bm, q.wg.bj);
+        return 0;
+    });
 }
 
 // y = conv(x) with the output channels interleaved in quads, y[b][Cout / 4][Ho * Wo][4] (ConvFwdBufQuadLoader): the layout of
@@ -1555,29 +1671,19 @@ extern "C" int cnuda_conv2d_cat_backward_weight(const float* const* xs, const in
 // implicit GEMM without a K split; elsewhere the caller keeps the plain layout.  Workspace: cnuda_conv2d_workspace_bytes.
 extern "C" int cnuda_conv2d_rowquads_supported(int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph,
                                                int pw) {
-    ConvGeom g;
-    if (fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_rowquads_supported")) return 0;
-    // (a form of the buffer-addressed GEMM, also where the plain forward would take halo tiles)
-    const ConvPlan q = make_plan(g);
-    return Cout % 4 == 0 && q.fwd != FwdPath::SmallC && q.fwd != FwdPath::BufSplitK && q.fwd_buf;
+    return plan_query(plan_rowquads_ok, "cnuda_conv2d_rowquads_supported", B, C, H, W, Cout, kh, kw, sh, sw, ph, pw);
 }
 
 extern "C" int cnuda_conv2d_forward_rowquads(const float* x, const float* weight, float* y, int B, int C, int H, int W,
                                              int Cout, int kh, int kw, int sh, int sw, int ph, int pw, void* workspace,
                                              size_t workspace_bytes, cnuda_stream_t stream) {
     CNUDA_REQUIRE(x && weight && y, "cnuda_conv2d_forward_rowquads: null pointer");
-    CNUDA_REQUIRE(cnuda_conv2d_rowquads_supported(B, C, H, W, Cout, kh, kw, sh, sw, ph, pw),
-                  "cnuda_conv2d_forward_rowquads: geometry without a quad-interleaved epilogue (cnuda_conv2d_rowquads_supported)");
-    ConvGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_forward_rowquads")) return rc;
-    const ConvPlan q = make_plan(g);
-    CNUDA_REQUIRE(workspace && workspace_bytes >= q.fwd_bytes, "cnuda_conv2d_forward_rowquads: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    Carver cv(workspace, workspace_bytes);
-    ConvFwdParams p{g, x, nullptr, y, -1.0f, nullptr};
-    const float* A = launch_pack(weight, reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpf, q.Mpf))),
-                                 ig_a_bytes(q.Kpf, q.Mpf), Cout, C, q.T, PACK_FWD, q.Kpf, q.Mpf, 0, st);
-    return launch_fwd<ConvFwdBufQuadLoader>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward_rowquads");
+    ConvCall c("cnuda_conv2d_forward_rowquads", workspace, workspace_bytes, stream);
+    if (int rc = c.open(ConvDir::Fwd, false, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, plan_rowquads_ok,
+                        "geometry without a quad-interleaved epilogue (cnuda_conv2d_rowquads_supported)"))
+        return rc;
+    ConvFwdParams p{c.g, x, nullptr, y, -1.0f, nullptr};
+    return c.fwd_gemm<ConvFwdBufQuadLoader>(p, c.pack(weight, PACK_FWD), c.who);
 }
 
 // y = conv(x) + bias with a sigmoid on the output channels >= sig_from: the offset / mask convolution of a DCN layer when the
@@ -1585,32 +1691,21 @@ extern "C" int cnuda_conv2d_forward_rowquads(const float* x, const float* weight
 // geometries with such an epilogue compiled (C % 16 == 0, at most 32 output channels, tensors below 2 GiB, f32 matrix mode).
 extern "C" int cnuda_conv2d_rowsig_supported(int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph,
                                              int pw) {
-    ConvGeom g;
-    if (fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_rowsig_supported")) return 0;
-    const ConvPlan q = make_plan(g);
-    return (Cout <= 32 && matrix_mode() == 0 && q.fwd != FwdPath::SmallC && q.fwd_buf && q.y_buf) ? 1 : 0;
+    return plan_query(plan_rowsig_ok, "cnuda_conv2d_rowsig_supported", B, C, H, W, Cout, kh, kw, sh, sw, ph, pw);
 }
 extern "C" int cnuda_conv2d_forward_rowsig(const float* x, const float* weight, const float* bias, float* y, int sig_from,
                                            int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                                            void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
     CNUDA_REQUIRE(x && weight && y && sig_from >= 0, "cnuda_conv2d_forward_rowsig: bad arguments");
-    CNUDA_REQUIRE(cnuda_conv2d_rowsig_supported(B, C, H, W, Cout, kh, kw, sh, sw, ph, pw),
-                  "cnuda_conv2d_forward_rowsig: geometry without a row-sigmoid epilogue (cnuda_conv2d_rowsig_supported)");
-    ConvGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_forward_rowsig")) return rc;
-    const ConvPlan q = make_plan(g);
-    CNUDA_REQUIRE(workspace && workspace_bytes >= q.fwd_bytes, "cnuda_conv2d_forward_rowsig: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    Carver cv(workspace, workspace_bytes);
-    ConvFwdSigParams p;
-    static_cast<ConvFwdParams&>(p) = ConvFwdParams{g, x, bias, y, -1.0f, nullptr};
-    p.sig_from = sig_from;
-    const bool halo = q.fwd == FwdPath::Halo;
-    const float* A = launch_pack(weight, reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpf, q.Mpf))), ig_a_bytes(q.Kpf, q.Mpf),
-                                 Cout, C, q.T, halo ? PACK_HALO_FWD : PACK_FWD, q.Kpf, q.Mpf, 0, st);
-    if (halo) return launch_hconv<HconvFwdSig>(q.bmf, p, x, C, g, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward_rowsig");
-    float* slab = q.skf.on() ? reinterpret_cast<float*>(cv.take<char>(splitk_slab_bytes(q.skf, Cout, q.Nf))) : nullptr;
-    return launch_fwd<ConvFwdBufSigLoader>(q.bmf, p, A, q.Mpf, q.Kpf, Cout, q.Nf, st, "cnuda_conv2d_forward_rowsig", q.skf, slab);
+    ConvCall c("cnuda_conv2d_forward_rowsig", workspace, workspace_bytes, stream);
+    if (int rc = c.open(ConvDir::Fwd, false, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, plan_rowsig_ok,
+                        "geometry without a row-sigmoid epilogue (cnuda_conv2d_rowsig_supported)"))
+        return rc;
+    const ConvFwdSigParams p{{c.g, x, bias, y, -1.0f, nullptr}, sig_from};
+    const bool halo = c.q.fwd == FwdPath::Halo;
+    const float* A = c.pack(weight, halo ? PACK_HALO_FWD : PACK_FWD);
+    if (halo) return launch_hconv<HconvFwdSig>(c.q.bmf, p, x, C, c.g, A, c.q.Mpf, c.q.Kpf, Cout, c.q.Nf, c.st, c.who);
+    return c.fwd_gemm<ConvFwdBufSigLoader>(p, A, c.who, c.q.skf, c.splitk_slabs(c.q.skf, Cout, c.q.Nf));
 }
 
 extern "C" int cnuda_conv2d_backward_data(const float* grad_y, const float* weight, float* grad_x, int B, int C, int H,
@@ -1660,13 +1755,9 @@ extern "C" int cnuda_conv2d_backward_weight_norm_input(const float* x, const flo
                   "cnuda_conv2d_backward_weight_norm_input: geometry without an apply-on-load kernel");
     ConvGeom g;
     if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_backward_weight_norm_input")) return rc;
-    hipStream_t st = (hipStream_t)stream;
     const SmallNorm nm{mean, invstd, gamma, beta, imgs_per_group};
-    if (int rc = smallc_backward_weight(x, grad_y, grad_weight, B, C, H, W, Cout, kh, kw, sh, ph, pw, workspace, workspace_bytes,
-                                        st, &nm))
-        return rc;
-    if (grad_bias) launch_channel_sum(grad_y, grad_bias, B, Cout, (long long)g.Ho * g.Wo, st);
-    return check_launch("cnuda_conv2d_backward_weight_norm_input");
+    return wgrad_lds_tiles(g, x, grad_y, grad_weight, grad_bias, workspace, workspace_bytes, (hipStream_t)stream, &nm,
+                           "cnuda_conv2d_backward_weight_norm_input");
 }
 
 extern "C" int cnuda_conv2d_backward_data_add(const float* grad_y, const float* weight, const float* addend,
@@ -1675,123 +1766,20 @@ extern "C" int cnuda_conv2d_backward_data_add(const float* grad_y, const float* 
                                               size_t workspace_bytes, cnuda_stream_t stream) {
     if (!addend && addend2) { addend = addend2; addend2 = nullptr; }
     CNUDA_REQUIRE(grad_y && weight && grad_x, "cnuda_conv2d_backward_data: null pointer");
-    ConvGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_backward_data")) return rc;
-    // An addend that IS grad_x (the fan-in slots of hip_runtime.fanout accumulate in place) must be read before the
-    // tile is stored: the implicit-GEMM epilogues below do that per element; the LDS-tile kernels store first and add
-    // in a second pass, which would double the new gradient and lose the old content -> they take the call only when
-    // no addend aliases the output.
+    // An addend that IS grad_x (the fan-in slots of hip_runtime.fanout accumulate in place) must be read before the tile is
+    // stored: the implicit-GEMM epilogues do that per element; the LDS-tile kernels store first and add in a second pass, which
+    // would double the new gradient and lose the old content -> they take the call only when no addend aliases the output.
     const bool aliased = (addend && addend == grad_x) || (addend2 && addend2 == grad_x);
-    const ConvPlan q = make_plan(g);
-    const DgradPath path = aliased ? q.dgrad_gemm : q.dgrad;
-    if (path == DgradPath::SmallC) {
-        // (the LDS-tile kernels of the 3- / 16-channel layers have no addend: one elementwise pass behind them)
-        if (int rc = smallc_forward(grad_y, weight, nullptr, grad_x, B, Cout, g.Ho, g.Wo, C, kh, kw, 1, kh - 1 - ph,
-                                    kw - 1 - pw, -1.0f, 1, workspace, workspace_bytes, (hipStream_t)stream))
-            return rc;
-        if (addend) if (int rc = cnuda_add(grad_x, addend, grad_x, (long long)B * C * H * W, stream)) return rc;
-        return addend2 ? cnuda_add(grad_x, addend2, grad_x, (long long)B * C * H * W, stream) : 0;
+    ConvCall c("cnuda_conv2d_backward_data", workspace, workspace_bytes, stream);
+    if (int rc = c.open(ConvDir::Dgrad, aliased, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw)) return rc;
+    const DgradArgs a{grad_y, weight, addend, addend2, grad_x};
+    switch (c.dgrad()) {
+        case DgradPath::SmallC: return dgrad_lds_tiles(c, a);
+        case DgradPath::S2C16: return dgrad_s2_c16(c, a);
+        case DgradPath::Classes: case DgradPath::ClassLoop: return dgrad_classes(c, a);
+        case DgradPath::Halo: return dgrad_halo(c, a);
+        default: return dgrad_gemm(c, a);       // BufSplitK, Buf, Ptr
     }
-    CNUDA_REQUIRE(workspace && workspace_bytes >= q.dgrad_bytes, "cnuda_conv2d_backward_data: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    Carver cv(workspace, workspace_bytes);
-    float* Aws = reinterpret_cast<float*>(cv.take<char>(ig_a_bytes(q.Kpd, q.Mpd)));
-    if (path == DgradPath::S2C16) {
-        CNUDA_LAUNCH(dgrad_s2_c16_pack_kernel, dim3((Cout * 144 + 255) / 256), dim3(256), 0, st, weight, Aws, Cout);
-        DgradS2Params dp{grad_y, Aws, grad_x, addend, addend2, B, Cout, H, W, g.Ho, g.Wo, (H + 1) / 2, (W + 1) / 2};
-        ProfScope prof(st);
-        prof.name("dgrad_s2_c16_kernel");
-        CNUDA_LAUNCH(dgrad_s2_c16_kernel, dim3((dp.QW + 63) / 64, (dp.QH + 3) / 4, B), dim3(256), 0, st, dp);
-        return check_launch("cnuda_conv2d_backward_data(stride 2, 16 channels)");
-    }
-    if (path == DgradPath::Classes || path == DgradPath::ClassLoop) {
-        // (ClassLoop: one launch per class -- buffer-addressed, each with its own split-K plan, or the pointer loader)
-        const bool buf_ok = q.dgrad_buf;
-        ProfScope prof(st);   // brackets the whole class group (inner scopes find nothing armed)
-        prof.name("igemm_fwd*_kernel<*, ConvDgradClassLoader> x %d parity classes", sh * sw);
-        const long long Nc = (long long)B * (H / sh) * (W / sw);
-        ConvDgradClassParams cps[16];
-        int Kpcs[16], taps_all[16][9], ncls = 0;
-        for (int py = 0; py < sh; ++py)
-            for (int px = 0; px < sw; ++px) {
-                CNUDA_REQUIRE(ncls < 16, "cnuda_conv2d_backward_data: more than 16 parity classes");
-                ConvDgradClassParams& cp = cps[ncls];
-                cp.g = g; cp.gy = grad_y; cp.gx = grad_x; cp.py = py; cp.px = px; cp.Hc = H / sh; cp.Wc = W / sw;
-                cp.add = addend; cp.add2 = addend2;
-                cp.ntaps = 0;
-                for (int r = 0; r < kh; ++r)
-                    for (int t = 0; t < kw; ++t)
-                        if (class_tap(g, py, px, r, t)) {
-                            cp.tap_r[cp.ntaps] = r; cp.tap_s[cp.ntaps] = t; taps_all[ncls][cp.ntaps] = r * kw + t;
-                            cp.tap_dy[cp.ntaps] = (py + ph - r) / sh; cp.tap_dx[cp.ntaps] = (px + pw - t) / sw;
-                            ++cp.ntaps;
-                        }
-                Kpcs[ncls] = class_kp(cp.ntaps, Cout);
-                ++ncls;
-            }
-        if (path == DgradPath::Classes) {
-            const int bm = conv_pick_bm(C, Nc * ncls), Mp = round_up(C, bm);      // (the grid is ncls times one class's)
-            // classes in order of decreasing K: the long ones start first
-            int order[MAX_CLASSES];
-            for (int i = 0; i < ncls; ++i) order[i] = i;
-            std::stable_sort(order, order + ncls, [&](int a, int b2) { return Kpcs[a] > Kpcs[b2]; });
-            ConvDgradClassSet set;
-            size_t used = 0;
-            for (int i = 0; i < ncls; ++i) {
-                const int c = order[i];
-                const size_t bytes = carve_bytes(ig_a_bytes(Kpcs[c], Mp), 1);
-                CNUDA_REQUIRE(used + bytes + 256 <= workspace_bytes, "cnuda_conv2d_backward_data: workspace");
-                float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(Aws) + used);
-                used += bytes;
-                set.cls[i] = cps[c];
-                set.Kp[i] = Kpcs[c];
-                set.A[i] = launch_pack_taps(weight, dst, ig_a_bytes(Kpcs[c], Mp), Cout, C, q.T, taps_all[c], cps[c].ntaps, Kpcs[c], Mp, st);
-            }
-            for (int i = ncls; i < MAX_CLASSES; ++i) { set.cls[i] = set.cls[0]; set.Kp[i] = set.Kp[0]; set.A[i] = set.A[0]; }
-            CNUDA_REQUIRE(Nc < (1ll << 31) - IG_BN, "cnuda_conv2d_backward_data: more than 2^31 pixels per call");
-            const int n_tiles = ceil_div(Nc, IG_BN), m_tiles = Mp / bm;
-            const dim3 grid(n_tiles * m_tiles, ncls);
-            const bool found = (wave_specialised() && bm >= 64)
-                ? with_tile<64, 128>(bm, [&](auto BM) {
-                      CNUDA_LAUNCH((igemm_fwd_ws_classes_kernel<BM()>), grid, dim3(2 * IG_THREADS), 0, st, set, Mp, C, Nc, n_tiles, m_tiles);
-                  })
-                : with_tile<32, 64, 128>(bm, [&](auto BM) {
-                      CNUDA_LAUNCH((igemm_fwd_classes_kernel<BM()>), grid, dim3(IG_THREADS), 0, st, set, Mp, C, Nc, n_tiles, m_tiles);
-                  });
-            CNUDA_REQUIRE(found, "cnuda_conv2d_backward_data: no parity-class kernel instance for a %d-row tile", bm);
-            return check_launch("cnuda_conv2d_backward_data(classes)");
-        }
-        for (int ci = 0; ci < ncls; ++ci) {
-                const ConvDgradClassParams& cp = cps[ci];
-                const int Kpc = Kpcs[ci];
-                const int* taps = taps_all[ci];
-                const SplitK sc = buf_ok ? pick_splitk(C, Nc, Kpc) : SplitK();
-                const int bm = sc.on() ? sc.bm : conv_pick_bm(C, Nc), Mp = round_up(C, bm);
-                const size_t slab_bytes = splitk_slab_bytes(sc, C, Nc);
-                CNUDA_REQUIRE(carve_bytes(ig_a_bytes(Kpc, Mp), 1) + carve_bytes(slab_bytes, 1) + 256 <= workspace_bytes,
-                              "cnuda_conv2d_backward_data: workspace");
-                const float* A = launch_pack_taps(weight, Aws, ig_a_bytes(Kpc, Mp), Cout, C, q.T, taps, cp.ntaps, Kpc, Mp, st);
-                // (the slabs of a class behind the packed matrix -- whose room is that of the plan's largest: the same carve)
-                float* slab = sc.on() ? reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(Aws) + ig_a_bytes(Kpc, Mp) + 255) & ~(uintptr_t)255) : nullptr;
-                if (int rc = buf_ok ? launch_fwd<ConvDgradClassBufLoader>(bm, cp, A, Mp, Kpc, C, Nc, st, "cnuda_conv2d_backward_data(class)", sc, slab)
-                                    : launch_fwd<ConvDgradClassLoader>(bm, cp, A, Mp, Kpc, C, Nc, st, "cnuda_conv2d_backward_data(class)"))
-                    return rc;
-        }
-        return 0;
-    }
-    if (path == DgradPath::Halo) {
-        const float* Ah = launch_pack(weight, Aws, ig_a_bytes(q.Kpd, q.Mpd), Cout, C, q.T, PACK_HALO_DGRAD, q.Kpd, q.Mpd, 0, st);
-        ConvDgradParams ph{g, grad_y, grad_x, Cout, addend, addend2};
-        return launch_hconv<HconvDgrad>(q.bmd, ph, grad_y, Cout, g, Ah, q.Mpd, q.Kpd, C, q.Nd, st, "cnuda_conv2d_backward_data");
-    }
-    const float* A = launch_pack(weight, Aws, ig_a_bytes(q.Kpd, q.Mpd), Cout, C, q.T, PACK_DGRAD, q.Kpd, q.Mpd,
-                                 round_up(Cout, IG_BK), st);
-    ConvDgradParams p{g, grad_y, grad_x, round_up(Cout, IG_BK), addend, addend2};
-    if (path == DgradPath::BufSplitK || path == DgradPath::Buf) {
-        float* slab = q.skd.on() ? reinterpret_cast<float*>(cv.take<char>(splitk_slab_bytes(q.skd, C, q.Nd))) : nullptr;
-        return launch_fwd<ConvDgradBufLoader>(q.bmd, p, A, q.Mpd, q.Kpd, C, q.Nd, st, "cnuda_conv2d_backward_data", q.skd, slab);
-    }
-    return launch_fwd<ConvDgradLoader>(q.bmd, p, A, q.Mpd, q.Kpd, C, q.Nd, st, "cnuda_conv2d_backward_data");
 }
 
 extern "C" int cnuda_conv2d_backward_weight(const float* x, const float* grad_y, float* grad_weight, float* grad_bias,
@@ -1799,33 +1787,24 @@ extern "C" int cnuda_conv2d_backward_weight(const float* x, const float* grad_y,
                                             int ph, int pw, void* workspace, size_t workspace_bytes,
                                             cnuda_stream_t stream) {
     CNUDA_REQUIRE(x && grad_y && grad_weight, "cnuda_conv2d_backward_weight: null pointer");
-    ConvGeom g;
-    if (int rc = fill_geom(g, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, "cnuda_conv2d_backward_weight")) return rc;
-    const ConvPlan q = make_plan(g);
-    hipStream_t st = (hipStream_t)stream;
-    if (q.wgrad == WgradPath::SmallC) {
-        if (int rc = smallc_backward_weight(x, grad_y, grad_weight, B, C, H, W, Cout, kh, kw, sh, ph, pw, workspace,
-                                            workspace_bytes, st))
-            return rc;
-        if (grad_bias) launch_channel_sum(grad_y, grad_bias, B, Cout, (long long)g.Ho * g.Wo, st);
-        return check_launch("cnuda_conv2d_backward_weight(small)");
-    }
-    CNUDA_REQUIRE(workspace && workspace_bytes >= q.wgrad_bytes, "cnuda_conv2d_backward_weight: workspace too small");
-    Carver cv(workspace, workspace_bytes);
-    float* slabs = cv.take<float>((size_t)q.Z * q.Mpw * q.Jp);
-    // bias gradient: row sums of grad_y per split from the GEMM's own staging registers, summed with the slabs
-    float* bsl = grad_bias ? cv.take<float>((size_t)q.Z * q.Mpw) : nullptr;
+    ConvCall c("cnuda_conv2d_backward_weight", workspace, workspace_bytes, stream);
+    if (int rc = c.open(ConvDir::Wgrad, false, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw)) return rc;
+    const ConvGeom& g = c.g;  const ConvPlan& q = c.q;  const WgradShape& s = q.wg;  hipStream_t st = c.st;
+    if (q.wgrad == WgradPath::SmallC)
+        return wgrad_lds_tiles(g, x, grad_y, grad_weight, grad_bias, workspace, workspace_bytes, st, nullptr, "cnuda_conv2d_backward_weight(small)");
     ConvWParams p{g, x, grad_y};
-    bool found = true, lds_ok = true;
-    {
-        ProfScope prof(st);       // (the main kernel alone: closed before the slab reduce)
+    // bias gradient: row sums of grad_y per split [Z][Mpw] from the GEMM's own staging registers, summed with the slabs
+    return wgrad_then_reduce(s, c.cv, grad_bias ? (size_t)s.Z * s.Mpw : 0, grad_weight, grad_bias, Cout, C, q.T, st, 0,
+                             "cnuda_conv2d_backward_weight", "cnuda_conv2d_backward_weight(reduce)",
+                             [&](ProfScope& prof, float* slabs, float* bsl) -> int {
+        bool found = true, lds_ok = true;
         if (q.wgrad == WgradPath::HaloS2) {
             prof.name("hwgrad_s2_kernel");
             const HwS2Params hp{x, grad_y, B, C, H, W, Cout, g.Ho, g.Wo, q.hw_tiles, q.hw_tiles_per_split};
             const size_t lds = HS_LDS_FLOATS * sizeof(float);
             lds_ok = raise_dynamic_lds(reinterpret_cast<const void*>(&hwgrad_s2_kernel), lds);
             if (lds_ok)
-                CNUDA_LAUNCH(hwgrad_s2_kernel, dim3(C / 16, q.Z, (Cout + 31) / 32), dim3(IG_THREADS), lds, st, hp, slabs, q.Mpw, q.Jp, bsl);
+                CNUDA_LAUNCH(hwgrad_s2_kernel, dim3(C / 16, s.Z, (Cout + 31) / 32), dim3(IG_THREADS), lds, st, hp, slabs, s.Mpw, s.Jp, bsl);
         } else if (q.wgrad == WgradPath::Halo) {
             const int tw = halo_tile_width(W);
             const bool side = tw < W;           // (tiles with neighbours in their row)
@@ -1836,32 +1815,21 @@ extern "C" int cnuda_conv2d_backward_weight(const float* x, const float* grad_y,
                 constexpr bool kSide = SIDE() != 0;
                 const size_t lds = HwShape<TW(), kSide>::lds_floats * sizeof(float);
                 lds_ok = raise_dynamic_lds(reinterpret_cast<const void*>(&hwgrad_kernel<TW(), kSide>), lds);
-                if (lds_ok) CNUDA_LAUNCH((hwgrad_kernel<TW(), kSide>), dim3(C / 16, q.Z), dim3(IG_THREADS), lds, st, hp, slabs, q.Mpw, q.Jp, bsl);
+                if (lds_ok) CNUDA_LAUNCH((hwgrad_kernel<TW(), kSide>), dim3(C / 16, s.Z), dim3(IG_THREADS), lds, st, hp, slabs, s.Mpw, s.Jp, bsl);
             });
         } else {
             prof.name(q.wgrad_ws ? "igemm_wgrad_ws_kernel<%s, %d, %d>" : "igemm_wgrad_kernel<%s, %d, %d>", wgrad_loader_name(q.wgrad),
-                      q.wbm, q.wbj);
+                      s.bm, s.bj);
             switch (q.wgrad) {
-                case WgradPath::BufC8:
-                    found = launch_wgrad<ConvWBufLoaderC8, false, Tile<32, 128>, Tile<64, 64>>(q, p, slabs, bsl, st);
-                    break;
-                case WgradPath::Buf:
-                    found = launch_wgrad_buf<ConvWBufLoader>(q, p, slabs, bsl, st);
-                    break;
-                case WgradPath::PtrFastWs:
-                    found = launch_wgrad<ConvWLoader<2>, true, Tile<64, 128>, Tile<64, 64>>(q, p, slabs, bsl, st);
-                    break;
-                case WgradPath::PtrFast:
-                    found = launch_wgrad<ConvWLoader<2>, false, Tile<64, 128>, Tile<64, 64>, Tile<32, 128>>(q, p, slabs, bsl, st);
-                    break;
-                default:
-                    found = launch_wgrad<ConvWLoader<0>, false, Tile<64, 64>, Tile<32, 128>>(q, p, slabs, bsl, st);
+                case WgradPath::BufC8: found = launch_wgrad<ConvWBufLoaderC8, false, Tile<32, 128>, Tile<64, 64>>(s, p, slabs, bsl, st); break;
+                case WgradPath::Buf: found = launch_wgrad_buf<ConvWBufLoader>(q, p, slabs, bsl, st); break;
+                case WgradPath::PtrFastWs: found = launch_wgrad<ConvWLoader<2>, true, Tile<64, 128>, Tile<64, 64>>(s, p, slabs, bsl, st); break;
+                case WgradPath::PtrFast: found = launch_wgrad<ConvWLoader<2>, false, Tile<64, 128>, Tile<64, 64>, Tile<32, 128>>(s, p, slabs, bsl, st); break;
+                default: found = launch_wgrad<ConvWLoader<0>, false, Tile<64, 64>, Tile<32, 128>>(s, p, slabs, bsl, st);
             }
         }
-    }
-    CNUDA_REQUIRE(lds_ok, "cnuda_conv2d_backward_weight: dynamic LDS");
-    CNUDA_REQUIRE(found, "cnuda_conv2d_backward_weight: no kernel instance for this tile (%d x %d)", q.wbm, q.wbj);
-    if (int rc = check_launch("cnuda_conv2d_backward_weight")) return rc;
-    launch_slab_reduce(slabs, grad_weight, q.Z, q.Mpw, q.Jp, Cout, C, q.T, st, bsl, grad_bias);
-    return check_launch("cnuda_conv2d_backward_weight(reduce)");
+        CNUDA_REQUIRE(lds_ok, "cnuda_conv2d_backward_weight: dynamic LDS");
+        CNUDA_REQUIRE(found, "cnuda_conv2d_backward_weight: no kernel instance for this tile (%d x %d)", s.bm, s.bj);
+        return 0;
+    });
 }

@@ -1556,11 +1556,10 @@ struct DcnPlan {
     bool fwd_buf;                   // SampleThenGemm / Gather: the buffer-addressed loader
     bool fwd_ws;                    // SampleThenGemm: the GEMM's wave-specialised instance
     bool colw_buf, colw_ws;         // weight gradient from saved columns: buffer-addressed loader, wave-specialised instance
-    int wbj;                        // ... and its column tile (rows: WG_BM)
     bool dcol_quads;                // column gradient with its rows interleaved in quads (both consumers read 16 bytes)
     int T, K, Kp, bm, Mp;           // forward pack [Kp][Mp]
-    int Mpw, Jp, Z;                 // wgrad slabs [Z][Mpw][Jp]
-    long long N, pix_per_split;
+    WgradShape wg;                  // wgrad slabs and tile: WG_BM rows x the column tile of the saved-columns loaders
+    long long N;
     size_t fwd_bytes, bwd_bytes;
     bool fwd_two_kernels;           // several M tiles: sample the columns once, then a plain GEMM
     // split backward: 1x1 GEMM workspace, transposed weights, dcol, geometry records; col2im tiling
@@ -1578,15 +1577,8 @@ DcnPlan make_plan(const DcnGeom& g) {
     q.N = (long long)g.B * g.Ho * g.Wo;
     q.bm = dcn_pick_bm(g.Co, q.N);
     q.Mp = round_up(g.Co, q.bm);
-    q.Mpw = round_up(g.Co, WG_BM);
-    q.Jp = round_up(q.K, WG_BJ);
-    q.N = (long long)g.B * g.Ho * g.Wo;
-    // enough pixel splits to fill the chip (>= ~1024 workgroups), each a multiple of the chunk
-    q.wbj = q.Jp % 128 == 0 ? 128 : WG_BJ;             // (of the saved-columns loaders; the sampling loader has 64 x 64 alone)
-    const long long tiles = (long long)(q.Mpw / WG_BM) * (q.Jp / q.wbj);
-    const long long z = wgrad_splits(tiles, WG_BM, q.wbj, (q.N + WG_BP - 1) / WG_BP);
-    q.pix_per_split = ((q.N + z - 1) / z + WG_BP - 1) / WG_BP * WG_BP;
-    q.Z = (int)((q.N + q.pix_per_split - 1) / q.pix_per_split);
+    // (128-column tiles where the 64-column ones pair up; the sampling loader has 64 x 64 alone and runs it on the same splits)
+    q.wg = make_wgrad_shape(g.Co, q.K, q.N, WG_BM, round_up(q.K, WG_BJ) % 128 == 0 ? 128 : WG_BJ, WG_BP);
     q.fwd_two_kernels = q.Mp / q.bm > 1;
     q.fwd_bytes = carve_bytes((size_t)q.Kp * q.Mp, 4) + 256 +
                   (q.fwd_two_kernels ? carve_bytes((size_t)g.B * q.K * g.Ho * g.Wo, 4) : 0);
@@ -1595,8 +1587,8 @@ DcnPlan make_plan(const DcnGeom& g) {
         if (wb > q.fwd_bytes) q.fwd_bytes = wb;
     }
     q.gemm_bytes = cnuda_conv2d_workspace_bytes(g.B, g.Co, g.Ho, g.Wo, q.T * g.C, 1, 1, 1, 1, 0, 0);
-    q.bwd_bytes = carve_bytes((size_t)q.Z * q.Mpw * q.Jp, 4) +
-                  carve_bytes(std::max((size_t)g.Co * g.B, (size_t)q.Z * q.Mpw), 4) +
+    q.bwd_bytes = carve_bytes((size_t)q.wg.Z * q.wg.Mpw * q.wg.Jp, 4) +
+                  carve_bytes(std::max((size_t)g.Co * g.B, (size_t)q.wg.Z * q.wg.Mpw), 4) +
                   carve_bytes((size_t)12 * g.C * (g.Co < 64 ? 64 : g.Co), 4) +
                   carve_bytes((size_t)g.B * q.T * g.C * g.Ho * g.Wo, 4) +
                   carve_bytes((size_t)g.B * q.T * g.Ho * g.Wo, sizeof(DcnGeo)) + carve_bytes(q.gemm_bytes, 1) + 256;
@@ -1699,17 +1691,6 @@ bool launch_dcn_fwd(const DcnPlan& q, const P& p, const float* A, int Cout, hipS
         return with_tile<32, 64, 128>(q.bm, [&](auto BM) {
             CNUDA_LAUNCH((igemm_fwd_kernel<BM(), Loader>), grid, dim3(IG_THREADS), 0, st, p, A, q.Mp, q.Kp, Cout, q.N, n_tiles, m_tiles);
         });
-}
-// the weight-gradient GEMM of one loader on the 64-row tile: BJS lists its column tiles
-template <class Loader, bool WS, int... BJS, class P>
-bool launch_dcn_wgrad(const DcnPlan& q, int bj, const P& p, float* slabs, float* bsl, hipStream_t st) {
-    const dim3 grid(q.Jp / bj, q.Mpw / WG_BM, q.Z), blk((WS ? 2 : 1) * IG_THREADS);
-    return with_tile<BJS...>(bj, [&](auto BJ) {
-        if constexpr (WS)
-            CNUDA_LAUNCH((igemm_wgrad_ws_kernel<Loader, 64, BJ()>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
-        else
-            CNUDA_LAUNCH((igemm_wgrad_kernel<Loader, 64, BJ()>), grid, blk, 0, st, p, slabs, q.Mpw, q.Jp, q.N, q.pix_per_split, bsl);
-    });
 }
 
 }  // namespace
@@ -2059,40 +2040,37 @@ static int dcn_backward_impl(const DcnBwdCall& c, const DcnPlan& q) {
     }
     CNUDA_REQUIRE(c.workspace && c.workspace_bytes >= q.bwd_bytes, "cnuda_dcn_v2_backward: workspace too small");
     Carver cv(c.workspace, c.workspace_bytes);
-    float* slabs = cv.take<float>((size_t)q.Z * q.Mpw * q.Jp);
-    float* bsl = cv.take<float>(std::max((size_t)g.Co * g.B, (size_t)q.Z * q.Mpw));    // bias row sums per split: [Z][Mpw]
+    // every timed scope below is recorded under the call's tag; sub 0: the column-gradient 1x1 GEMM (its own scope
+    // inside cnuda_conv2d_forward), 1: coord_grad, 2: col2im, 3: both as one launch, 4: the weight-gradient GEMM
+    ProfGroup prof;
+    // (2) weight gradient (and, from the same staging registers, the bias gradient: row sums per split [Z][Mpw] -> slab reduce)
+    // (running it on a second stream beside the data-gradient chain was tried in round 2: the kernels do overlap but
+    // contend for the same LDS / issue slots -- nothing gained, removed)
+    if (int rc = wgrad_then_reduce(
+            q.wg, cv, std::max((size_t)g.Co * g.B, (size_t)q.wg.Z * q.wg.Mpw), c.grad_weight, c.grad_bias, g.Co, g.C, q.T, st, 4,
+            "cnuda_dcn_v2_backward(weight)", "cnuda_dcn_v2_backward(weight reduce)", [&](ProfScope& wscope, float* slabs, float* bsl) -> int {
+                bool found;
+                if (c.columns) {
+                    DcnColWParams p{g, c.columns, c.grad_output};
+                    wscope.name(q.colw_ws ? "igemm_wgrad_ws_kernel<%s, 64, %d>" : "igemm_wgrad_kernel<%s, 64, %d>",
+                                q.colw_buf ? "DcnColWBufLoader" : "DcnColWLoader", q.wg.bj);
+                    found = q.colw_ws    ? launch_wgrad<DcnColWBufLoader, true, Tile<64, 64>, Tile<64, 128>>(q.wg, p, slabs, bsl, st)
+                            : q.colw_buf ? launch_wgrad<DcnColWBufLoader, false, Tile<64, 64>, Tile<64, 128>>(q.wg, p, slabs, bsl, st)
+                                         : launch_wgrad<DcnColWLoader, false, Tile<64, 64>, Tile<64, 128>>(q.wg, p, slabs, bsl, st);
+                } else {
+                    DcnWParams p{g, c.input, c.offset, c.mask, c.grad_output};
+                    wscope.name("igemm_wgrad_kernel<DcnWLoader, 64, 64>");
+                    WgradShape s = q.wg;  s.bj = WG_BJ;      // (64-column tiles over the same slabs and splits)
+                    found = launch_wgrad<DcnWLoader, false, Tile<64, 64>>(s, p, slabs, bsl, st);
+                }
+                CNUDA_REQUIRE(found, "cnuda_dcn_v2_backward: no weight-gradient instance for %d-column tiles", q.wg.bj);
+                return 0;
+            }))
+        return rc;
     float* wt = cv.take<float>((size_t)12 * g.C * (g.Co < 64 ? 64 : g.Co));   // (or the window kernels' packs: [64][10 C], [12 C][64])
     float* dcol = cv.take<float>((size_t)g.B * q.T * g.C * HoWo);
     DcnGeo* geo = cv.take<DcnGeo>((size_t)g.B * q.T * HoWo);
     void* gemm_ws = cv.take<char>(q.gemm_bytes);
-    // (running the weight gradient on a second stream beside the data-gradient chain was tried in round 2: the
-    // kernels do overlap but contend for the same LDS / issue slots -- nothing gained, removed)
-    hipStream_t wst = st;
-    // every timed scope below is recorded under the call's tag; sub 0: the column-gradient 1x1 GEMM (its own scope
-    // inside cnuda_conv2d_forward), 1: coord_grad, 2: col2im, 3: both as one launch, 4: the weight-gradient GEMM
-    ProfGroup prof;
-    // (2) weight gradient (and, from the same staging registers, the bias gradient: bsl -> slab reduce)
-    {
-      bool found;
-      {
-        ProfScope wscope(st, 4);
-        if (c.columns) {
-            DcnColWParams p{g, c.columns, c.grad_output};
-            wscope.name(q.colw_ws ? "igemm_wgrad_ws_kernel<%s, 64, %d>" : "igemm_wgrad_kernel<%s, 64, %d>",
-                        q.colw_buf ? "DcnColWBufLoader" : "DcnColWLoader", q.wbj);
-            found = q.colw_ws    ? launch_dcn_wgrad<DcnColWBufLoader, true, 64, 128>(q, q.wbj, p, slabs, bsl, wst)
-                    : q.colw_buf ? launch_dcn_wgrad<DcnColWBufLoader, false, 64, 128>(q, q.wbj, p, slabs, bsl, wst)
-                                 : launch_dcn_wgrad<DcnColWLoader, false, 64, 128>(q, q.wbj, p, slabs, bsl, wst);
-        } else {
-            DcnWParams p{g, c.input, c.offset, c.mask, c.grad_output};
-            wscope.name("igemm_wgrad_kernel<DcnWLoader, 64, 64>");
-            found = launch_dcn_wgrad<DcnWLoader, false, 64>(q, WG_BJ, p, slabs, bsl, wst);
-        }
-      }
-        CNUDA_REQUIRE(found, "cnuda_dcn_v2_backward: no weight-gradient instance for %d-column tiles", q.wbj);
-        if (int rc = check_launch("cnuda_dcn_v2_backward(weight)")) return rc;
-        launch_slab_reduce(slabs, c.grad_weight, q.Z, q.Mpw, q.Jp, g.Co, g.C, q.T, wst, bsl, c.grad_bias);
-    }
     {
         // (1) dcol = W^T x grad_output as a 1x1 implicit GEMM, then the two streaming consumers
         {

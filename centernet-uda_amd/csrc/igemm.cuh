@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <utility>
 #include "common.h"
+#include "igemm_host.h"
 
 namespace cnuda {
 
@@ -1154,6 +1155,35 @@ __global__ __launch_bounds__(2 * IG_THREADS) void igemm_wgrad_ws_kernel(
         cur ^= 1;
     }
     ig_wgrad_store_slab<BM, BJ>(slabs, acc, Mp, Jp, m0, j0, wm_off, wj_off, lane);
+}
+
+// ---- host side of the weight gradient (conv.hip, dcn.hip).  The GEMM of one loader into the slabs of `s`: `Tiles` lists the
+// (row, column) tile shapes compiled for it, WS picks the wave-specialised kernel.  false: the shape's tile is not among them.
+template <class Loader, bool WS, class... Tiles, class P>
+bool launch_wgrad(const WgradShape& s, const P& p, float* slabs, float* bsl, hipStream_t st) {
+    const dim3 grid(s.Jp / s.bj, s.Mpw / s.bm, s.Z), blk((WS ? 2 : 1) * IG_THREADS);
+    return with_tiles<Tiles...>(s.bm, s.bj, [&](auto BM, auto BJ) {
+        if constexpr (WS)
+            CNUDA_LAUNCH((igemm_wgrad_ws_kernel<Loader, BM(), BJ()>), grid, blk, 0, st, p, slabs, s.Mpw, s.Jp, s.N, s.pix_per_split, bsl);
+        else
+            CNUDA_LAUNCH((igemm_wgrad_kernel<Loader, BM(), BJ()>), grid, blk, 0, st, p, slabs, s.Mpw, s.Jp, s.N, s.pix_per_split, bsl);
+    });
+}
+
+// A whole weight gradient: slabs and -- bias_floats > 0 -- the per-split row sums of grad_y carved from the workspace; main(prof,
+// slabs, bsl) names its ProfScope (the main kernel alone) and launches what fills them; then the fixed-order reduce into gw (, gb).
+template <class Main>
+int wgrad_then_reduce(const WgradShape& s, Carver& cv, size_t bias_floats, float* gw, float* gb, int Co, int C, int T,
+                      hipStream_t st, int prof_sub, const char* who, const char* who_reduce, Main&& main) {
+    float* slabs = cv.take<float>((size_t)s.Z * s.Mpw * s.Jp);
+    float* bsl = bias_floats ? cv.take<float>(bias_floats) : nullptr;
+    {
+        ProfScope prof(st, prof_sub);
+        if (int rc = main(prof, slabs, bsl)) return rc;
+    }
+    if (int rc = check_launch(who)) return rc;
+    launch_slab_reduce(slabs, gw, s.Z, s.Mpw, s.Jp, Co, C, T, st, bsl, gb);
+    return check_launch(who_reduce);
 }
 
 }  // namespace cnuda

@@ -53,6 +53,17 @@ inline long long wgrad_splits(long long tiles, int bm, int bj, long long max_z) 
     if (z > max_z) z = max_z;
     return z < 1 ? 1 : z;
 }
+// Slabs and grid of a weight-gradient GEMM (igemm.cuh launch_wgrad): [Z] slabs of [Mpw][Jp] in bm x bj tiles, the N pixels cut
+// into Z splits of pix_per_split -- whole chunks of `chunk` pixels (WG_BP).  ConvPlan and DcnPlan each hold one.
+struct WgradShape { int Mpw, Jp, Z, bm, bj; long long N, pix_per_split; };
+inline WgradShape make_wgrad_shape(int M, int J, long long N, int bm, int bj, int chunk) {
+    WgradShape s{round_up(M, bm), round_up(J, bj), 0, bm, bj, N, 0};
+    const long long tiles = (long long)(s.Mpw / bm) * (s.Jp / bj);
+    const long long z = wgrad_splits(tiles, bm, bj, (N + chunk - 1) / chunk);
+    s.pix_per_split = ((N + z - 1) / z + chunk - 1) / chunk * chunk;
+    s.Z = (int)((N + s.pix_per_split - 1) / s.pix_per_split);
+    return s;
+}
 
 // W is the reference layout [Co][C][T] (T = kh*kw).  The packed image is [Kp][Mp], zero padded.  Returns the
 // buffer the GEMM must read: `dst` (the caller's workspace, freshly packed) or -- when the caller announced a

@@ -47,6 +47,63 @@ def _conv_geom(x, weight, stride, padding):
     return (B, C, H, W, Co, kh, kw, sh, sw, ph, pw)
 
 
+# One launch core per direction: workspace, prof_arm, pack_stamp (token 0: none) and check around the C-ABI call of geometry g.
+def _conv_forward(g, x, weight, bias, act_slope=-1.0, token=0, version=None, residual=None, stats_box=None, sig_from=None,
+                  norm=None, what='conv2d_forward'):
+    """-> y.  The epilogue by keyword: residual (added before the activation), stats_box (BatchNorm statistics of y where
+    this geometry's kernel leaves them: the record is appended), sig_from (sigmoid on the channels from there on), norm
+    (x_raw, mean, invstd, gamma, beta, imgs_per_group: apply on load -- `x` is then only the placeholder's shape)."""
+    B, C, H, W, Co, kh, kw, sh, sw, ph, pw = g
+    Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    y = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=x.device)
+    L = lib()
+    wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), x)
+    stats = None
+    if stats_box is not None:
+        rec = stats_side_output(stats_box, L.cnuda_conv2d_stats_block, g, Ho * Wo, x.device, per_image=True)
+        stats = rec and rec[0]
+    prof_arm('conv_fwd', B, C, H, W, Co, kh, kw, Ho, Wo)
+    with pack_stamp(token, weight, version):
+        if norm is not None:
+            check(L.cnuda_conv2d_forward_norm_input(*[ptr(t) for t in norm[:5]], int(norm[5]), ptr(weight), ptr(bias), ptr(y),
+                                                    ptr(stats), *g, float(act_slope), wp, wn, stream()),
+                  'conv2d_forward_norm_input')
+        elif sig_from is not None:
+            check(L.cnuda_conv2d_forward_rowsig(ptr(x), ptr(weight), ptr(bias), ptr(y), int(sig_from), *g, wp, wn, stream()),
+                  'conv2d_forward_rowsig')
+        else:
+            check(L.cnuda_conv2d_forward_stats(ptr(x), ptr(weight), ptr(bias), ptr(residual), ptr(y), ptr(stats), *g,
+                                               float(act_slope), wp, wn, stream()), what)
+    return y
+
+
+def _conv_dgrad(g, gy, weight, out, addend=None, addend2=None, token=0, what='conv2d_backward_data'):
+    """out = input gradient (+ addend + addend2: other consumers' shares, either may BE out) -> out"""
+    L = lib()
+    wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), gy)
+    prof_arm('conv_dgrad', *g[:7], gy.shape[2], gy.shape[3])
+    with pack_stamp(token, weight):
+        check(L.cnuda_conv2d_backward_data_add(ptr(gy), ptr(weight), ptr(addend), ptr(addend2), ptr(out), *g, wp, wn,
+                                               stream()), what)
+    return out
+
+
+def _conv_wgrad(g, x, gy, weight, bias=None, norm=None, what='conv2d_backward_weight'):
+    """-> (gw, gb) as autograd takes them (_param_grad).  norm: (mean, invstd, gamma, beta, imgs_per_group) when `x` is the raw
+    input of a deferred BatchNorm + ReLU, normalised again while it is staged."""
+    gw_buf, gw = _param_grad(weight)
+    gb_buf, gb = _param_grad(bias)
+    L = lib()
+    wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), x)
+    prof_arm('conv_wgrad', *g[:7], gy.shape[2], gy.shape[3])
+    if norm is not None:
+        check(L.cnuda_conv2d_backward_weight_norm_input(ptr(x), *[ptr(t) for t in norm[:4]], int(norm[4]), ptr(gy), ptr(gw_buf),
+                                                        ptr(gb_buf), *g, wp, wn, stream()), 'conv2d_backward_weight_norm_input')
+    else:
+        check(L.cnuda_conv2d_backward_weight(ptr(x), ptr(gy), ptr(gw_buf), ptr(gb_buf), *g, wp, wn, stream()), what)
+    return gw, gb
+
+
 class _Conv2d(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding, act_slope, pack_token=0, stats_box=None, norm=None, sig_from=None):
@@ -64,32 +121,9 @@ class _Conv2d(Function):
         x, weight = (x if norm is not None else f32c(x)), f32c(weight)
         bias = None if bias is None else f32c(bias)
         g = _conv_geom(x, weight, stride, padding)
-        B, C, H, W, Co, kh, kw, sh, sw, ph, pw = g
-        Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
-        y = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=x.device)
-        L = lib()
-        wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), x)
-        stats = None
-        if stats_box is not None and act_slope < 0:
-            # BatchNorm statistics of y from the GEMM's epilogue, where this geometry's kernel can give them
-            rec = stats_side_output(stats_box, L.cnuda_conv2d_stats_block, g, Ho * Wo, x.device, per_image=True)
-            stats = rec and rec[0]
-        prof_arm('conv_fwd', B, C, H, W, Co, kh, kw, Ho, Wo)
-        with pack_stamp(pack_token, weight):
-            if norm is not None:
-                xr, mean, invstd, gamma, beta, ipg = norm
-                check(L.cnuda_conv2d_forward_norm_input(ptr(xr), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), int(ipg),
-                                                        ptr(weight), ptr(bias), ptr(y), ptr(stats), *g, float(act_slope),
-                                                        wp, wn, stream()), 'conv2d_forward_norm_input')
-            elif sig_from is not None:
-                check(L.cnuda_conv2d_forward_rowsig(ptr(x), ptr(weight), ptr(bias), ptr(y), int(sig_from), *g, wp, wn, stream()),
-                      'conv2d_forward_rowsig')
-            elif stats is None:
-                check(L.cnuda_conv2d_forward(ptr(x), ptr(weight), ptr(bias), ptr(y), *g, float(act_slope),
-                                             wp, wn, stream()), 'conv2d_forward')
-            else:
-                check(L.cnuda_conv2d_forward_stats(ptr(x), ptr(weight), ptr(bias), ptr(None), ptr(y), ptr(stats), *g,
-                                                   float(act_slope), wp, wn, stream()), 'conv2d_forward_stats')
+        # (BatchNorm statistics of y from the GEMM's epilogue, where this geometry's kernel can give them)
+        y = _conv_forward(g, x, weight, bias, act_slope, pack_token, stats_box=stats_box if act_slope < 0 else None,
+                          sig_from=sig_from, norm=norm)
         ctx.geom, ctx.act_slope, ctx.has_bias, ctx.pack_token = g, act_slope, bias is not None, pack_token
         ctx.norm_ipg = None
         if norm is not None:
@@ -105,34 +139,18 @@ class _Conv2d(Function):
     def backward(ctx, gy):
         x, weight, y, bias = ctx.saved_tensors[:4]
         g = ctx.geom
-        L = lib()
         gy = f32c(gy)
         if ctx.act_slope >= 0:
             t = torch.empty_like(gy)
-            check(L.cnuda_act_backward(ptr(gy), ptr(y), ptr(t), gy.numel(), float(ctx.act_slope), stream()))
+            check(lib().cnuda_act_backward(ptr(gy), ptr(y), ptr(t), gy.numel(), float(ctx.act_slope), stream()))
             gy = t
-        wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), x)
         gx = gw = gb = None
-        B, C, H, W, Co, kh, kw = g[:7]
-        Ho, Wo = gy.shape[2], gy.shape[3]
         if ctx.needs_input_grad[0]:
             gx, addend, addend2 = accumulate_target(ctx.slot, x)     # the slots' content is summed in the GEMM's epilogue
-            prof_arm('conv_dgrad', B, C, H, W, Co, kh, kw, Ho, Wo)
-            with pack_stamp(ctx.pack_token, weight):
-                check(L.cnuda_conv2d_backward_data_add(ptr(gy), ptr(weight), ptr(addend), ptr(addend2), ptr(gx), *g, wp, wn,
-                                                       stream()), 'conv2d_backward_data')
+            _conv_dgrad(g, gy, weight, gx, addend, addend2, ctx.pack_token)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gw_buf, gw = _param_grad(weight)
-            gb_buf, gb = _param_grad(bias, ctx.has_bias)
-            prof_arm('conv_wgrad', B, C, H, W, Co, kh, kw, Ho, Wo)
-            if ctx.norm_ipg is not None:
-                mean, invstd, gamma, beta = ctx.saved_tensors[4:]
-                check(L.cnuda_conv2d_backward_weight_norm_input(ptr(x), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta),
-                                                                ctx.norm_ipg, ptr(gy), ptr(gw_buf), ptr(gb_buf), *g, wp, wn,
-                                                                stream()), 'conv2d_backward_weight_norm_input')
-            else:
-                check(L.cnuda_conv2d_backward_weight(ptr(x), ptr(gy), ptr(gw_buf), ptr(gb_buf), *g, wp, wn, stream()),
-                      'conv2d_backward_weight')
+            norm = None if ctx.norm_ipg is None else (*ctx.saved_tensors[4:], ctx.norm_ipg)
+            gw, gb = _conv_wgrad(g, x, gy, weight, bias, norm)
         return gx, gw, gb, None, None, None, None, None, None, None
 
 
@@ -195,23 +213,9 @@ class _ConvActConv1x1(Function):
         b1 = None if b1 is None else f32c(b1)
         b2 = None if b2 is None else f32c(b2)
         g1 = _conv_geom(x, w1, 1, padding)
-        B, C, H, W, Ch, kh, kw, sh, sw, ph, pw = g1
-        Ho, Wo = H + 2 * ph - kh + 1, W + 2 * pw - kw + 1
-        hidden = torch.empty((B, Ch, Ho, Wo), dtype=torch.float32, device=x.device)
-        L = lib()
-        wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g1), x)
-        prof_arm('conv_fwd', B, C, H, W, Ch, kh, kw, Ho, Wo)
-        with pack_stamp(token1, w1):
-            check(L.cnuda_conv2d_forward(ptr(x), ptr(w1), ptr(b1), ptr(hidden), *g1, float(act_slope), wp, wn, stream()),
-                  'conv2d_forward')
+        hidden = _conv_forward(g1, x, w1, b1, act_slope, token1)
         g2 = _conv_geom(hidden, w2, 1, 0)
-        Co = g2[4]
-        y = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=x.device)
-        wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g2), x)
-        prof_arm('conv_fwd', B, Ch, Ho, Wo, Co, 1, 1, Ho, Wo)
-        with pack_stamp(token2, w2):
-            check(L.cnuda_conv2d_forward(ptr(hidden), ptr(w2), ptr(b2), ptr(y), *g2, -1.0, wp, wn, stream()),
-                  'conv2d_forward')
+        y = _conv_forward(g2, hidden, w2, b2, -1.0, token2)
         ctx.g1, ctx.g2, ctx.act_slope, ctx.token1 = g1, g2, float(act_slope), token1
         ctx.has_b1, ctx.has_b2 = b1 is not None, b2 is not None
         ctx.save_for_backward(x, w1, b1, w2, b2, hidden)
@@ -226,22 +230,14 @@ class _ConvActConv1x1(Function):
         gy = f32c(gy)
         if gy.data_ptr() % 16:                 # (a view at an odd offset: the fused pass reads 16 bytes at a time)
             gy = gy.clone()
-        B, C, H, W, Ch, kh, kw = g1[:7]
-        Co, Ho, Wo = g2[4], hidden.shape[2], hidden.shape[3]
+        B, Ch, Co = g1[0], g1[4], g2[4]
         gx = gw1 = gb1 = gw2 = gb2 = None
         if ctx.needs_input_grad[3] or (ctx.has_b2 and ctx.needs_input_grad[4]):
-            gw2_buf, gw2 = _param_grad(w2)
-            gb2_buf, gb2 = _param_grad(b2, ctx.has_b2)
-            wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g2), x)
-            prof_arm('conv_wgrad', B, Ch, Ho, Wo, Co, 1, 1, Ho, Wo)
-            check(L.cnuda_conv2d_backward_weight(ptr(hidden), ptr(gy), ptr(gw2_buf), ptr(gb2_buf), *g2, wp, wn, stream()),
-                  'conv2d_backward_weight')
+            gw2, gb2 = _conv_wgrad(g2, hidden, gy, w2, b2)
         gh = torch.empty_like(hidden)
-        check(L.cnuda_conv1x1_backward_data_act(ptr(gy), ptr(w2), ptr(hidden), ptr(gh), B, Co, Ch, Ho * Wo,
+        check(L.cnuda_conv1x1_backward_data_act(ptr(gy), ptr(w2), ptr(hidden), ptr(gh), B, Co, Ch, hidden.shape[2] * hidden.shape[3],
                                                 ctx.act_slope, stream()), 'conv1x1_backward_data_act')
-        wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g1), x)
         if ctx.needs_input_grad[0]:
-            prof_arm('conv_dgrad', B, C, H, W, Ch, kh, kw, Ho, Wo)
             slot = ctx.slot
             if ctx.full is None:
                 gx, addend, addend2 = accumulate_target(slot, x)
@@ -253,15 +249,9 @@ class _ConvActConv1x1(Function):
                 gx = claim(slot, torch.empty(ctx.full, dtype=torch.float32, device=x.device))
                 gx[B:].zero_()
                 part, addend, addend2 = gx[:B], None, None
-            with pack_stamp(ctx.token1, w1):
-                check(L.cnuda_conv2d_backward_data_add(ptr(gh), ptr(w1), ptr(addend), ptr(addend2), ptr(part), *g1, wp, wn,
-                                                       stream()), 'conv2d_backward_data')
+            _conv_dgrad(g1, gh, w1, part, addend, addend2, ctx.token1)
         if ctx.needs_input_grad[1] or (ctx.has_b1 and ctx.needs_input_grad[2]):
-            gw1_buf, gw1 = _param_grad(w1)
-            gb1_buf, gb1 = _param_grad(b1, ctx.has_b1)
-            prof_arm('conv_wgrad', B, C, H, W, Ch, kh, kw, Ho, Wo)
-            check(L.cnuda_conv2d_backward_weight(ptr(x), ptr(gh), ptr(gw1_buf), ptr(gb1_buf), *g1, wp, wn, stream()),
-                  'conv2d_backward_weight')
+            gw1, gb1 = _conv_wgrad(g1, x, gh, w1, b1)
         return gx, gw1, gb1, gw2, gb2, None, None, None, None, None
 
 
@@ -298,14 +288,7 @@ def conv2d_infer(x, weight, bias=None, stride=1, padding=0, act_slope=-1.0, resi
         if tuple(residual.shape) != (B, Co, Ho, Wo):
             raise RuntimeError("conv2d_infer: residual %s does not match the output %s"
                                % (tuple(residual.shape), (B, Co, Ho, Wo)))
-    y = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=x.device)
-    L = lib()
-    wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), x)
-    prof_arm('conv_fwd', B, C, H, W, Co, kh, kw, Ho, Wo)
-    with pack_stamp(pack_token, weight, pack_version):
-        check(L.cnuda_conv2d_forward_res(ptr(x), ptr(weight), ptr(bias), ptr(residual), ptr(y), *g, float(act_slope),
-                                         wp, wn, stream()), 'conv2d_forward')
-    return y
+    return _conv_forward(g, x, weight, bias, act_slope, pack_token, pack_version, residual=residual)
 
 
 class _ConvTranspose2d(Function):
@@ -330,36 +313,21 @@ class _ConvTranspose2d(Function):
             raise RuntimeError("conv_transpose2d: output_padding %s inconsistent with stride %s" %
                                ((oph, opw), (sh, sw)))
         y = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=x.device)
-        L = lib()
-        wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), x)
-        prof_arm('conv_dgrad', B, Co, Ho, Wo, Ci, kh, kw, H, W)
-        check(L.cnuda_conv2d_backward_data(ptr(x), ptr(weight), ptr(y), *g, wp, wn, stream()),
-              'conv_transpose2d(forward)')
         ctx.geom = g
         ctx.save_for_backward(x, weight)
-        return y
+        return _conv_dgrad(g, x, weight, y, what='conv_transpose2d(forward)')
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
         g = ctx.geom
-        B, Co, Ho, Wo, Ci, kh, kw = g[:7]
-        H, W = x.shape[2], x.shape[3]
         gy = f32c(gy)
-        L = lib()
-        wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), x)
         gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            prof_arm('conv_fwd', B, Co, Ho, Wo, Ci, kh, kw, H, W)
-            check(L.cnuda_conv2d_forward(ptr(gy), ptr(weight), None, ptr(gx), *g, -1.0, wp, wn, stream()),
-                  'conv_transpose2d(backward data)')
+        if ctx.needs_input_grad[0]:       # (the convolution's forward over gy: its output has x's shape)
+            gx = _conv_forward(g, gy, weight, None, what='conv_transpose2d(backward data)')
         if ctx.needs_input_grad[1]:
-            gw_buf, gw = _param_grad(weight)
-            prof_arm('conv_wgrad', B, Co, Ho, Wo, Ci, kh, kw, H, W)
-            check(L.cnuda_conv2d_backward_weight(ptr(gy), ptr(x), ptr(gw_buf), None, *g, wp, wn, stream()),
-                  'conv_transpose2d(backward weight)')
+            gw, _ = _conv_wgrad(g, gy, x, weight, what='conv_transpose2d(backward weight)')
         return gx, gw, None, None, None
 
 
@@ -837,6 +805,26 @@ def _ptr_array(ts):
     return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
 
 
+def _cat_forward(xs, weight, bias, act_slope, token, version=None, stats_box=None):
+    """One cnuda_conv2d_cat_forward launch over the sources xs -> (y, their channel counts); stats_box as _conv_forward"""
+    B, _, H, W = xs[0].shape
+    cs = [int(t.shape[1]) for t in xs]
+    Co = weight.shape[0]
+    g = (B, sum(cs), H, W, Co, 1, 1, 1, 1, 0, 0)
+    L = lib()
+    y = torch.empty((B, Co, H, W), dtype=torch.float32, device=weight.device)
+    wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), y)
+    stats = None
+    if stats_box is not None:
+        rec = stats_side_output(stats_box, L.cnuda_conv2d_stats_block, g, H * W, weight.device, per_image=True)
+        stats = rec and rec[0]
+    prof_arm('conv_fwd', B, sum(cs), H, W, Co, 1, 1, H, W)
+    with pack_stamp(token, weight, version):
+        check(L.cnuda_conv2d_cat_forward(_ptr_array(xs), (ctypes.c_int * len(cs))(*cs), len(xs), ptr(weight), ptr(bias), ptr(y),
+                                         ptr(stats), float(act_slope), B, H, W, Co, wp, wn, stream()), 'conv2d_cat_forward')
+    return y, cs
+
+
 class _CatConv1x1(Function):
     """y = conv1x1(cat(xs, 1), weight) without the concatenation (cnuda_conv2d_cat_*): DLA's Root (backends/dla.py
     Root.forward; reference dla.py:150-168).  The input gradient of every source goes to that source's own tensor, with the
@@ -849,26 +837,13 @@ class _CatConv1x1(Function):
         xs = [f32c(t) for t in xs]
         weight = f32c(weight)
         B, _, H, W = xs[0].shape
-        cs = [int(t.shape[1]) for t in xs]
-        Co = weight.shape[0]
+        cin = sum(int(t.shape[1]) for t in xs)
         for t in xs:
             if t.shape[0] != B or t.shape[2] != H or t.shape[3] != W:
                 raise RuntimeError("conv1x1_cat: mismatching shapes")
-        if weight.shape[1] != sum(cs) or weight.shape[2] != 1 or weight.shape[3] != 1:
-            raise RuntimeError("conv1x1_cat: weight %s for %d concatenated channels" % (tuple(weight.shape), sum(cs)))
-        g = (B, sum(cs), H, W, Co, 1, 1, 1, 1, 0, 0)
-        L = lib()
-        y = torch.empty((B, Co, H, W), dtype=torch.float32, device=weight.device)
-        wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), y)
-        stats = None
-        if stats_box is not None:
-            rec = stats_side_output(stats_box, L.cnuda_conv2d_stats_block, g, H * W, weight.device, per_image=True)
-            stats = rec and rec[0]
-        cs_arr = (ctypes.c_int * len(cs))(*cs)
-        prof_arm('conv_fwd', B, sum(cs), H, W, Co, 1, 1, H, W)
-        with pack_stamp(pack_token, weight):
-            check(L.cnuda_conv2d_cat_forward(_ptr_array(xs), cs_arr, len(xs), ptr(weight), None, ptr(y), ptr(stats), -1.0,
-                                             B, H, W, Co, wp, wn, stream()), 'conv2d_cat_forward')
+        if weight.shape[1] != cin or weight.shape[2] != 1 or weight.shape[3] != 1:
+            raise RuntimeError("conv1x1_cat: weight %s for %d concatenated channels" % (tuple(weight.shape), cin))
+        y, cs = _cat_forward(xs, weight, None, -1.0, pack_token, stats_box=stats_box)
         ctx.cs, ctx.pack_token = cs, pack_token
         ctx.save_for_backward(weight, *xs)
         return y
@@ -932,18 +907,7 @@ def conv1x1_cat_infer(xs, weight, bias=None, act_slope=-1.0, pack_token=0, pack_
     xs = [f32c(t.detach()) for t in xs]
     weight = f32c(weight.detach())
     bias = None if bias is None else f32c(bias.detach())
-    B, _, H, W = xs[0].shape
-    cs = [int(t.shape[1]) for t in xs]
-    Co = weight.shape[0]
-    g = (B, sum(cs), H, W, Co, 1, 1, 1, 1, 0, 0)
-    L = lib()
-    y = torch.empty((B, Co, H, W), dtype=torch.float32, device=weight.device)
-    wp, wn = _ws(L.cnuda_conv2d_workspace_bytes(*g), y)
-    prof_arm('conv_fwd', B, sum(cs), H, W, Co, 1, 1, H, W)
-    with pack_stamp(pack_token, weight, pack_version):
-        check(L.cnuda_conv2d_cat_forward(_ptr_array(xs), (ctypes.c_int * len(cs))(*cs), len(xs), ptr(weight), ptr(bias), ptr(y),
-                                         None, float(act_slope), B, H, W, Co, wp, wn, stream()), 'conv2d_cat_forward')
-    return y
+    return _cat_forward(xs, weight, bias, act_slope, pack_token, pack_version)[0]
 
 
 def conv1x1_cat(xs, weight, pack_token=0, emit_stats=False):
