@@ -162,6 +162,7 @@ class _Sig:
     cnuda_augment_warp = (_I, [_P] * 8 + [ctypes.c_ulonglong] + [_I] * 5 + [_P])
     cnuda_augment_points = (_I, [_P] * 3 + [_I] + [_P] * 2 + [_I] * 2 + [_P])
     cnuda_render_detections = (_I, [_P] * 6 + [_I] * 8 + [_F] * 6 + [_P])
+    cnuda_meter_update = (_I, [_P, _I, _D, _P, _P, _P, _P])
     cnuda_fda_workspace_bytes = (c_size_t, [_I] * 4)
     cnuda_fda_source_to_target = (_I, [_P] * 4 + [_I] * 4 + _WS)
     cnuda_adam_step = (_I, [_P] * 4 + [_LL] + [_F] * 5 + [_I, _P])

@@ -1295,3 +1295,32 @@ def fda_source_to_target(src, trg, use_target_amp):
     check(lib().cnuda_fda_source_to_target(ptr(src), ptr(trg), ptr(m), ptr(out), B, C, H, W, wp, wn, stream()),
           'fda_source_to_target')
     return out
+
+
+# ---------------------------------------------------------------------------
+# Running statistics on the device (csrc/meters.hip)
+# ---------------------------------------------------------------------------
+METER_SLOTS = 32
+
+
+def meter_update(values, n, sums, counts, last):
+    """values: 1 to 32 0-dim float32 device tensors; meter i of the device arrays sums / counts (float64) and last
+    (float32), each of at least len(values) elements, takes sums[i] += float64(values[i]) * n, counts[i] += n,
+    last[i] = values[i] -- one launch, nothing read back, nothing uploaded (the pointers travel in the kernel
+    arguments).  The caller keeps stream order: the values are read on the current stream."""
+    values = list(values)
+    require_gpu(sums, counts, last, *values)
+    S = len(values)
+    if not 1 <= S <= METER_SLOTS:
+        raise RuntimeError("meter_update: 1 to %d values per call, got %d" % (METER_SLOTS, S))
+    for v in values:
+        if v.dtype != torch.float32 or v.dim() != 0:
+            raise RuntimeError("meter_update: values must be 0-dim float32 tensors, got %s %s"
+                               % (v.dtype, tuple(v.shape)))
+    if sums.dtype != torch.float64 or counts.dtype != torch.float64 or last.dtype != torch.float32 \
+            or min(sums.numel(), counts.numel(), last.numel()) < S \
+            or not (sums.is_contiguous() and counts.is_contiguous() and last.is_contiguous()):
+        raise RuntimeError("meter_update: sums / counts must be contiguous float64 and last float32 arrays of at "
+                           "least %d elements" % S)
+    table = (ctypes.c_void_p * S)(*[v.data_ptr() for v in values])
+    check(lib().cnuda_meter_update(table, S, float(n), ptr(sums), ptr(counts), ptr(last), stream()), 'meter_update')

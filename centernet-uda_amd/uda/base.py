@@ -26,6 +26,10 @@ class Model:
     # DLASeg.forward_domains) when the backend offers it; False restores the reference's literal call sequence
     batch_domains = True
     target_grad_heads = ('hm',)        # heads whose target-domain output feeds a loss (entropy / max-squares: hm)
+    # True: `outputs['stats']` are host tensors, one blocking copy per statistic and step, as in the reference
+    # (uda/base.py:51-52).  The driver sets False when it keeps its meters on the device (utils.helper.DeviceMeters):
+    # the statistics then stay detached device tensors and the step reads nothing back.
+    host_stats = True
 
     def __init__(self):
         self.cfg = None
@@ -83,8 +87,9 @@ class Model:
             if hasattr(m, 'finish_gradient_sync'):
                 m.finish_gradient_sync()
 
-    @staticmethod
-    def _detach_stats(stats):
+    def _detach_stats(self, stats):
+        if not self.host_stats:
+            return {k: v.detach() for k, v in stats.items()}
         # one device->host sync per step, where the reference has it (uda/base.py:51-52)
         return {k: v.cpu().detach() for k, v in stats.items()}
 

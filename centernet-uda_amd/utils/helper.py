@@ -34,6 +34,79 @@ class AverageMeter:
         return fmtstr.format(**self.__dict__)
 
 
+class DeviceMeters:
+    """The driver's AverageMeters (train.py:162-166) with their state on the device: `update` folds the 0-dim float32
+    device tensors of a step's `stats` into sum / count / last arrays with one kernel launch per 32 of them
+    (hip_runtime.ops.meter_update) and reads nothing back; `read` copies the arrays to the host once.  The sums are
+    the float64 sums `AverageMeter.update(v.item(), n)` builds, bit for bit.  Anything that is not such a tensor (a
+    Python number, a host tensor) goes to a host AverageMeter of that name."""
+
+    def __init__(self, device, capacity=64):
+        self.device = torch.device(device)
+        self.capacity = int(capacity)
+        self.slots = {}                 # name -> index, in order of first sight
+        self.host = {}                  # name -> AverageMeter
+        # one buffer, so that read() is one copy: sum [capacity] f64 | count [capacity] f64 | last [capacity] f32
+        self._state = torch.zeros(self.capacity * 20, dtype=torch.uint8, device=self.device)
+        c = self.capacity
+        self._sum = self._state[:8 * c].view(torch.float64)
+        self._count = self._state[8 * c:16 * c].view(torch.float64)
+        self._last = self._state[16 * c:].view(torch.float32)
+
+    def _on_device(self, v):
+        return isinstance(v, torch.Tensor) and v.is_cuda and v.dim() == 0 and v.dtype == torch.float32
+
+    def update(self, stats, n):
+        from hip_runtime import ops
+        taken = []
+        for name, v in stats.items():
+            if name not in self.slots and name not in self.host and self._on_device(v):
+                if len(self.slots) >= self.capacity:
+                    raise RuntimeError("DeviceMeters: more than %d names (capacity=)" % self.capacity)
+                self.slots[name] = len(self.slots)
+            if name in self.slots and self._on_device(v):
+                taken.append((self.slots[name], v.detach()))
+            else:
+                if name in self.slots:
+                    raise RuntimeError("DeviceMeters: %r was a device scalar before and is a %s now"
+                                       % (name, type(v).__name__))
+                m = self.host.setdefault(name, AverageMeter(name=name))
+                m.update(v.item() if isinstance(v, torch.Tensor) else v, n)
+        taken.sort(key=lambda e: e[0])
+        start = 0
+        while start < len(taken):       # runs of consecutive slots, at most 32 per launch
+            end = start + 1
+            while end < len(taken) and end - start < ops.METER_SLOTS and taken[end][0] == taken[end - 1][0] + 1:
+                end += 1
+            first = taken[start][0]
+            ops.meter_update([v for _, v in taken[start:end]], n, self._sum[first:], self._count[first:],
+                             self._last[first:])
+            start = end
+
+    def read(self):
+        """-> {name: AverageMeter} (val, sum, count, avg) after ONE copy to the host, which also synchronises."""
+        host = self._state.cpu()
+        c = self.capacity
+        sums = host[:8 * c].view(torch.float64).tolist()
+        counts = host[8 * c:16 * c].view(torch.float64).tolist()
+        last = host[16 * c:].view(torch.float32).tolist()
+        out = {}
+        for name, i in self.slots.items():
+            m = AverageMeter(name=name)
+            m.val, m.sum, m.count = last[i], sums[i], counts[i]
+            if m.count > 0:
+                m.avg = m.sum / m.count
+            out[name] = m
+        out.update(self.host)
+        return out
+
+    def reset(self):
+        """Values back to zero; the names keep their slots."""
+        self._state.zero_()
+        for m in self.host.values():
+            m.reset()
+
+
 def _unwrap(model):
     return model.module if hasattr(model, 'module') and isinstance(model.module, torch.nn.Module) else model
 

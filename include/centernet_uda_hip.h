@@ -800,6 +800,17 @@ int cnuda_render_detections(const float* input, const int* index, const int* pri
                             int G, int gh, int gw, float mean0, float mean1, float mean2,
                             float std0, float std1, float std2, cnuda_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * Running statistics on the device (the driver's AverageMeter bookkeeping, train.py:162-166, without a read-back per
+ * statistic and step).  values: a HOST array of S (1..32) device pointers to float32 scalars; they are passed to the
+ * kernel by value, nothing is uploaded.  sum [S] f64, count [S] f64 and last [S] f32 are device arrays; meter i does
+ *   sum[i] = sum[i] + (double)v_i * n;  count[i] = count[i] + n;  last[i] = v_i
+ * with the product and the sum rounded separately (no fused multiply-add): the float64 sequence of
+ * AverageMeter.update(float(v), n).  One launch of one 64-lane workgroup, no atomics.  Null pointers, S outside 1..32
+ * and n < 0 (or NaN) return CNUDA_ERR_INVALID_ARGUMENT without a launch. */
+int cnuda_meter_update(const float* const* values, int S, double n, double* sum, double* count, float* last,
+                       cnuda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
