@@ -95,6 +95,12 @@ inline int stream_grid(long long work_items, int block) {
     return (int)(g > kMaxStreamBlocks ? kMaxStreamBlocks : g);
 }
 
+// The clamped sigmoid of the heat map (utils/tensor.py:5-7), defined once: cnuda_sigmoid_clamp_ (loss.hip) and
+// cnuda_tta_merge (predict.hip) must give the same bits for the same logit.
+constexpr float kProbLo = 1e-4f, kProbHi = 1.0f - 1e-4f;
+__device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float sigmoid_clamped(float x) { return fminf(fmaxf(sigmoid_f32(x), kProbLo), kProbHi); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

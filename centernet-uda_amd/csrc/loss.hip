@@ -13,9 +13,9 @@ namespace cnuda {
 namespace {
 
 constexpr int kT = 256;
-constexpr float kLo = 1e-4f, kHi = 1.0f - 1e-4f;
+constexpr float kLo = kProbLo, kHi = kProbHi;       // common.h: shared with predict.hip
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float sigmoidf_(float x) { return sigmoid_f32(x); }
 
 // ---------------- focal ----------------
 // partial[blk*3 + {0,1,2}] = sum pos_loss, sum neg_loss, num_pos

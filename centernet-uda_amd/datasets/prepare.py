@@ -27,7 +27,9 @@ def _three(v, what):
     return [float(x) for x in a]                      # float32 values: the c_float conversion is exact
 
 
-def prepare_input(images, mean=MEAN, std=STD):
+def prepare_input(images, mean=MEAN, std=STD, out=None):
+    """`out`: a contiguous float32 [B, 3, H, W] tensor to fill instead of a new one (predict.py: the first half of the
+    batch whose second half holds the mirrors)."""
     require_gpu(images)
     if images.dtype != torch.uint8:
         raise RuntimeError("prepare_input: images must be uint8, got %s" % images.dtype)
@@ -37,7 +39,12 @@ def prepare_input(images, mean=MEAN, std=STD):
     if images.data_ptr() % 4:
         images = images.clone()                       # a byte-offset view: the kernel loads dwords
     B, H, W, _ = images.shape
-    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=images.device)
+    if out is None:
+        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=images.device)
+    elif tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != images.device:
+        raise RuntimeError("prepare_input: out must be a contiguous float32 %s on %s, got %s %s"
+                           % ((B, 3, H, W), images.device, out.dtype, tuple(out.shape)))
     check(lib().cnuda_prepare_input(ptr(images), ptr(out), B, H, W, *_three(mean, 'mean'), *_three(std, 'std'),
                                     stream()), 'prepare_input')
     return out

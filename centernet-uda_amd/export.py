@@ -5,7 +5,7 @@ DLA backend, in eval mode -- with every BatchNorm folded into the convolution in
 conv + BN + skip connection + ReLU block: backends/dla.py `fold_batchnorm`), then the clamped sigmoid of the heat
 map, the fused NMS + top-K decode and the `down_ratio` scaling, and returns `(boxes, scores, classes)` exactly like the reference's module:
 boxes `[B, K, 4]` (`[x1, y1, x2, y2]` in input pixels) or `[B, K, 5]` (`[cx, cy, w, h, angle]`) for rotated
-models.  The ONNX export / simplifier part of export.py is out of scope; `build_model` keeps
+models.  `CenterNet.heads(x)` stops after the backend: the raw head maps, for predict.py.  The ONNX export / simplifier part of export.py is out of scope; `build_model` keeps
 the reference's checkpoint lookup (`model_last.pth` / `model_best.pth` in the experiment folder).
 """
 from importlib import import_module
@@ -45,9 +45,15 @@ class CenterNet(nn.Module):
         return mod.folded_inference()
 
     @torch.no_grad()
-    def forward(self, x):
+    def heads(self, x):
+        """The backend's raw output dict ('hm' logits, 'wh', 'reg', 'kps' when the model has the head) under the same
+        BatchNorm folding as `forward`: what predict.py merges and decodes itself."""
         with self._folding():
-            out = self.backend(x)
+            return self.backend(x)
+
+    @torch.no_grad()
+    def forward(self, x):
+        out = self.heads(x)
         has_kps = 'kps' in out
         dets = decode_detection(ops.sigmoid_clamp_(out['hm']), out['wh'], out['reg'],
                                 kps=out['kps'] if has_kps else None, K=self.max_detections,

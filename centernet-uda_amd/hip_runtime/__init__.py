@@ -163,6 +163,11 @@ class _Sig:
     cnuda_augment_points = (_I, [_P] * 3 + [_I] + [_P] * 2 + [_I] * 2 + [_P])
     cnuda_render_detections = (_I, [_P] * 6 + [_I] * 8 + [_F] * 6 + [_P])
     cnuda_meter_update = (_I, [_P, _I, _D, _P, _P, _P, _P])
+    cnuda_mirror_input = (_I, [_P, _P, _LL, _I, _I, _P])
+    cnuda_tta_merge = (_I, [_P] * 9 + [_I] * 6 + [_P])
+    cnuda_project_detections = (_I, [_P] * 9 + [_I] * 4 + [_F, _F, _I, _I, _P])
+    cnuda_predict_workspace_bytes = (c_size_t, [_I, _I])
+    cnuda_soft_nms_merge = (_I, [_P] * 10 + [_I] * 5 + [_F] + _WS)
     cnuda_fda_workspace_bytes = (c_size_t, [_I] * 4)
     cnuda_fda_source_to_target = (_I, [_P] * 4 + [_I] * 4 + _WS)
     cnuda_adam_step = (_I, [_P] * 4 + [_LL] + [_F] * 5 + [_I, _P])

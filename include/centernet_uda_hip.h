@@ -811,6 +811,59 @@ int cnuda_render_detections(const float* input, const int* index, const int* pri
 int cnuda_meter_update(const float* const* values, int S, double n, double* sum, double* count, float* last,
                        cnuda_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * Prediction over images (predict.py; csrc/predict.hip; DESIGN.md, "Prediction").  Deterministic: no floating-point
+ * atomics, every result independent of scheduling.  Caller's stream.
+ * ---------------------------------------------------------------------- */
+/* y[p, i, j] = x[p, i, W-1-j] for `planes` planes of H x W float32 (an input batch [B,3,H,W]: planes = 3 B).  A copy:
+ * bit-exact.  x and y must not overlap. */
+int cnuda_mirror_input(const float* x, float* y, long long planes, int H, int W, cnuda_stream_t stream);
+/* Mirror test-time augmentation: the RAW head maps of a 2B batch -- images 0..B-1 and their left-right mirrors
+ * B..2B-1 -- to B merged maps (M = the mirror j -> W-1-j), float32, one rounding per output:
+ *   hm_out[b]  = 0.5 (s(hm[b]) + M s(hm[B+b])), s = clamp(sigmoid, 1e-4, 1 - 1e-4) as cnuda_sigmoid_clamp_ computes it
+ *                (hm_out is what decode_detection takes: no further sigmoid);      hm [2B,C,H,W] -> [B,C,H,W]
+ *   wh_out[b]  = 0.5 (wh[b] + M wh[B+b]) for channels 0, 1; a third channel (the angle) is wh[b]'s; wh [2B,wh_ch,H,W]
+ *   reg_out[b] = reg[b]                                     (reg, reg_out both NULL: the model has no offset head)
+ *   kps_out[b]: x_j = 0.5 (kps[b][2j] - M kps[B+b][2 perm[j]]), y_j = 0.5 (kps[b][2j+1] + M kps[B+b][2 perm[j] + 1]);
+ *               kps [2B,2J,H,W], perm [J] int32 on the device with values in [0, J) (NULL: the identity); J = 0: kps,
+ *               kps_out and perm NULL. */
+int cnuda_tta_merge(const float* hm, const float* wh, const float* reg, const float* kps, const int* perm,
+                    float* hm_out, float* wh_out, float* reg_out, float* kps_out,
+                    int B, int C, int wh_ch, int J, int H, int W, cnuda_stream_t stream);
+/* Decoded detections to source-image pixels.  dets [B,K,6] (x1, y1, x2, y2, score, class) or, rotated, [B,K,7]
+ * (cx, cy, w, h, angle in degrees, score, class) as cnuda_decode_detection leaves them, rows in descending score order;
+ * the four geometry columns (and kps [B,K,J,2], NULL with J = 0) are first multiplied by `scale` in float32 (the
+ * model's down_ratio; 1: already input pixels).  matrix [B,6] float64: input -> source pixels, row-major 2 x 3,
+ * X = (m0 x + m1 y) + m2, Y = (m3 x + m4 y) + m5; sizes [B,2] int32 (h, w) of the sources.  All arithmetic in double,
+ * stored as float32.  Outputs are arrays of out_rows >= out_first + K rows per image; row k of the call lands in row
+ * out_first + k (several scales write one candidate table):
+ *   axis-aligned: boxes [B,out_rows,4], the bounding box of the four mapped corners clipped to [0, w] x [0, h];
+ *   rotated: boxes [B,out_rows,4,2], the vertices centre + (-w/2,-h/2), (w/2,-h/2), (w/2,h/2), (-w/2,h/2) times
+ *     [[cos, sin], [-sin, cos]] (utils/box.py rotate_bboxes, not truncated), mapped, not clipped;
+ *   scores [B,out_rows], classes [B,out_rows] int32, kps_out [B,out_rows,J,2] (mapped, not clipped);
+ *   counts [B] int32: the rows of this call with score >= threshold (both float32; a prefix, given the order). */
+int cnuda_project_detections(const float* dets, const float* kps, const double* matrix, const int* sizes,
+                             float* boxes, float* scores, int* classes, float* kps_out, int* counts,
+                             int B, int K, int J, int rotated, float scale, float threshold,
+                             int out_rows, int out_first, cnuda_stream_t stream);
+/* Gaussian soft-NMS over the candidates of several scales, per image.  boxes [B,N,4] (x1, y1, x2, y2), scores [B,N],
+ * classes [B,N] int32 (outside [0, C): ignored), kps [B,N,J,2] or NULL (J = 0); ncand [B] int32 or NULL: image b
+ * uses its first ncand[b] (clamped to [0, N]) candidates, all N with NULL.  N <= CNUDA_SOFT_NMS_MAX_CANDIDATES, else
+ * an error (never truncated).  Stage 1, per (image, class), in double: area = (x2-x1)(y2-y1); iou = inter /
+ * ((a_i + a_j) - inter), 0 without overlap or with a union <= 0; repeat: take the live candidate with the largest
+ * current score (ties: the lower candidate index); stop when it is < 1e-3; else emit it with that score and multiply
+ * every other live candidate's score by exp(-(iou iou) / 0.5).  Stage 2, per image: the emitted candidates ordered by
+ * (score descending, class ascending, index ascending), the first max_detections kept: out_boxes [B,max_detections,4],
+ * out_scores (float32 of the double), out_classes int32, out_kps [B,max_detections,J,2]; rows past the last kept one
+ * are zero with class -1.  counts [B]: kept rows with float32 score >= threshold.
+ * Workspace: cnuda_predict_workspace_bytes(B, N) (0 and an error text when N is over the limit). */
+#define CNUDA_SOFT_NMS_MAX_CANDIDATES 2048
+size_t cnuda_predict_workspace_bytes(int B, int N);
+int cnuda_soft_nms_merge(const float* boxes, const float* scores, const int* classes, const float* kps,
+                         const int* ncand, float* out_boxes, float* out_scores, int* out_classes, float* out_kps,
+                         int* counts, int B, int N, int C, int J, int max_detections, float threshold,
+                         void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
