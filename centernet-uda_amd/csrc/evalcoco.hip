@@ -1,7 +1,9 @@
 // COCO evaluation on the GPU (evaluation/coco.py): the masks of rotated boxes as one span per image row, the IoU of
 // every (detection, ground truth) pair of one image and one category in float64, and COCOeval's greedy matching for
-// the ten IoU thresholds and four area ranges.  Everything here is integers and doubles that do not depend on
-// scheduling: no floating-point atomics, the only atomics are integer min / max on LDS.
+// the ten IoU thresholds and four area ranges.  For keypoints (evaluation/coco_keypoints.py) the pair similarity is the
+// object keypoint similarity instead, and a ground truth without a labelled joint is ignored by the matching.
+// Everything here is integers and doubles that do not depend on scheduling: no floating-point atomics, the only atomics
+// are integer min / max on LDS.
 //
 // A "group" is one (image, category): five ints {first detection, detections, first ground truth, ground truths,
 // first pair}; pair (d, g) of a group lives at first pair + d * ground truths + g.  Groups are built on the host; every
@@ -155,6 +157,76 @@ __global__ __launch_bounds__(256) void eval_iou_axis_kernel(const int* __restric
     }
 }
 
+constexpr int kMaxJoints = 64;
+
+// One thread per detection, then per ground truth: the area COCO's loadRes gives a keypoint result (the bounds of its J
+// predicted joints), and the flag of a ground truth without a labelled joint (COCOeval._prepare ignores it).
+__global__ __launch_bounds__(256) void eval_kps_prepare_kernel(const float* __restrict__ det_kps,
+                                                               const unsigned char* __restrict__ gt_vis, int ND, int NGT,
+                                                               int J, double* __restrict__ det_area,
+                                                               unsigned char* __restrict__ gt_flags) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < ND) {
+        const float* P = det_kps + 2 * (size_t)J * (size_t)i;
+        double x0 = P[0], x1 = x0, y0 = P[1], y1 = y0;
+        for (int j = 1; j < J; ++j) {
+            const double x = P[2 * j], y = P[2 * j + 1];
+            x0 = x < x0 ? x : x0, x1 = x > x1 ? x : x1;
+            y0 = y < y0 ? y : y0, y1 = y > y1 ? y : y1;
+        }
+        det_area[i] = (x1 - x0) * (y1 - y0);
+    } else if (i < (long long)ND + NGT) {
+        const size_t g = (size_t)(i - ND);
+        int k1 = 0;
+        for (int j = 0; j < J; ++j) k1 += gt_vis[g * J + j] > 0;
+        gt_flags[g] = k1 == 0;
+    }
+}
+
+// One thread per pair: COCOeval.computeOks in its order of operations.  Joints are float32 (x, y), the arithmetic is
+// double; the sum runs over ascending j.  lds: var_j = (2 sigma_j)^2.
+__global__ __launch_bounds__(256) void eval_oks_kernel(const int* __restrict__ groups, int ND, int NGT, long long num_pairs,
+                                                       const float* __restrict__ det_kps, const float* __restrict__ gt_kps,
+                                                       const unsigned char* __restrict__ gt_vis,
+                                                       const double* __restrict__ gt_area, const float* __restrict__ gt_box,
+                                                       const double* __restrict__ sigmas, int J, double* __restrict__ oks) {
+    __shared__ double var[kMaxJoints];
+    Group q;
+    if (!load_group(groups, blockIdx.x, ND, NGT, num_pairs, q)) return;      // the whole workgroup leaves
+    if ((int)threadIdx.x < J) {
+        const double s = 2.0 * sigmas[threadIdx.x];
+        var[threadIdx.x] = s * s;
+    }
+    __syncthreads();
+    const long long pairs = (long long)q.nd * q.ng;
+    for (long long p = (long long)blockIdx.y * blockDim.x + threadIdx.x; p < pairs; p += (long long)gridDim.y * blockDim.x) {
+        const size_t d = (size_t)(q.det0 + (int)(p / q.ng)), g = (size_t)(q.gt0 + (int)(p % q.ng));
+        const float* D = det_kps + 2 * (size_t)J * d;
+        const float* Gt = gt_kps + 2 * (size_t)J * g;
+        const unsigned char* V = gt_vis + (size_t)J * g;
+        int k1 = 0;
+        for (int j = 0; j < J; ++j) k1 += V[j] > 0;
+        const double scale = gt_area[g] + 0x1p-52;
+        double sum = 0.0;
+        if (k1 > 0) {
+            for (int j = 0; j < J; ++j) {
+                if (V[j] == 0) continue;
+                const double dx = (double)D[2 * j] - (double)Gt[2 * j], dy = (double)D[2 * j + 1] - (double)Gt[2 * j + 1];
+                sum += exp(-((dx * dx + dy * dy) / var[j] / scale / 2.0));
+            }
+        } else {      // no labelled joint: the distance to the ground-truth box doubled about its centre, over all joints
+            const double bx = gt_box[4 * g], by = gt_box[4 * g + 1], bw = gt_box[4 * g + 2], bh = gt_box[4 * g + 3];
+            const double x0 = bx - bw, x1 = bx + 2.0 * bw, y0 = by - bh, y1 = by + 2.0 * bh;
+            for (int j = 0; j < J; ++j) {
+                const double xd = D[2 * j], yd = D[2 * j + 1];
+                const double dx = fmax(0.0, x0 - xd) + fmax(0.0, xd - x1), dy = fmax(0.0, y0 - yd) + fmax(0.0, yd - y1);
+                sum += exp(-((dx * dx + dy * dy) / var[j] / scale / 2.0));
+            }
+        }
+        oks[q.pair0 + p] = sum / (double)(k1 > 0 ? k1 : J);
+    }
+}
+
 struct MatchTables {
     double thr[kMaxThresholds], lo[kAreaRanges], hi[kAreaRanges];
     int T;
@@ -163,11 +235,13 @@ struct MatchTables {
 // One wave per (group, area range): detections in score order, one after the other; for each of the T thresholds the
 // arg-max over the still unmatched ground truths across the lanes.  Key: (not ignored, IoU, index), so a non-ignored
 // candidate beats every ignored one, the larger IoU wins, and a tie goes to the later ground truth.
+// gt_flags (may be null): a flagged ground truth is ignored in every area range.
 // lds: per ground truth, bit t = matched at threshold t, bit 31 = ignored in this range.
 __global__ __launch_bounds__(64) void eval_match_kernel(const double* __restrict__ iou, const int* __restrict__ groups,
                                                         int ND, int NGT, long long num_pairs,
                                                         const double* __restrict__ det_area,
-                                                        const double* __restrict__ gt_area, MatchTables mt,
+                                                        const double* __restrict__ gt_area,
+                                                        const unsigned char* __restrict__ gt_flags, MatchTables mt,
                                                         unsigned* __restrict__ det_bits,
                                                         unsigned char* __restrict__ gt_ignore) {
     extern __shared__ unsigned gstate[];
@@ -177,7 +251,7 @@ __global__ __launch_bounds__(64) void eval_match_kernel(const double* __restrict
     const double lo = mt.lo[a], hi = mt.hi[a];
     for (int j = lane; j < q.ng; j += 64) {
         const double ar = gt_area[q.gt0 + j];
-        const unsigned ig = (ar < lo || ar > hi) ? 1u : 0u;
+        const unsigned ig = (ar < lo || ar > hi || (gt_flags && gt_flags[q.gt0 + j])) ? 1u : 0u;
         gstate[j] = ig << 31;
         gt_ignore[(size_t)(q.gt0 + j) * kAreaRanges + a] = (unsigned char)ig;
     }
@@ -270,11 +344,10 @@ extern "C" int cnuda_eval_iou_axis(const float* det_boxes, const float* gt_boxes
     return check_launch(who);
 }
 
-extern "C" int cnuda_eval_match(const double* iou, const int* groups, int num_groups, const double* det_area,
-                                const double* gt_area, int num_det, int num_gt, long long num_pairs,
-                                const double* thresholds, int num_thresholds, const double* area_ranges,
-                                unsigned* det_bits, unsigned char* gt_ignore, void* stream) {
-    const char* who = "cnuda_eval_match";
+static int eval_match(const char* who, const double* iou, const int* groups, int num_groups, const double* det_area,
+                      const double* gt_area, const unsigned char* gt_flags, bool flagged, int num_det, int num_gt,
+                      long long num_pairs, const double* thresholds, int num_thresholds, const double* area_ranges,
+                      unsigned* det_bits, unsigned char* gt_ignore, void* stream) {
     const char* bad = groups_error(num_groups, num_det, num_gt, num_pairs);
     CNUDA_REQUIRE(!bad, "%s: %s", who, bad);
     bad = match_error(thresholds, num_thresholds, area_ranges);
@@ -282,7 +355,7 @@ extern "C" int cnuda_eval_match(const double* iou, const int* groups, int num_gr
     CNUDA_REQUIRE(num_gt <= 8192 * 2, "%s: more than 16384 ground truths in one call", who);
     if (num_groups == 0) return 0;
     CNUDA_REQUIRE(groups && (det_area || num_det == 0) && (gt_area || num_gt == 0) && (iou || num_pairs == 0) &&
-                      (det_bits || num_det == 0) && (gt_ignore || num_gt == 0),
+                      (det_bits || num_det == 0) && (gt_ignore || num_gt == 0) && (gt_flags || !flagged || num_gt == 0),
                   "%s: null pointer", who);
     MatchTables mt;
     mt.T = num_thresholds;
@@ -290,6 +363,47 @@ extern "C" int cnuda_eval_match(const double* iou, const int* groups, int num_gr
     for (int a = 0; a < kAreaRanges; ++a) mt.lo[a] = area_ranges[2 * a], mt.hi[a] = area_ranges[2 * a + 1];
     // a group's ground truths never outnumber num_gt: the kernel skips a group that says otherwise
     CNUDA_LAUNCH(eval_match_kernel, dim3((unsigned)num_groups, kAreaRanges), dim3(kWave), sizeof(unsigned) * num_gt,
-                 (hipStream_t)stream, iou, groups, num_det, num_gt, num_pairs, det_area, gt_area, mt, det_bits, gt_ignore);
+                 (hipStream_t)stream, iou, groups, num_det, num_gt, num_pairs, det_area, gt_area, gt_flags, mt, det_bits,
+                 gt_ignore);
+    return check_launch(who);
+}
+
+extern "C" int cnuda_eval_match(const double* iou, const int* groups, int num_groups, const double* det_area,
+                                const double* gt_area, int num_det, int num_gt, long long num_pairs,
+                                const double* thresholds, int num_thresholds, const double* area_ranges,
+                                unsigned* det_bits, unsigned char* gt_ignore, void* stream) {
+    return eval_match("cnuda_eval_match", iou, groups, num_groups, det_area, gt_area, nullptr, false, num_det, num_gt,
+                      num_pairs, thresholds, num_thresholds, area_ranges, det_bits, gt_ignore, stream);
+}
+
+extern "C" int cnuda_eval_match_flagged(const double* iou, const int* groups, int num_groups, const double* det_area,
+                                        const double* gt_area, const unsigned char* gt_flags, int num_det, int num_gt,
+                                        long long num_pairs, const double* thresholds, int num_thresholds,
+                                        const double* area_ranges, unsigned* det_bits, unsigned char* gt_ignore,
+                                        void* stream) {
+    return eval_match("cnuda_eval_match_flagged", iou, groups, num_groups, det_area, gt_area, gt_flags, true, num_det,
+                      num_gt, num_pairs, thresholds, num_thresholds, area_ranges, det_bits, gt_ignore, stream);
+}
+
+extern "C" int cnuda_eval_oks(const float* det_kps, const float* gt_kps, const unsigned char* gt_vis, const double* gt_area,
+                              const float* gt_box, const double* sigmas, int num_joints, const int* groups, int num_groups,
+                              int num_det, int num_gt, long long num_pairs, double* oks, double* det_area,
+                              unsigned char* gt_flags, void* stream) {
+    const char* who = "cnuda_eval_oks";
+    const char* bad = groups_error(num_groups, num_det, num_gt, num_pairs);
+    CNUDA_REQUIRE(!bad, "%s: %s", who, bad);
+    CNUDA_REQUIRE(num_joints >= 1 && num_joints <= kMaxJoints, "%s: J = %d joints, between 1 and %d are supported", who,
+                  num_joints, kMaxJoints);
+    if (num_det == 0 && num_gt == 0) return 0;
+    CNUDA_REQUIRE((det_kps && det_area) || num_det == 0, "%s: null pointer (detections)", who);
+    CNUDA_REQUIRE((gt_vis && gt_flags) || num_gt == 0, "%s: null pointer (ground truths)", who);
+    const bool any_pair = num_groups > 0 && num_pairs > 0;
+    CNUDA_REQUIRE(!any_pair || (groups && gt_kps && gt_area && gt_box && sigmas && oks), "%s: null pointer (pairs)", who);
+    CNUDA_LAUNCH(eval_kps_prepare_kernel, dim3((unsigned)(((long long)num_det + num_gt + 255) / 256)), dim3(256), 0,
+                 (hipStream_t)stream, det_kps, gt_vis, num_det, num_gt, num_joints, det_area, gt_flags);
+    int rc = check_launch(who);
+    if (rc != 0 || !any_pair) return rc;
+    CNUDA_LAUNCH(eval_oks_kernel, dim3((unsigned)num_groups, kPairChunks), dim3(256), 0, (hipStream_t)stream, groups,
+                 num_det, num_gt, num_pairs, det_kps, gt_kps, gt_vis, gt_area, gt_box, sigmas, num_joints, oks);
     return check_launch(who);
 }

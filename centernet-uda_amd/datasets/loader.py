@@ -76,7 +76,7 @@ class HostBatch:
 
 class DeviceLoader:
     def __init__(self, dataset, batch_size, shuffle, num_workers, device, seed, num_classes, num_keypoints,
-                 rotated_boxes, down_ratio, mean, std, max_detections):
+                 rotated_boxes, down_ratio, mean, std, max_detections, keypoint_visibility=False):
         self.dataset = dataset
         self.batch_size = int(batch_size)
         if self.batch_size < 1:
@@ -90,6 +90,7 @@ class DeviceLoader:
         self.down_ratio = int(down_ratio)
         self.mean, self.std = tuple(mean), tuple(std)
         self.max_detections = int(max_detections)
+        self.keypoint_visibility = bool(keypoint_visibility) and self.num_keypoints > 0
         self.epoch = 0
         sizes = sorted({tuple(m.input_size) for m in _members(dataset)})
         if len(sizes) != 1:
@@ -216,14 +217,16 @@ class DeviceLoader:
     def to_device(self, host):
         """Uploads and build_batch on the CURRENT stream -> the batch dict (the reference's keys plus `id`)."""
         up = lambda t: None if t is None else t.to(self.device, non_blocking=True)
-        geometry = up(host.geometry)
+        geometry, visibility = up(host.geometry), up(host.visibility)
         batch = build_batch(
             up(host.images), None if self.rotated_boxes else geometry, up(host.classes), up(host.counts),
             params=host.params, input_size=self.input_size, num_classes=self.num_classes, down_ratio=self.down_ratio,
             sizes=host.sizes, corners=geometry if self.rotated_boxes else None, keypoints=up(host.keypoints),
-            visibility=up(host.visibility), areas=up(host.areas), mean=self.mean, std=self.std,
+            visibility=visibility, areas=up(host.areas), mean=self.mean, std=self.std,
             target_images=up(host.target_images), target_sizes=host.target_sizes, target_params=host.target_params)
         batch['id'] = up(host.ids)
+        if self.keypoint_visibility:
+            batch['gt_kps_visibility'] = visibility          # [B, M, J] int32, COCO's v: evaluation/coco_keypoints.py
         return batch
 
     def _issue(self, host):

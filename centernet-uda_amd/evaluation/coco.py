@@ -15,7 +15,8 @@ Differences from the reference, all documented in README.md:
     `rotate_bbox` vertices), not cv2.fillPoly; the two have not been compared;
   * an image id repeated within one evaluation raises ValueError (the reference merges the two images' annotations);
   * per-class values stay float64 (the reference rounds them to float32 before the mean over classes);
-  * `num_workers` is accepted and unused (no pool); keypoints are ignored, as in the reference; no crowd regions."""
+  * `num_workers` is accepted and unused (no pool); keypoints are ignored here, as in the reference (their metrics are
+    evaluation/coco_keypoints.py); no crowd regions."""
 import ctypes
 
 import numpy as np
@@ -48,9 +49,9 @@ SUMMARIES = (
 )
 
 
-def group_batch(pred_classes, pred_scores, gt_classes, score_threshold):
+def group_batch(pred_classes, pred_scores, gt_classes, score_threshold, max_det=MAX_DETECTIONS[-1]):
     """Index bookkeeping of one batch.  Per image: predictions with score < threshold dropped, the rest and the ground
-    truths grouped by category (ascending), a group's detections in descending score order (stable) and cut to 100.
+    truths grouped by category (ascending), a group's detections in descending score order (stable) and cut to `max_det`.
     -> (det_src [ND, 2] (image in batch, prediction index), gt_src [NGT, 2], groups [G, 5] int32 as csrc/evalcoco.hip
     reads them, group_key [G, 2] (image in batch, category), labels seen (before the cut))"""
     det_src, gt_src, groups, keys, labels = [], [], [], [], set()
@@ -64,7 +65,7 @@ def group_batch(pred_classes, pred_scores, gt_classes, score_threshold):
         labels.update(int(c) for c in cats)
         for c in cats:
             d = kept[pc[kept] == c]
-            d = d[np.argsort(-ps[d], kind='mergesort')][:MAX_DETECTIONS[-1]]
+            d = d[np.argsort(-ps[d], kind='mergesort')][:max_det]
             g = np.flatnonzero(gc == c)
             det_src.append(np.stack([np.full(len(d), i), d], 1))
             gt_src.append(np.stack([np.full(len(g), i), g], 1))
@@ -76,10 +77,11 @@ def group_batch(pred_classes, pred_scores, gt_classes, score_threshold):
             np.asarray(keys, dtype=np.int64).reshape(-1, 2), labels)
 
 
-def accumulate(cats, det, gt):
+def accumulate(cats, det, gt, max_dets=MAX_DETECTIONS):
     """COCOeval.accumulate.  det: dict(image, cat, rank (position in its group), score float32, bits uint32 [ND, 4]);
-    gt: dict(cat, ignore bool [NGT, 4]).  -> precision [T, R, K, A, M], recall [T, K, A, M], -1 where undefined."""
-    T, R, K, A, M = len(IOU_THRESHOLDS), len(RECALL_THRESHOLDS), len(cats), len(AREA_RANGES), len(MAX_DETECTIONS)
+    gt: dict(cat, ignore bool [NGT, 4]); max_dets: the detection limits M.  -> precision [T, R, K, A, M],
+    recall [T, K, A, M], -1 where undefined."""
+    T, R, K, A, M = len(IOU_THRESHOLDS), len(RECALL_THRESHOLDS), len(cats), len(AREA_RANGES), len(max_dets)
     precision, recall = -np.ones((T, R, K, A, M)), -np.ones((T, K, A, M))
     shifts = np.arange(T, dtype=np.uint32)[:, None]
     for k, c in enumerate(cats):
@@ -92,7 +94,7 @@ def accumulate(cats, det, gt):
             npig = int(np.count_nonzero(~gt['ignore'][gt_of_cat, a]))
             if npig == 0:
                 continue
-            for m, max_det in enumerate(MAX_DETECTIONS):
+            for m, max_det in enumerate(max_dets):
                 sel = of_cat[det['rank'][of_cat] < max_det]
                 sel = sel[np.argsort(-det['score'][sel], kind='mergesort')]
                 bits = det['bits'][sel, a][None, :]
@@ -117,10 +119,10 @@ def accumulate(cats, det, gt):
     return precision, recall
 
 
-def summarize(precision, recall, is_precision, iou_index, area_index, max_det):
+def summarize(precision, recall, is_precision, iou_index, area_index, max_det, max_dets=MAX_DETECTIONS):
     """The reference's summary of one metric: -1 -> NaN, per class the mean over thresholds (and recall points) that
     have a value, then the mean over the classes that have one.  -> (per class [K], mean)"""
-    m = MAX_DETECTIONS.index(max_det)
+    m = tuple(max_dets).index(max_det)
     v = precision[:, :, :, area_index, m] if is_precision else recall[:, :, area_index, m]
     if iou_index is not None:
         v = v[iou_index:iou_index + 1]
@@ -133,11 +135,11 @@ def summarize(precision, recall, is_precision, iou_index, area_index, max_det):
     return per_class, (per_class[has].mean() if has.any() else np.nan)
 
 
-def to_tensorboard(summaries, existent_labels, per_class, classes):
-    """summaries: [(per-label array, mean)] in the order of SUMMARIES -> {scalar name: value}.  With per_class False the
+def to_tensorboard(summaries, existent_labels, per_class, classes, table=SUMMARIES):
+    """summaries: [(per-label array, mean)] in the order of `table` -> {scalar name: value}.  With per_class False the
     per-label arrays are returned whole under the unformatted per-class names, as the reference does."""
     out = {}
-    for (mean_name, class_name, *_), (per_label, mean) in zip(SUMMARIES, summaries):
+    for (mean_name, class_name, *_), (per_label, mean) in zip(table, summaries):
         if per_class:
             for c in existent_labels:
                 label = classes[c]['name'] if classes is not None and c in classes else c
@@ -160,6 +162,7 @@ def _gather(per_image, src, ncol):
 
 class Evaluator:
     _known_ids = []          # process-wide: ground-truth id -> 1-based image id, in order of first appearance
+    summaries, max_detections = SUMMARIES, MAX_DETECTIONS          # evaluation/coco_keypoints.py has its own
 
     def __init__(self, per_class=True, score_threshold=0.1):
         hr.lib()             # RuntimeError when the HIP library has not been built
@@ -181,10 +184,8 @@ class Evaluator:
         self._batches.clear()
 
     # -- one batch -------------------------------------------------------------------------------------------------
-    def add_batch(self, pred_boxes, pred_classes, pred_scores, gt_boxes, gt_classes, gt_ids, gt_areas, image_shape,
-                  pred_kps=None, gt_kps=None):
-        B = len(gt_ids)
-        H, W = int(image_shape[1]), int(image_shape[2])
+    def _group(self, pred_classes, pred_scores, gt_classes, gt_ids):
+        """the batch's image ids (new to this evaluation, else ValueError) and its `group_batch`"""
         image_ids = []
         for gid in gt_ids:
             gid = int(gid)
@@ -194,10 +195,53 @@ class Evaluator:
             if image_id in self.ids or image_id in image_ids:
                 raise ValueError("Evaluator.add_batch: image id %r was already added to this evaluation" % gid)
             image_ids.append(image_id)
-        det_src, gt_src, groups, keys, labels = group_batch(pred_classes, pred_scores, gt_classes, self.score_threshold)
+        det_src, gt_src, groups, keys, labels = group_batch(pred_classes, pred_scores, gt_classes, self.score_threshold,
+                                                            self.max_detections[-1])
         self.ids.extend(image_ids)
         for lb in labels:
             self.existent_labels[lb] = True
+        return image_ids, det_src, gt_src, groups, keys
+
+    def _match(self, image_ids, det_src, groups, d_groups, keys, pred_scores, iou, det_area, gt_area, gt_flags=None):
+        """queues the matching of one batch (`d_groups`, the pair similarities `iou`, the areas and, for keypoints, the
+        flags of the ground truths to ignore: all on the device) and keeps its record for `evaluate()`"""
+        nd, ngt = len(det_src), int(groups[:, 3].sum())
+        npairs = int((groups[:, 1].astype(np.int64) * groups[:, 3]).sum())
+        dev = iou.device
+        L, st = hr.lib(), hr.stream()
+        det_bits = torch.zeros((max(nd, 1), 4), dtype=torch.int32, device=dev)
+        gt_ignore = torch.zeros((max(ngt, 1), 4), dtype=torch.uint8, device=dev)
+        thr = (ctypes.c_double * len(IOU_THRESHOLDS))(*IOU_THRESHOLDS)
+        rng = (ctypes.c_double * AREA_RANGES.size)(*AREA_RANGES.reshape(-1))
+        if gt_flags is None:
+            hr.check(L.cnuda_eval_match(hr.ptr(iou), hr.ptr(d_groups), len(groups), hr.ptr(det_area), hr.ptr(gt_area), nd,
+                                        ngt, npairs, thr, len(IOU_THRESHOLDS), rng, hr.ptr(det_bits), hr.ptr(gt_ignore),
+                                        st), 'eval_match')
+        else:
+            hr.check(L.cnuda_eval_match_flagged(hr.ptr(iou), hr.ptr(d_groups), len(groups), hr.ptr(det_area),
+                                                hr.ptr(gt_area), hr.ptr(gt_flags), nd, ngt, npairs, thr,
+                                                len(IOU_THRESHOLDS), rng, hr.ptr(det_bits), hr.ptr(gt_ignore), st),
+                     'eval_match_flagged')
+        ids = np.asarray(image_ids, dtype=np.int64)
+        rank = np.concatenate([np.arange(n) for n in groups[:, 1]]) if len(groups) else np.zeros(0, np.int64)
+        scores = _gather(pred_scores, det_src, 1)[:, 0]
+        record = {
+            'det_image': np.repeat(ids[keys[:, 0]], groups[:, 1]) if len(groups) else np.zeros(0, np.int64),
+            'det_cat': np.repeat(keys[:, 1], groups[:, 1]) if len(groups) else np.zeros(0, np.int64),
+            'det_rank': rank.astype(np.int64), 'det_score': scores,
+            'gt_cat': np.repeat(keys[:, 1], groups[:, 3]) if len(groups) else np.zeros(0, np.int64),
+            'nd': nd, 'ngt': ngt, 'det_bits': det_bits, 'gt_ignore': gt_ignore, 'groups': groups, 'keys': keys}
+        if self._keep_intermediates:          # the tests compare these with the oracle's; an epoch does not hold them
+            record.update({'iou': iou, 'det_area': det_area, 'gt_area': gt_area})
+            if gt_flags is not None:
+                record['gt_flags'] = gt_flags
+        self._batches.append(record)
+
+    def add_batch(self, pred_boxes, pred_classes, pred_scores, gt_boxes, gt_classes, gt_ids, gt_areas, image_shape,
+                  pred_kps=None, gt_kps=None):
+        B = len(gt_ids)
+        H, W = int(image_shape[1]), int(image_shape[2])
+        image_ids, det_src, gt_src, groups, keys = self._group(pred_classes, pred_scores, gt_classes, gt_ids)
         ncol = 5 if self.use_rotated_boxes else 4
         det_boxes, gt_boxes_ = _gather(pred_boxes, det_src, ncol), _gather(gt_boxes, gt_src, ncol)
         nd, ngt, npairs = len(det_src), len(gt_src), int((groups[:, 1].astype(np.int64) * groups[:, 3]).sum())
@@ -231,25 +275,7 @@ class Evaluator:
             det_area, gt_area = up(det_area_host), up(gt_area_host)
             hr.check(L.cnuda_eval_iou_axis(hr.ptr(d_det), hr.ptr(d_gt), hr.ptr(d_groups), len(groups), nd, ngt, npairs,
                                            hr.ptr(iou), st), 'eval_iou_axis')
-        det_bits = torch.zeros((max(nd, 1), 4), dtype=torch.int32, device=dev)
-        gt_ignore = torch.zeros((max(ngt, 1), 4), dtype=torch.uint8, device=dev)
-        thr = (ctypes.c_double * len(IOU_THRESHOLDS))(*IOU_THRESHOLDS)
-        rng = (ctypes.c_double * AREA_RANGES.size)(*AREA_RANGES.reshape(-1))
-        hr.check(L.cnuda_eval_match(hr.ptr(iou), hr.ptr(d_groups), len(groups), hr.ptr(det_area), hr.ptr(gt_area), nd, ngt,
-                                    npairs, thr, len(IOU_THRESHOLDS), rng, hr.ptr(det_bits), hr.ptr(gt_ignore), st),
-                 'eval_match')
-        ids = np.asarray(image_ids, dtype=np.int64)
-        rank = np.concatenate([np.arange(n) for n in groups[:, 1]]) if len(groups) else np.zeros(0, np.int64)
-        scores = _gather(pred_scores, det_src, 1)[:, 0]
-        record = {
-            'det_image': np.repeat(ids[keys[:, 0]], groups[:, 1]) if len(groups) else np.zeros(0, np.int64),
-            'det_cat': np.repeat(keys[:, 1], groups[:, 1]) if len(groups) else np.zeros(0, np.int64),
-            'det_rank': rank.astype(np.int64), 'det_score': scores,
-            'gt_cat': np.repeat(keys[:, 1], groups[:, 3]) if len(groups) else np.zeros(0, np.int64),
-            'nd': nd, 'ngt': ngt, 'det_bits': det_bits, 'gt_ignore': gt_ignore, 'groups': groups, 'keys': keys}
-        if self._keep_intermediates:          # the tests compare these with the oracle's; an epoch does not hold them
-            record.update({'iou': iou, 'det_area': det_area, 'gt_area': gt_area})
-        self._batches.append(record)
+        self._match(image_ids, det_src, groups, d_groups, keys, pred_scores, iou, det_area, gt_area)
 
     # -- the epoch's result ----------------------------------------------------------------------------------------
     def _read_back(self):
@@ -279,13 +305,14 @@ class Evaluator:
                'score': join('det_score', np.float32),
                'bits': np.concatenate(bits) if bits else np.zeros((0, 4), np.uint32)}
         gt = {'cat': join('gt_cat', np.int64), 'ignore': np.concatenate(ignore) if ignore else np.zeros((0, 4), bool)}
-        precision, recall = accumulate(existent_labels, det, gt)
+        precision, recall = accumulate(existent_labels, det, gt, self.max_detections)
         summaries = []
-        for _, _, is_precision, iou_index, area_index, max_det in SUMMARIES:
-            per_class, mean = summarize(precision, recall, is_precision, iou_index, area_index, max_det)
+        for _, _, is_precision, iou_index, area_index, max_det in self.summaries:
+            per_class, mean = summarize(precision, recall, is_precision, iou_index, area_index, max_det,
+                                        self.max_detections)
             per_label = np.full(max(existent_labels) + 1, np.nan)
             per_label[existent_labels] = per_class
             summaries.append((per_label, mean))
-        results = to_tensorboard(summaries, existent_labels, self.per_class, self.classes)
+        results = to_tensorboard(summaries, existent_labels, self.per_class, self.classes, self.summaries)
         self.reset()
         return results

@@ -85,6 +85,8 @@ class _Sig:
     cnuda_eval_iou_rotated = (_I, [_P, _I, _I, _I, _LL, _P, _P, _I, _P] + _WS)
     cnuda_eval_iou_axis = (_I, [_P, _P, _P, _I, _I, _I, _LL, _P, _P])
     cnuda_eval_match = (_I, [_P, _P, _I, _P, _P, _I, _I, _LL, _P, _I, _P, _P, _P, _P])
+    cnuda_eval_match_flagged = (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _LL, _P, _I, _P, _P, _P, _P])
+    cnuda_eval_oks = (_I, [_P] * 6 + [_I, _P, _I, _I, _I, _LL, _P, _P, _P, _P])
     cnuda_conv2d_workspace_bytes = (c_size_t, [_I] * 11)
     cnuda_conv2d_forward = (_I, [_P] * 4 + [_I] * 11 + [_F] + _WS)
     cnuda_conv2d_forward_res = (_I, [_P] * 5 + [_I] * 11 + [_F] + _WS)

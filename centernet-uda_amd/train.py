@@ -102,8 +102,21 @@ def select_device(gpu):
     return torch.device('cuda', int(gpu))
 
 
+def wants_keypoint_visibility(evaluation, num_keypoints):
+    """Whether the validation and test batches must carry COCO's `v` flag: `coco_keypoints` is among the evaluators.
+    A model without keypoints cannot feed that evaluator: ValueError, before a dataset is read."""
+    if 'coco_keypoints' not in (evaluation or {}):
+        return False
+    if not num_keypoints:
+        raise ValueError("evaluation.coco_keypoints is configured but model.backend.params.num_keypoints is %r: a model "
+                         "without a keypoint head has no keypoint metrics; set num_keypoints (and kp_weight) or take "
+                         "coco_keypoints out of `evaluation`" % (num_keypoints,))
+    return True
+
+
 def load_datasets(cfg, device, down_ratio, rotated_boxes):
     from datasets.loader import DeviceLoader
+    visibility = wants_keypoint_visibility(cfg.evaluation, cfg.model.backend.params.num_keypoints)
     defaults = {"max_detections": cfg.max_detections,
                 "down_ratio": down_ratio,
                 "rotated_boxes": rotated_boxes,
@@ -112,7 +125,7 @@ def load_datasets(cfg, device, down_ratio, rotated_boxes):
                 "mean": cfg.normalize.mean,
                 "std": cfg.normalize.std}
 
-    def loader(split, shuffle):
+    def loader(split, shuffle, keypoint_visibility=False):
         spec = cfg.datasets[split]
         dataset = import_module('datasets.%s' % spec.name).Dataset(**{**spec.params, **defaults})
         log.info("Found %d samples in %s dataset", len(dataset), split)
@@ -120,11 +133,11 @@ def load_datasets(cfg, device, down_ratio, rotated_boxes):
                             device=device, seed=cfg.seed, num_classes=defaults["num_classes"],
                             num_keypoints=defaults["num_keypoints"], rotated_boxes=rotated_boxes,
                             down_ratio=down_ratio, mean=defaults["mean"], std=defaults["std"],
-                            max_detections=cfg.max_detections)
+                            max_detections=cfg.max_detections, keypoint_visibility=keypoint_visibility)
 
-    validation = loader('validation', False)
+    validation = loader('validation', False, visibility)
     training = loader('training', True)
-    test = loader('test', False) if 'test' in cfg.datasets else None
+    test = loader('test', False, visibility) if 'test' in cfg.datasets else None
     return training, validation, test
 
 

@@ -186,6 +186,9 @@ class Model:
             out['gt_areas'].append(areas[i, keep[i]])
         if has_kps:
             kps_gt = batch['gt_kps'].cpu().numpy() * ratio
+            if 'gt_kps_visibility' in batch:          # rows (x, y, v): the loader's keypoint_visibility=True
+                v = batch['gt_kps_visibility'].cpu().numpy().astype(kps_gt.dtype)
+                kps_gt = np.concatenate([kps_gt, v[..., None]], -1)
             out['gt_kps'] = [kps_gt[i, keep[i]] for i in range(gt.shape[0])]
             out['pred_kps'] = kps
         return out

@@ -330,6 +330,18 @@ int cnuda_dcn_v2_psroi_pooling_backward(const float* grad_output, const float* i
  *   (ties: the later one), else the ignored one by the same rule.  det_bits [num_det, 4]: bits 0..15 matched per
  *   threshold, bits 16..31 ignored per threshold (matched to an ignored ground truth, or unmatched with an area outside
  *   the range).  gt_ignore [num_gt, 4] bytes.  num_gt <= 16384 per call (one 32-bit word of LDS per ground truth).
+ * cnuda_eval_match_flagged: cnuda_eval_match with gt_flags [num_gt] bytes: a ground truth whose flag is not 0 is
+ *   ignored in every area range (COCOeval._prepare for keypoints: num_keypoints == 0), so a detection matched to it is
+ *   ignored, not a false positive.  One kernel serves both entries; cnuda_eval_match passes no flags.
+ * cnuda_eval_oks (evaluation/coco_keypoints.py): COCOeval.computeOks for every pair of every group, in float64 and in
+ *   this order of operations.  det_kps [num_det, J, 2] and gt_kps [num_gt, J, 2] float32 (x, y); gt_vis [num_gt, J]
+ *   bytes, COCO's v (a joint is labelled when v > 0); gt_area [num_gt] double; gt_box [num_gt, 4] float32 (x, y, w, h);
+ *   sigmas [J] double, on the DEVICE; 1 <= J <= 64.  var_j = (2 sigma_j)^2; k1 = labelled joints of the ground truth.
+ *   k1 > 0: dx_j = xd_j - xg_j, dy_j = yd_j - yg_j over the labelled joints.  k1 == 0: x0 = bx - bw, x1 = bx + 2 bw,
+ *   y0 = by - bh, y1 = by + 2 bh; dx_j = max(0, x0 - xd_j) + max(0, xd_j - x1), dy_j likewise, over all J joints.
+ *   e_j = (dx_j^2 + dy_j^2) / var_j / (area + 2^-52) / 2; oks = sum_j exp(-e_j) / n in ascending j, n = k1 or J.
+ *   The same call writes det_area [num_det] double, (max x - min x) * (max y - min y) over a detection's J joints (the
+ *   area COCO's loadRes gives a keypoint result), and gt_flags [num_gt] bytes, 1 where k1 == 0.  No fused multiply-add.
  * Integers and doubles only, no floating-point atomics: bit-stable.  Nothing synchronises the stream.
  * ---------------------------------------------------------------------- */
 size_t cnuda_eval_workspace_bytes(int num_boxes, int H);
@@ -344,6 +356,15 @@ int cnuda_eval_match(const double* iou, const int* groups, int num_groups, const
                      const double* gt_area, int num_det, int num_gt, long long num_pairs,
                      const double* thresholds, int num_thresholds, const double* area_ranges,
                      unsigned* det_bits, unsigned char* gt_ignore, cnuda_stream_t stream);
+int cnuda_eval_match_flagged(const double* iou, const int* groups, int num_groups, const double* det_area,
+                             const double* gt_area, const unsigned char* gt_flags, int num_det, int num_gt,
+                             long long num_pairs, const double* thresholds, int num_thresholds,
+                             const double* area_ranges, unsigned* det_bits, unsigned char* gt_ignore,
+                             cnuda_stream_t stream);
+int cnuda_eval_oks(const float* det_kps, const float* gt_kps, const unsigned char* gt_vis, const double* gt_area,
+                   const float* gt_box, const double* sigmas, int num_joints, const int* groups, int num_groups,
+                   int num_det, int num_gt, long long num_pairs, double* oks, double* det_area,
+                   unsigned char* gt_flags, cnuda_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Dense convolution (groups 1, dilation 1) -- replaces torch.nn.Conv2d -> cuDNN
