@@ -99,7 +99,8 @@ inline int stream_grid(long long work_items, int block) {
 // cnuda_tta_merge (predict.hip) must give the same bits for the same logit.
 constexpr float kProbLo = 1e-4f, kProbHi = 1.0f - 1e-4f;
 __device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float sigmoid_clamped(float x) { return fminf(fmaxf(sigmoid_f32(x), kProbLo), kProbHi); }
+__device__ __forceinline__ float clamp_prob(float s) { return fminf(fmaxf(s, kProbLo), kProbHi); }   // of a sigmoid already taken
+__device__ __forceinline__ float sigmoid_clamped(float x) { return clamp_prob(sigmoid_f32(x)); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

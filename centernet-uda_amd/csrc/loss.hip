@@ -7,15 +7,49 @@
 //   utils/image.py:121-124      entropy_map      losses/advent.py:10-18    BCE-with-logits vs constant
 // Every loss is a pair (forward -> scalar(s) in device memory, backward ->
 // gradient w.r.t. the logits given a device-resident upstream scalar).
+// The shared pieces keep every order of operations and so the bits: tests/test_gpu_loss_bits.py.
 #include "common.h"
 
 namespace cnuda {
 namespace {
 
 constexpr int kT = 256;
-constexpr float kLo = kProbLo, kHi = kProbHi;       // common.h: shared with predict.hip
+constexpr int kLossBlocks = 1024;
 
-__device__ __forceinline__ float sigmoidf_(float x) { return sigmoid_f32(x); }
+__device__ __forceinline__ float sgnf(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
+__device__ __forceinline__ bool in_clamp(float s) { return s >= kProbLo && s <= kProbHi; }   // clamp passes gradient
+
+// ---------------- the reduction tail ----------------
+// Every thread's N fp64 sums -> the block's (valid in thread 0), one after the other through `red`.  N is 1 or 3: the
+// loops over the sums unroll, and the sums stay in registers (no loss kernel has scratch: profiles/loss_dedupe_ab.txt).
+template <int N>
+__device__ __forceinline__ void block_sums(double (&acc)[N], double* red) {
+    for (int k = 0; k < N; ++k) acc[k] = block_sum(acc[k], red);
+}
+// The tail of a reducing forward: partial[blk*N + k] receives the block's k-th sum.  (The accumulation loop stays in the
+// kernel, on named sums: focal's three sums behind a lambda went to scratch or cost an add each per item.)
+template <int N>
+__device__ __forceinline__ void store_partials(double (&acc)[N], double* __restrict__ partial, double* red) {
+    block_sums(acc, red);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < N; ++k) partial[(size_t)blockIdx.x * N + k] = acc[k];
+}
+// One workgroup re-sums the `blocks` partial rows; epilogue(sums, out) turns them into the loss.
+template <class Epilogue>
+__global__ void finalize_kernel(const double* __restrict__ partial, int blocks, Epilogue epilogue,
+                                float* __restrict__ out) {
+    __shared__ double red[16];
+    double acc[Epilogue::N] = {};
+    for (int i = threadIdx.x; i < blocks; i += blockDim.x)
+        for (int k = 0; k < Epilogue::N; ++k) acc[k] += partial[(size_t)i * Epilogue::N + k];
+    block_sums(acc, red);
+    if (threadIdx.x == 0) epilogue(acc, out);
+}
+struct ScaleEpilogue {   // the scalar losses: out[0] = sum * scale
+    static constexpr int N = 1;
+    double scale;
+    __device__ void operator()(const double (&s)[1], float* out) const { out[0] = (float)(s[0] * scale); }
+};
 
 // ---------------- focal ----------------
 // partial[blk*3 + {0,1,2}] = sum pos_loss, sum neg_loss, num_pos
@@ -25,7 +59,7 @@ __global__ __launch_bounds__(kT) void focal_fwd_kernel(const float* __restrict__
     __shared__ double red[16];
     double ps = 0.0, ns = 0.0, np = 0.0;
     for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)gridDim.x * kT) {
-        const float p = fminf(fmaxf(sigmoidf_(logits[i]), kLo), kHi);
+        const float p = sigmoid_clamped(logits[i]);
         prob[i] = p;
         const float g = gt[i];
         if (g == 1.0f) {
@@ -33,40 +67,23 @@ __global__ __launch_bounds__(kT) void focal_fwd_kernel(const float* __restrict__
             ps += (double)(logf(p) * (q * q));
             np += 1.0;
         } else if (g < 1.0f) {
-            const float w = 1.0f - g;
-            const float w2 = w * w;
+            const float w = 1.0f - g, w2 = w * w;
             ns += (double)(logf(1.0f - p) * (p * p) * (w2 * w2));
         }
     }
-    ps = block_sum(ps, red);
-    ns = block_sum(ns, red);
-    np = block_sum(np, red);
-    if (threadIdx.x == 0) {
-        partial[(size_t)blockIdx.x * 3 + 0] = ps;
-        partial[(size_t)blockIdx.x * 3 + 1] = ns;
-        partial[(size_t)blockIdx.x * 3 + 2] = np;
-    }
+    double acc[3] = {ps, ns, np};
+    store_partials(acc, partial, red);
 }
-// out[0] = loss, out[1] = num_pos (kept for backward)
-__global__ void focal_finalize_kernel(const double* __restrict__ partial, int blocks, float weight,
-                                      float* __restrict__ out) {
-    __shared__ double red[16];
-    double ps = 0.0, ns = 0.0, np = 0.0;
-    for (int i = threadIdx.x; i < blocks; i += blockDim.x) {
-        ps += partial[(size_t)i * 3];
-        ns += partial[(size_t)i * 3 + 1];
-        np += partial[(size_t)i * 3 + 2];
-    }
-    ps = block_sum(ps, red);
-    ns = block_sum(ns, red);
-    np = block_sum(np, red);
-    if (threadIdx.x == 0) {
-        const float pos = (float)ps, neg = (float)ns, n = (float)np;
+struct FocalEpilogue {   // out[0] = loss, out[1] = num_pos (kept for backward)
+    static constexpr int N = 3;
+    float weight;
+    __device__ void operator()(const double (&s)[3], float* out) const {
+        const float pos = (float)s[0], neg = (float)s[1], n = (float)s[2];
         const float loss = (n == 0.0f) ? (0.0f - neg) : (0.0f - (pos + neg) / n);
         out[0] = loss * weight;
         out[1] = n;
     }
-}
+};
 // dlogits = upstream * weight * dL/dp * dp/dx
 __global__ void focal_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ gt,
                                  const float* __restrict__ fwd_out, const float* __restrict__ upstream, float weight,
@@ -74,9 +91,9 @@ __global__ void focal_bwd_kernel(const float* __restrict__ logits, const float* 
     const float np = fwd_out[1];
     const float scale = upstream[0] * weight * (np == 0.0f ? -1.0f : -1.0f / np);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float s = sigmoidf_(logits[i]);
+        const float s = sigmoid_f32(logits[i]);
         float gval = 0.0f;
-        if (s >= kLo && s <= kHi) {   // clamp passes gradient inside [min, max] only
+        if (in_clamp(s)) {
             const float p = s, q = 1.0f - s, g = gt[i];
             float dldp = 0.0f;
             if (g == 1.0f) {
@@ -91,213 +108,211 @@ __global__ void focal_bwd_kernel(const float* __restrict__ logits, const float* 
     }
 }
 
-// ---------------- gather + masked L1 (wh / reg / angle) ----------------
-// mode 0: plain (ch 2 or 3: with 3 channels = rotated non-periodic: angle through clamped sigmoid)
-// mode 1: periodic angle
-// out[0] = loss, out[1] = denominator (expanded-mask sum + 1e-4)
-// Single workgroup: B*M is a few thousand at most (M = max_detections).
+// ---------------- gather + masked L1: what the wh / reg / angle loss and the keypoint loss share ----------------
+// feat [B,ch,HW] is gathered at ind [B,M]; prediction and target are multiplied by the mask, the batch's target tensor
+// is masked in place (Q2); out[0] = loss, out[1] = denominator (expanded-mask sum + 1e-4): the backward divides by it.
+// The forwards run in a single workgroup (B*M*ch is tens of thousands at most, M = max_detections); the backwards
+// scatter-add into a zero-initialised grad [B,ch,HW].
 // `ind` comes from the data loader (datasets/coco.py:211).  The reference's torch.gather device-asserts on an index
 // outside [0, HW) (e.g. targets encoded for another output size); here such a row never touches memory: the forward
 // kernels read cell 0 instead and poison the loss with NaN (loud, no host sync), the backward kernels skip the row.
 __device__ __forceinline__ bool ind_ok(long long id, long long HW) { return id >= 0 && id < HW; }
+__device__ __forceinline__ long long fwd_cell(long long id, long long HW, double& poisoned) {
+    if (!ind_ok(id, HW)) { id = 0; poisoned = (double)NAN; }
+    return id;
+}
+struct L1Elem { int c, bm, b; };   // element i of a [B,M,ch] tensor: channel, row of [B,M], image
+__device__ __forceinline__ L1Elem l1_elem(int i, int ch, int M) { return {i % ch, i / ch, i / ch / M}; }
+__device__ __forceinline__ size_t feat_at(int b, int ch, int c, size_t HW, long long id) {
+    return ((size_t)b * ch + c) * HW + id;
+}
+// -> prediction * m; the masked target is returned and written back in place
+__device__ __forceinline__ float masked_pair(const float* __restrict__ feat, size_t cell, float* __restrict__ target,
+                                             size_t t, float m, float& tg) {
+    const float pred = feat[cell] * m;
+    tg = target[t] * m;
+    target[t] = tg;
+    return pred;
+}
+// s[0]: the main L1 sum, s[1]: the second term's (angle / pair distance), s[2]: the mask sum; valid in thread 0
+__device__ __forceinline__ void l1_epilogue(const double (&s)[3], float weight, bool second, float second_weight,
+                                            float* __restrict__ out) {
+    const float denom = (float)s[2] + 1e-4f;
+    float loss = (float)s[0] / denom * weight;
+    if (second) loss += (float)s[1] / denom * second_weight;
+    out[0] = loss;
+    out[1] = denom;
+}
+__device__ __forceinline__ float l1_upstream(const float* up, const float* fwd_out) { return up[0] / fwd_out[1]; }
 
+// ---------------- wh / reg / angle ----------------
+// mode 0: plain (ch 2 or 3: with 3 channels = rotated non-periodic: angle through clamped sigmoid)
+// mode 1: periodic angle
+constexpr float kPi = 3.14159265358979323846f;
+// PeriodicRegL1Loss: the clamped sigmoid `ps` spans (-pi, pi), the target is in degrees -> remainder(d - pi/2, pi) - pi/2
+__device__ __forceinline__ float periodic_residual(float ps, float tg) {
+    const float pa = ps * 2.0f * kPi - kPi;
+    const float ta = tg * (kPi / 180.0f);
+    float r = fmodf((pa - ta) - kPi / 2.0f, kPi);
+    if (r != 0.0f && r < 0.0f) r += kPi;   // torch.remainder: sign of the divisor
+    return r - kPi / 2.0f;
+}
 __global__ __launch_bounds__(kT) void regl1_fwd_kernel(const float* __restrict__ feat, const unsigned char* __restrict__ mask,
                                                        const long long* __restrict__ ind, float* __restrict__ target,
                                                        int B, int M, int ch, int HW, int mode, float weight,
                                                        float angle_weight, float* __restrict__ out) {
     __shared__ double red[16];
-    double s_wh = 0.0, s_a = 0.0, s_m = 0.0;
+    double s_wh = 0.0, s_a = 0.0, s_m = 0.0;   // named, not s[k]: the compiler then keeps one add per branch
     for (int i = threadIdx.x; i < B * M; i += kT) {
         const int b = i / M;
         const float m = mask[i] ? 1.0f : 0.0f;
-        long long id = ind[i];
-        if (!ind_ok(id, HW)) { id = 0; s_wh = (double)NAN; }
+        const long long id = fwd_cell(ind[i], HW, s_wh);
         for (int c = 0; c < ch; ++c) {
-            const float pred = feat[((size_t)b * ch + c) * HW + id] * m;
-            const float tg = target[(size_t)i * ch + c] * m;
-            target[(size_t)i * ch + c] = tg;   // in-place masking of the batch tensor (Q2)
+            const size_t t = (size_t)i * ch + c;
+            float tg;
+            const float pred = masked_pair(feat, feat_at(b, ch, c, HW, id), target, t, m, tg);
             s_m += (double)m;
             if (ch == 3 && c == 2) {
+                const float ps = sigmoid_clamped(pred);
                 if (mode == 0) {
-                    const float ps = fminf(fmaxf(sigmoidf_(pred), kLo), kHi);
-                    const float tsig = sigmoidf_(tg);
-                    target[(size_t)i * ch + c] = tsig;   // target[...,2:3].sigmoid_() is in place too (Q2)
-                    const float ts = fminf(fmaxf(tsig, kLo), kHi);
-                    s_a += (double)fabsf(ps - ts);
+                    const float tsig = sigmoid_f32(tg);
+                    target[t] = tsig;   // target[...,2:3].sigmoid_() is in place too (Q2)
+                    s_a += (double)fabsf(ps - clamp_prob(tsig));
                 } else {
-                    const float pi = 3.14159265358979323846f;
-                    const float pa = fminf(fmaxf(sigmoidf_(pred), kLo), kHi) * 2.0f * pi - pi;
-                    const float ta = tg * (pi / 180.0f);
-                    const float d = (pa - ta) - pi / 2.0f;
-                    float r = fmodf(d, pi);
-                    if (r != 0.0f && r < 0.0f) r += pi;   // torch.remainder: sign of the divisor
-                    s_a += (double)fabsf(r - pi / 2.0f);
+                    s_a += (double)fabsf(periodic_residual(ps, tg));
                 }
             } else {
                 s_wh += (double)fabsf(pred - tg);
             }
         }
     }
-    s_wh = block_sum(s_wh, red);
-    s_a = block_sum(s_a, red);
-    s_m = block_sum(s_m, red);
-    if (threadIdx.x == 0) {
-        const float denom = (float)s_m + 1e-4f;
-        float loss = (float)s_wh / denom * weight;
-        if (ch == 3) loss += (float)s_a / denom * angle_weight;
-        out[0] = loss;
-        out[1] = denom;
-    }
+    double s[3] = {s_wh, s_a, s_m};
+    block_sums(s, red);
+    if (threadIdx.x == 0) l1_epilogue(s, weight, ch == 3, angle_weight, out);
 }
-// scatter-add into a zero-initialised grad [B, ch, HW]; `target` is the (already masked / sigmoided) tensor
+// `target` is the (already masked / sigmoided) tensor
 __global__ void regl1_bwd_kernel(const float* __restrict__ feat, const unsigned char* __restrict__ mask,
                                  const long long* __restrict__ ind, const float* __restrict__ target,
                                  const float* __restrict__ fwd_out, const float* __restrict__ upstream, int B, int M,
                                  int ch, int HW, int mode, float weight, float angle_weight, float* __restrict__ grad) {
-    const float up = upstream[0] / fwd_out[1];
+    const float up = l1_upstream(upstream, fwd_out);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * M * ch; i += gridDim.x * blockDim.x) {
-        const int c = i % ch, bm = i / ch, b = bm / M;
-        if (!mask[bm]) continue;
-        const long long id = ind[bm];
+        const L1Elem e = l1_elem(i, ch, M);
+        if (!mask[e.bm]) continue;
+        const long long id = ind[e.bm];
         if (!ind_ok(id, HW)) continue;
-        const float pred = feat[((size_t)b * ch + c) * HW + id];
+        const size_t cell = feat_at(e.b, ch, e.c, HW, id);
+        const float pred = feat[cell];
         const float tg = target[i];
         float g;
-        if (ch == 3 && c == 2) {
-            const float s = sigmoidf_(pred);
-            const float ds = (s >= kLo && s <= kHi) ? s * (1.0f - s) : 0.0f;
-            const float ps = fminf(fmaxf(s, kLo), kHi);
-            if (mode == 0) {
-                const float ts = fminf(fmaxf(tg, kLo), kHi);   // target already holds sigmoid(target)
-                const float d = ps - ts;
-                g = (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * ds * angle_weight;
-            } else {
-                const float pi = 3.14159265358979323846f;
-                const float pa = ps * 2.0f * pi - pi, ta = tg * (pi / 180.0f);
-                float r = fmodf((pa - ta) - pi / 2.0f, pi);
-                if (r != 0.0f && r < 0.0f) r += pi;
-                const float e = r - pi / 2.0f;
-                g = (e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f)) * (2.0f * pi) * ds * angle_weight;
-            }
+        if (ch == 3 && e.c == 2) {
+            const float s = sigmoid_f32(pred);
+            const float ds = in_clamp(s) ? s * (1.0f - s) : 0.0f;
+            const float ps = clamp_prob(s);
+            if (mode == 0) g = sgnf(ps - clamp_prob(tg)) * ds * angle_weight;   // target already holds sigmoid(target)
+            else g = sgnf(periodic_residual(ps, tg)) * (2.0f * kPi) * ds * angle_weight;
         } else {
-            const float d = pred - tg;
-            g = (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * weight;
+            g = sgnf(pred - tg) * weight;
         }
-        atomicAdd(grad + ((size_t)b * ch + c) * HW + id, g * up);
+        atomicAdd(grad + cell, g * up);
     }
 }
 
 // ---------------- softmax-over-channels losses ----------------
+// One pixel's softmax over the channels: i -> (b, hw), the channel maximum, the denominator.  Channels are visited in
+// ascending order here and by every user; v(c) is recomputed at each use (C is 80 for COCO: no per-thread array).
+struct SoftmaxPixel {
+    const float* px;   // channel 0 of this pixel: x + base
+    size_t base, HW;
+    float mx, den;
+    __device__ __forceinline__ SoftmaxPixel(const float* x, long long i, int C, long long HW_) : HW(HW_) {
+        const long long b = i / HW_, hw = i - b * HW_;
+        base = (size_t)b * C * HW_ + hw;
+        px = x + base;
+        mx = px[0];
+        for (int c = 1; c < C; ++c) mx = fmaxf(mx, px[(size_t)c * HW]);
+        den = 0.0f;
+        for (int c = 0; c < C; ++c) den += expf(px[(size_t)c * HW] - mx);
+    }
+    __device__ __forceinline__ size_t at(int c) const { return base + (size_t)c * HW; }
+    __device__ __forceinline__ float v(int c) const { return expf(px[(size_t)c * HW] - mx) / den; }
+};
 // f(v) = v*log2(v + 1e-30);   f'(v) = log2(v + eps) + v / ((v + eps) ln 2)
 __device__ __forceinline__ float fent(float v) { return v * log2f(v + 1e-30f); }
 __device__ __forceinline__ float dfent(float v) { return log2f(v + 1e-30f) + v / ((v + 1e-30f) * 0.6931471805599453f); }
 
-// kind 0: entropy  sum_c f(v_c)         kind 1: max-squares  sum_c v_c^2
-__global__ __launch_bounds__(kT) void softmax_loss_fwd_kernel(const float* __restrict__ x, double* __restrict__ partial,
-                                                              int B, int C, long long HW, int kind) {
-    __shared__ double red[16];
-    double acc = 0.0;
-    const long long total = (long long)B * HW;
-    for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < total; i += (long long)gridDim.x * kT) {
-        const long long b = i / HW, hw = i - b * HW;
-        const float* px = x + (size_t)b * C * HW + hw;
-        float mx = px[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, px[(size_t)c * HW]);
-        float den = 0.0f;
-        for (int c = 0; c < C; ++c) den += expf(px[(size_t)c * HW] - mx);
-        float s = 0.0f;
-        for (int c = 0; c < C; ++c) {
-            const float v = expf(px[(size_t)c * HW] - mx) / den;
-            s += kind == 0 ? fent(v) : v * v;
-        }
-        acc += (double)s;
-    }
-    acc = block_sum(acc, red);
-    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-__global__ void scalar_finalize_kernel(const double* __restrict__ partial, int blocks, double scale,
-                                       float* __restrict__ out) {
-    __shared__ double red[16];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < blocks; i += blockDim.x) s += partial[i];
-    s = block_sum(s, red);
-    if (threadIdx.x == 0) out[0] = (float)(s * scale);
-}
-// dx_j = up*scale * v_j * (h_j - sum_i v_i h_i),  h = f'(v) (entropy) or 2v (max-squares)
-__global__ void softmax_loss_bwd_kernel(const float* __restrict__ x, const float* __restrict__ upstream, float scale,
-                                        float* __restrict__ grad, int B, int C, long long HW, int kind) {
-    const float up = upstream[0] * scale;
-    const long long total = (long long)B * HW;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const long long b = i / HW, hw = i - b * HW;
-        const float* px = x + (size_t)b * C * HW + hw;
-        float* pg = grad + (size_t)b * C * HW + hw;
-        float mx = px[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, px[(size_t)c * HW]);
-        float den = 0.0f;
-        for (int c = 0; c < C; ++c) den += expf(px[(size_t)c * HW] - mx);
-        float dot = 0.0f;
-        for (int c = 0; c < C; ++c) {
-            const float v = expf(px[(size_t)c * HW] - mx) / den;
-            dot += v * (kind == 0 ? dfent(v) : 2.0f * v);
-        }
-        for (int c = 0; c < C; ++c) {
-            const float v = expf(px[(size_t)c * HW] - mx) / den;
-            pg[(size_t)c * HW] = up * v * ((kind == 0 ? dfent(v) : 2.0f * v) - dot);
-        }
-    }
-}
+// A scalar softmax loss is scale * sum over pixels of pixel(sum_c each(v_c)).  Its term gives the host's scale and
+//   each(v), slope(v) = each'(v), pixel(s), and coef(up, s) = up * pixel'(s)   (up = upstream * scale)
+// so that dx_j = coef * v_j * (slope_j - sum_i v_i slope_i).  A term is built on the device from (C, param).
+struct EntropyTerm {     // EntropyLoss = -sum f(v) / (n*h*w*log2 c)
+    static double scale(int B, int C, long long HW) { return -1.0 / ((double)B * (double)HW * (double)log2f((float)C)); }
+    __device__ EntropyTerm(int, float) {}
+    __device__ float each(float v) const { return fent(v); }
+    __device__ float slope(float v) const { return dfent(v); }
+    __device__ float pixel(float s) const { return s; }
+    __device__ float coef(float up, float) const { return up; }
+};
+struct MaxSquareTerm {   // MaxSquareLoss = -mean(v^2)/2
+    static double scale(int B, int C, long long HW) { return -1.0 / (2.0 * (double)B * (double)C * (double)HW); }
+    __device__ MaxSquareTerm(int, float) {}
+    __device__ float each(float v) const { return v * v; }
+    __device__ float slope(float v) const { return 2.0f * v; }
+    __device__ float pixel(float s) const { return s; }
+    __device__ float coef(float up, float) const { return up; }
+};
 // eta-weighted entropy (losses/entropy.py:17-22, the FDA plugin's form): e = -sum_c f(v_c) / log2(C) per pixel,
-// loss = mean (e^2 + 1e-30)^eta
-__global__ __launch_bounds__(kT) void entropy_eta_fwd_kernel(const float* __restrict__ x, double* __restrict__ partial,
-                                                             int B, int C, long long HW, float eta) {
-    __shared__ double red[16];
-    const float inv = 1.0f / log2f((float)C);
-    double acc = 0.0;
-    const long long total = (long long)B * HW;
-    for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < total; i += (long long)gridDim.x * kT) {
-        const long long b = i / HW, hw = i - b * HW;
-        const float* px = x + (size_t)b * C * HW + hw;
-        float mx = px[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, px[(size_t)c * HW]);
-        float den = 0.0f;
-        for (int c = 0; c < C; ++c) den += expf(px[(size_t)c * HW] - mx);
-        float s = 0.0f;
-        for (int c = 0; c < C; ++c) s += fent(expf(px[(size_t)c * HW] - mx) / den);
+// loss = mean (e^2 + 1e-30)^eta;  d/de = 2 eta e (e^2 + 1e-30)^(eta-1)
+struct EtaEntropyTerm {
+    float eta, inv;
+    static double scale(int B, int, long long HW) { return 1.0 / ((double)B * (double)HW); }
+    __device__ EtaEntropyTerm(int C, float eta_) : eta(eta_), inv(1.0f / log2f((float)C)) {}
+    __device__ float each(float v) const { return fent(v); }
+    __device__ float slope(float v) const { return dfent(v); }
+    __device__ float pixel(float s) const {
         const float e = -s * inv;
-        acc += (double)powf(e * e + 1e-30f, eta);
+        return powf(e * e + 1e-30f, eta);
     }
-    acc = block_sum(acc, red);
-    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-// dx_j = up/(B HW) * 2 eta e (e^2 + 1e-30)^(eta-1) * (-1/log2 C) * v_j (f'_j - sum_i v_i f'_i)
-__global__ void entropy_eta_bwd_kernel(const float* __restrict__ x, const float* __restrict__ upstream, float scale,
-                                       float eta, float* __restrict__ grad, int B, int C, long long HW) {
-    const float up = upstream[0] * scale;
-    const float inv = 1.0f / log2f((float)C);
-    const long long total = (long long)B * HW;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const long long b = i / HW, hw = i - b * HW;
-        const float* px = x + (size_t)b * C * HW + hw;
-        float* pg = grad + (size_t)b * C * HW + hw;
-        float mx = px[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, px[(size_t)c * HW]);
-        float den = 0.0f;
-        for (int c = 0; c < C; ++c) den += expf(px[(size_t)c * HW] - mx);
-        float s = 0.0f, dot = 0.0f;
-        for (int c = 0; c < C; ++c) {
-            const float v = expf(px[(size_t)c * HW] - mx) / den;
-            s += fent(v);
-            dot += v * dfent(v);
-        }
+    __device__ float coef(float up, float s) const {
         const float e = -s * inv;
         const float ge = 2.0f * eta * e * powf(e * e + 1e-30f, eta - 1.0f);
-        const float k = -up * ge * inv;
+        return -up * ge * inv;
+    }
+};
+template <class Term>
+__global__ __launch_bounds__(kT) void softmax_reduce_kernel(const float* __restrict__ x, double* __restrict__ partial,
+                                                            int B, int C, long long HW, float param) {
+    __shared__ double red[16];
+    const Term term(C, param);
+    double acc[1] = {};
+    const long long total = (long long)B * HW;
+    for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < total; i += (long long)gridDim.x * kT) {
+        const SoftmaxPixel p(x, i, C, HW);
+        float s = 0.0f;
+        for (int c = 0; c < C; ++c) s += term.each(p.v(c));
+        acc[0] += (double)term.pixel(s);
+    }
+    store_partials(acc, partial, red);
+}
+template <class Term>
+__global__ void softmax_grad_kernel(const float* __restrict__ x, const float* __restrict__ upstream, float scale,
+                                    float* __restrict__ grad, int B, int C, long long HW, float param) {
+    const float up = upstream[0] * scale;
+    const Term term(C, param);
+    const long long total = (long long)B * HW;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const SoftmaxPixel p(x, i, C, HW);
+        float s = 0.0f, dot = 0.0f;
         for (int c = 0; c < C; ++c) {
-            const float v = expf(px[(size_t)c * HW] - mx) / den;
-            pg[(size_t)c * HW] = k * v * (dfent(v) - dot);
+            const float v = p.v(c);
+            s += term.each(v);
+            dot += v * term.slope(v);
+        }
+        const float k = term.coef(up, s);
+        float* pg = grad + p.base;
+        for (int c = 0; c < C; ++c) {
+            const float v = p.v(c);
+            pg[(size_t)c * p.HW] = k * v * (term.slope(v) - dot);
         }
     }
 }
@@ -308,17 +323,8 @@ __global__ void entropy_map_fwd_kernel(const float* __restrict__ x, float* __res
     const long long total = (long long)B * HW;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
-        const long long b = i / HW, hw = i - b * HW;
-        const float* px = x + (size_t)b * C * HW + hw;
-        float* po = out + (size_t)b * C * HW + hw;
-        float mx = px[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, px[(size_t)c * HW]);
-        float den = 0.0f;
-        for (int c = 0; c < C; ++c) den += expf(px[(size_t)c * HW] - mx);
-        for (int c = 0; c < C; ++c) {
-            const float v = expf(px[(size_t)c * HW] - mx) / den;
-            po[(size_t)c * HW] = -fent(v) * inv;
-        }
+        const SoftmaxPixel p(x, i, C, HW);
+        for (int c = 0; c < C; ++c) out[p.at(c)] = -fent(p.v(c)) * inv;
     }
 }
 // gx_j = -(1/log2 C) * v_j * (g_j f'_j - sum_i g_i f'_i v_i)
@@ -328,21 +334,15 @@ __global__ void entropy_map_bwd_kernel(const float* __restrict__ x, const float*
     const long long total = (long long)B * HW;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
-        const long long b = i / HW, hw = i - b * HW;
-        const size_t base = (size_t)b * C * HW + hw;
-        const float* px = x + base;
-        float mx = px[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, px[(size_t)c * HW]);
-        float den = 0.0f;
-        for (int c = 0; c < C; ++c) den += expf(px[(size_t)c * HW] - mx);
+        const SoftmaxPixel p(x, i, C, HW);
         float dot = 0.0f;
         for (int c = 0; c < C; ++c) {
-            const float v = expf(px[(size_t)c * HW] - mx) / den;
-            dot += gout[base + (size_t)c * HW] * dfent(v) * v;
+            const float v = p.v(c);
+            dot += gout[p.at(c)] * dfent(v) * v;
         }
         for (int c = 0; c < C; ++c) {
-            const float v = expf(px[(size_t)c * HW] - mx) / den;
-            grad[base + (size_t)c * HW] = -inv * v * (gout[base + (size_t)c * HW] * dfent(v) - dot);
+            const float v = p.v(c);
+            grad[p.at(c)] = -inv * v * (gout[p.at(c)] * dfent(v) - dot);
         }
     }
 }
@@ -351,27 +351,27 @@ __global__ void entropy_map_bwd_kernel(const float* __restrict__ x, const float*
 __global__ __launch_bounds__(kT) void bce_const_fwd_kernel(const float* __restrict__ x, float label, long long n,
                                                            float* __restrict__ out) {
     __shared__ double red[16];
-    double acc = 0.0;
+    double acc[1] = {};
     for (long long i = threadIdx.x; i < n; i += kT) {
         const float v = x[i];
-        acc += (double)(fmaxf(v, 0.0f) - v * label + log1pf(expf(-fabsf(v))));
+        acc[0] += (double)(fmaxf(v, 0.0f) - v * label + log1pf(expf(-fabsf(v))));
     }
-    acc = block_sum(acc, red);
-    if (threadIdx.x == 0) out[0] = (float)(acc / (double)n);
+    block_sums(acc, red);
+    if (threadIdx.x == 0) out[0] = (float)(acc[0] / (double)n);
 }
 __global__ void bce_const_bwd_kernel(const float* __restrict__ x, float label, const float* __restrict__ upstream,
                                      long long n, float* __restrict__ grad) {
     const float up = upstream[0] / (float)n;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        grad[i] = (sigmoidf_(x[i]) - label) * up;
+        grad[i] = (sigmoid_f32(x[i]) - label) * up;
 }
 
 // y = clamp(sigmoid(x)); x <- sigmoid(x) in place (x.sigmoid_())
 __global__ void sigmoid_clamp_kernel(float* __restrict__ x, float* __restrict__ y, long long n) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float s = sigmoidf_(x[i]);
+        const float s = sigmoid_f32(x[i]);
         x[i] = s;
-        y[i] = fminf(fmaxf(s, kLo), kHi);
+        y[i] = clamp_prob(s);
     }
 }
 
@@ -381,7 +381,6 @@ __global__ void sigmoid_clamp_kernel(float* __restrict__ x, float* __restrict__ 
 //   loss  = sum |pred*m - tg*m| / (sum m + 1e-4) * weight
 //         + sum_{b,m,p} |d(pred_a, pred_b) - d(tg_a, tg_b)| / (sum m + 1e-4) * distance_weight
 //   d = L1 norm (use_l1) or sqrt(|.|^2 + 1e4)  (the literal 1e4 of :178-179)
-// out[0] = loss, out[1] = sum m + 1e-4.  Single workgroup (B*M*2J is tens of thousands at most).
 __device__ __forceinline__ float kps_dist(float ax, float ay, float bx, float by, int use_l1) {
     const float dx = ax - bx, dy = ay - by;
     return use_l1 ? fabsf(dx) + fabsf(dy) : sqrtf((dx * dx + dy * dy) + 1e4f);
@@ -393,17 +392,15 @@ __global__ __launch_bounds__(kT) void kpsl1_fwd_kernel(const float* __restrict__
                                                        float* __restrict__ out) {
     __shared__ double red[16];
     const int ch = 2 * J;
-    double s_l1 = 0.0, s_m = 0.0, s_d = 0.0;
+    double s[3] = {};   // L1, pair distance, mask
     for (int i = threadIdx.x; i < B * M * ch; i += kT) {
-        const int c = i % ch, bm = i / ch, b = bm / M;
+        const L1Elem e = l1_elem(i, ch, M);
         const float m = mask[i] ? 1.0f : 0.0f;
-        long long id = ind[bm];
-        if (!ind_ok(id, HW)) { id = 0; s_l1 = (double)NAN; }
-        const float pred = feat[((size_t)b * ch + c) * HW + id] * m;
-        const float tg = target[i] * m;
-        target[i] = tg;                                   // in place, like the reference
-        s_m += (double)m;
-        s_l1 += (double)fabsf(pred - tg);
+        const long long id = fwd_cell(ind[e.bm], HW, s[0]);
+        float tg;
+        const float pred = masked_pair(feat, feat_at(e.b, ch, e.c, HW, id), target, i, m, tg);
+        s[2] += (double)m;
+        s[0] += (double)fabsf(pred - tg);
     }
     __syncthreads();                                      // the pair term reads the masked targets
     for (int i = threadIdx.x; i < B * M * P; i += kT) {
@@ -413,35 +410,26 @@ __global__ __launch_bounds__(kT) void kpsl1_fwd_kernel(const float* __restrict__
         auto pm = [&](int c) { return feat[fb + (size_t)c * HW] * (mask[tb + c] ? 1.0f : 0.0f); };
         const float pd = kps_dist(pm(2 * ja), pm(2 * ja + 1), pm(2 * jb), pm(2 * jb + 1), use_l1);
         const float td = kps_dist(target[tb + 2 * ja], target[tb + 2 * ja + 1], target[tb + 2 * jb], target[tb + 2 * jb + 1], use_l1);
-        s_d += (double)fabsf(pd - td);
+        s[1] += (double)fabsf(pd - td);
     }
-    s_l1 = block_sum(s_l1, red);
-    s_m = block_sum(s_m, red);
-    s_d = block_sum(s_d, red);
-    if (threadIdx.x == 0) {
-        const float denom = (float)s_m + 1e-4f;
-        float loss = (float)s_l1 / denom * weight;
-        if (P > 0) loss += (float)s_d / denom * distance_weight;
-        out[0] = loss;
-        out[1] = denom;
-    }
+    block_sums(s, red);
+    if (threadIdx.x == 0) l1_epilogue(s, weight, P > 0, distance_weight, out);
 }
-__device__ __forceinline__ float sgnf(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
-// scatter-add into a zero-initialised grad [B, 2J, HW]; `target` already masked
+// `target` already masked
 __global__ void kpsl1_bwd_kernel(const float* __restrict__ feat, const unsigned char* __restrict__ mask,
                                  const long long* __restrict__ ind, const float* __restrict__ target,
                                  const int* __restrict__ pairs, const float* __restrict__ fwd_out,
                                  const float* __restrict__ upstream, int B, int M, int J, int HW, int P, int use_l1,
                                  float weight, float distance_weight, float* __restrict__ grad) {
     const int ch = 2 * J;
-    const float up = upstream[0] / fwd_out[1];
+    const float up = l1_upstream(upstream, fwd_out);
     const int n1 = B * M * ch, n2 = B * M * P;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n1 + n2; i += gridDim.x * blockDim.x) {
         if (i < n1) {
-            const int c = i % ch, bm = i / ch, b = bm / M;
-            if (!mask[i] || !ind_ok(ind[bm], HW)) continue;
-            const float pred = feat[((size_t)b * ch + c) * HW + ind[bm]];
-            atomicAdd(grad + ((size_t)b * ch + c) * HW + ind[bm], sgnf(pred - target[i]) * weight * up);
+            const L1Elem e = l1_elem(i, ch, M);
+            if (!mask[i] || !ind_ok(ind[e.bm], HW)) continue;
+            const size_t cell = feat_at(e.b, ch, e.c, HW, ind[e.bm]);
+            atomicAdd(grad + cell, sgnf(feat[cell] - target[i]) * weight * up);
         } else {
             const int k = i - n1, pr = k % P, bm = k / P, b = bm / M;
             const int ja = pairs[2 * pr], jb = pairs[2 * pr + 1];
@@ -487,28 +475,44 @@ __global__ void gather_feat_kernel(const float* __restrict__ feat, const long lo
     }
 }
 
-constexpr int kLossBlocks = 1024;
-
 }  // namespace
 }  // namespace cnuda
 
 using namespace cnuda;
 
 extern "C" size_t cnuda_loss_workspace_bytes(void) { return (size_t)kLossBlocks * 3 * sizeof(double) + 512; }
-
 static double* ws_ptr(void* ws) { return reinterpret_cast<double*>(((uintptr_t)ws + 255) & ~(uintptr_t)255); }
+
+// A reducing forward on the host, `who` the entry point's name for the error texts: the grid over `items` is capped at
+// kLossBlocks, launch(blocks, partial) starts the loss's own kernel, finalize_kernel<Epilogue> writes `out`.
+template <class Epilogue, class Launch>
+static int reduced_loss(const char* who, void* workspace, size_t workspace_bytes, long long items, hipStream_t st,
+                        Epilogue epilogue, float* out, Launch launch) {
+    CNUDA_REQUIRE(workspace && workspace_bytes >= cnuda_loss_workspace_bytes(), "%s: workspace", who);
+    int blocks = stream_grid(items, kT);
+    if (blocks > kLossBlocks) blocks = kLossBlocks;
+    double* partial = ws_ptr(workspace);
+    launch(blocks, partial);
+    CNUDA_LAUNCH(finalize_kernel<Epilogue>, dim3(1), dim3(kT), 0, st, partial, blocks, epilogue, out);
+    return check_launch(who);
+}
+// A masked-L1 backward on the host: zero the gradient, then launch() scatters into it.
+template <class Launch>
+static int scattered_grad(const char* who, const char* who_memset, float* grad, size_t cells, hipStream_t st,
+                          Launch launch) {
+    if (hipMemsetAsync(grad, 0, cells * sizeof(float), st) != hipSuccess) return check_launch(who_memset);
+    launch();
+    return check_launch(who);
+}
 
 extern "C" int cnuda_focal_loss_forward(const float* logits, const float* gt, float* prob, float* out2, long long n,
                                         float weight, void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
     CNUDA_REQUIRE(logits && gt && prob && out2 && n > 0, "cnuda_focal_loss_forward: bad arguments");
-    CNUDA_REQUIRE(workspace && workspace_bytes >= cnuda_loss_workspace_bytes(), "cnuda_focal_loss_forward: workspace");
     hipStream_t st = (hipStream_t)stream;
-    int blocks = stream_grid(n, kT);
-    if (blocks > kLossBlocks) blocks = kLossBlocks;
-    double* partial = ws_ptr(workspace);
-    CNUDA_LAUNCH(focal_fwd_kernel, dim3(blocks), dim3(kT), 0, st, logits, gt, prob, partial, n);
-    CNUDA_LAUNCH(focal_finalize_kernel, dim3(1), dim3(kT), 0, st, partial, blocks, weight, out2);
-    return check_launch("cnuda_focal_loss_forward");
+    return reduced_loss("cnuda_focal_loss_forward", workspace, workspace_bytes, n, st, FocalEpilogue{weight}, out2,
+                        [&](int blocks, double* partial) {
+        CNUDA_LAUNCH(focal_fwd_kernel, dim3(blocks), dim3(kT), 0, st, logits, gt, prob, partial, n);
+    });
 }
 extern "C" int cnuda_focal_loss_backward(const float* logits, const float* gt, const float* out2,
                                          const float* upstream, float* grad_logits, long long n, float weight,
@@ -535,12 +539,12 @@ extern "C" int cnuda_reg_l1_backward(const float* feat, const uint8_t* mask, con
     CNUDA_REQUIRE(feat && mask && ind && target && out2 && upstream && grad_feat && B > 0 && M > 0 && HW > 0,
                   "cnuda_reg_l1_backward: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(grad_feat, 0, (size_t)B * ch * HW * sizeof(float), st) != hipSuccess)
-        return check_launch("cnuda_reg_l1_backward(memset)");
-    CNUDA_LAUNCH(regl1_bwd_kernel, dim3(stream_grid((long long)B * M * ch, kT)), dim3(kT), 0, st, feat, mask,
-                       (const long long*)ind, target, out2, upstream, B, M, ch, (int)HW, periodic ? 1 : 0, weight,
-                       angle_weight, grad_feat);
-    return check_launch("cnuda_reg_l1_backward");
+    return scattered_grad("cnuda_reg_l1_backward", "cnuda_reg_l1_backward(memset)", grad_feat, (size_t)B * ch * HW, st,
+                          [&] {
+        CNUDA_LAUNCH(regl1_bwd_kernel, dim3(stream_grid((long long)B * M * ch, kT)), dim3(kT), 0, st, feat, mask,
+                     (const long long*)ind, target, out2, upstream, B, M, ch, (int)HW, periodic ? 1 : 0, weight,
+                     angle_weight, grad_feat);
+    });
 }
 
 extern "C" int cnuda_kps_l1_forward(const float* feat, const uint8_t* mask, const int64_t* ind, float* target,
@@ -559,12 +563,12 @@ extern "C" int cnuda_kps_l1_backward(const float* feat, const uint8_t* mask, con
     CNUDA_REQUIRE(feat && mask && ind && target && out2 && upstream && grad_feat && B > 0 && M > 0 && J > 0 && HW > 0 &&
                       n_pairs >= 0 && (n_pairs == 0 || pairs), "cnuda_kps_l1_backward: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(grad_feat, 0, (size_t)B * 2 * J * HW * sizeof(float), st) != hipSuccess)
-        return check_launch("cnuda_kps_l1_backward(memset)");
-    CNUDA_LAUNCH(kpsl1_bwd_kernel, dim3(stream_grid((long long)B * M * (2 * J + n_pairs), kT)), dim3(kT), 0, st, feat,
-                       mask, (const long long*)ind, target, (const int*)pairs, out2, upstream, B, M, J, (int)HW, n_pairs,
-                       use_l1 ? 1 : 0, weight, distance_weight, grad_feat);
-    return check_launch("cnuda_kps_l1_backward");
+    return scattered_grad("cnuda_kps_l1_backward", "cnuda_kps_l1_backward(memset)", grad_feat, (size_t)B * 2 * J * HW,
+                          st, [&] {
+        CNUDA_LAUNCH(kpsl1_bwd_kernel, dim3(stream_grid((long long)B * M * (2 * J + n_pairs), kT)), dim3(kT), 0, st,
+                     feat, mask, (const long long*)ind, target, (const int*)pairs, out2, upstream, B, M, J, (int)HW, n_pairs,
+                     use_l1 ? 1 : 0, weight, distance_weight, grad_feat);
+    });
 }
 extern "C" int cnuda_decode_keypoints(const float* kps, const float* reg, const int64_t* inds, float* out, int B, int J,
                                       int K, int H, int W, cnuda_stream_t stream) {
@@ -574,55 +578,50 @@ extern "C" int cnuda_decode_keypoints(const float* kps, const float* reg, const 
     return check_launch("cnuda_decode_keypoints");
 }
 
-// kind 0: EntropyLoss  = -sum f(v) / (n*h*w*log2 c);  kind 1: MaxSquareLoss = -mean(v^2)/2
-static double softmax_loss_scale(int kind, int B, int C, long long HW) {
-    if (kind == 0) return -1.0 / ((double)B * (double)HW * (double)log2f((float)C));
-    return -1.0 / (2.0 * (double)B * (double)C * (double)HW);
+// The scalar softmax losses: the term's scale multiplies the pixel sum (forward) and the upstream scalar (backward).
+template <class Term>
+static int softmax_loss_forward(const char* who, const float* logits, float* out1, int B, int C, long long HW,
+                                float param, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    return reduced_loss(who, workspace, workspace_bytes, (long long)B * HW, st, ScaleEpilogue{Term::scale(B, C, HW)},
+                        out1, [&](int blocks, double* partial) {
+        CNUDA_LAUNCH(softmax_reduce_kernel<Term>, dim3(blocks), dim3(kT), 0, st, logits, partial, B, C, HW, param);
+    });
 }
+template <class Term>
+static int softmax_loss_backward(const char* who, const float* logits, const float* upstream, float* grad_logits, int B,
+                                 int C, long long HW, float param, hipStream_t st) {
+    CNUDA_LAUNCH(softmax_grad_kernel<Term>, dim3(stream_grid((long long)B * HW, kT)), dim3(kT), 0, st, logits, upstream,
+                 (float)Term::scale(B, C, HW), grad_logits, B, C, HW, param);
+    return check_launch(who);
+}
+// kind 0: EntropyLoss, kind 1: MaxSquareLoss
 extern "C" int cnuda_softmax_loss_forward(const float* logits, float* out1, int B, int C, long long HW, int kind,
                                           void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
     CNUDA_REQUIRE(logits && out1 && B > 0 && C > 0 && HW > 0 && (kind == 0 || kind == 1),
                   "cnuda_softmax_loss_forward: bad arguments");
-    CNUDA_REQUIRE(workspace && workspace_bytes >= cnuda_loss_workspace_bytes(), "cnuda_softmax_loss_forward: workspace");
-    hipStream_t st = (hipStream_t)stream;
-    int blocks = stream_grid((long long)B * HW, kT);
-    if (blocks > kLossBlocks) blocks = kLossBlocks;
-    double* partial = ws_ptr(workspace);
-    CNUDA_LAUNCH(softmax_loss_fwd_kernel, dim3(blocks), dim3(kT), 0, st, logits, partial, B, C, HW, kind);
-    CNUDA_LAUNCH(scalar_finalize_kernel, dim3(1), dim3(kT), 0, st, partial, blocks,
-                       softmax_loss_scale(kind, B, C, HW), out1);
-    return check_launch("cnuda_softmax_loss_forward");
+    const auto forward = kind == 0 ? softmax_loss_forward<EntropyTerm> : softmax_loss_forward<MaxSquareTerm>;
+    return forward("cnuda_softmax_loss_forward", logits, out1, B, C, HW, 0.0f, workspace, workspace_bytes,
+                   (hipStream_t)stream);
 }
 extern "C" int cnuda_softmax_loss_backward(const float* logits, const float* upstream, float* grad_logits, int B, int C,
                                            long long HW, int kind, cnuda_stream_t stream) {
     CNUDA_REQUIRE(logits && upstream && grad_logits && B > 0 && C > 0 && HW > 0 && (kind == 0 || kind == 1),
                   "cnuda_softmax_loss_backward: bad arguments");
-    CNUDA_LAUNCH(softmax_loss_bwd_kernel, dim3(stream_grid((long long)B * HW, kT)), dim3(kT), 0,
-                       (hipStream_t)stream, logits, upstream, (float)softmax_loss_scale(kind, B, C, HW), grad_logits, B,
-                       C, HW, kind);
-    return check_launch("cnuda_softmax_loss_backward");
+    const auto backward = kind == 0 ? softmax_loss_backward<EntropyTerm> : softmax_loss_backward<MaxSquareTerm>;
+    return backward("cnuda_softmax_loss_backward", logits, upstream, grad_logits, B, C, HW, 0.0f, (hipStream_t)stream);
 }
 extern "C" int cnuda_entropy_eta_loss_forward(const float* logits, float* out1, int B, int C, long long HW, float eta,
                                               void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
     CNUDA_REQUIRE(logits && out1 && B > 0 && C > 0 && HW > 0, "cnuda_entropy_eta_loss_forward: bad arguments");
-    CNUDA_REQUIRE(workspace && workspace_bytes >= cnuda_loss_workspace_bytes(),
-                  "cnuda_entropy_eta_loss_forward: workspace");
-    hipStream_t st = (hipStream_t)stream;
-    int blocks = stream_grid((long long)B * HW, kT);
-    if (blocks > kLossBlocks) blocks = kLossBlocks;
-    double* partial = ws_ptr(workspace);
-    CNUDA_LAUNCH(entropy_eta_fwd_kernel, dim3(blocks), dim3(kT), 0, st, logits, partial, B, C, HW, eta);
-    CNUDA_LAUNCH(scalar_finalize_kernel, dim3(1), dim3(kT), 0, st, partial, blocks, 1.0 / ((double)B * (double)HW),
-                 out1);
-    return check_launch("cnuda_entropy_eta_loss_forward");
+    return softmax_loss_forward<EtaEntropyTerm>("cnuda_entropy_eta_loss_forward", logits, out1, B, C, HW, eta, workspace,
+                                                workspace_bytes, (hipStream_t)stream);
 }
 extern "C" int cnuda_entropy_eta_loss_backward(const float* logits, const float* upstream, float* grad_logits, int B,
                                                int C, long long HW, float eta, cnuda_stream_t stream) {
     CNUDA_REQUIRE(logits && upstream && grad_logits && B > 0 && C > 0 && HW > 0,
                   "cnuda_entropy_eta_loss_backward: bad arguments");
-    CNUDA_LAUNCH(entropy_eta_bwd_kernel, dim3(stream_grid((long long)B * HW, kT)), dim3(kT), 0, (hipStream_t)stream,
-                 logits, upstream, (float)(1.0 / ((double)B * (double)HW)), eta, grad_logits, B, C, HW);
-    return check_launch("cnuda_entropy_eta_loss_backward");
+    return softmax_loss_backward<EtaEntropyTerm>("cnuda_entropy_eta_loss_backward", logits, upstream, grad_logits, B, C,
+                                                 HW, eta, (hipStream_t)stream);
 }
 extern "C" int cnuda_entropy_map_forward(const float* logits, float* out, int B, int C, long long HW,
                                          cnuda_stream_t stream) {

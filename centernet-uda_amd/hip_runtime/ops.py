@@ -996,37 +996,50 @@ def focal_loss(logits, gt, weight=1.0, return_den=False):
     return (loss, prob, den) if return_den else (loss, prob)
 
 
+def _l1_batch_check(name, expected, mask, ind, target):
+    """dtypes and contiguity of the batch tensors of a gather + masked-L1 loss (`expected`: the loss's own wording)."""
+    if mask.dtype != torch.uint8 or ind.dtype != torch.int64 or target.dtype != torch.float32:
+        raise RuntimeError("%s: expected %s, got %s/%s/%s" % (name, expected, mask.dtype, ind.dtype, target.dtype))
+    if not (mask.is_contiguous() and ind.is_contiguous() and target.is_contiguous()):
+        raise RuntimeError("%s: batch tensors must be contiguous (target is updated in place)" % name)
+
+
+def _l1_forward_tail(ctx, feat, mask, ind, target, out2):
+    ctx.save_for_backward(feat, mask, ind, target, out2)
+    den = out2[1].clone()                      # expanded-mask sum + 1e-4
+    ctx.mark_non_differentiable(den)
+    return out2[0].clone(), den
+
+
+def _l1_backward(ctx, gloss, name, *pairs):
+    """-> gradient w.r.t. feat; `pairs`: the pointer the keypoint entry point takes between target and out2."""
+    feat, mask, ind, target, out2 = ctx.saved_tensors
+    grad = torch.empty_like(feat)
+    up = f32c(gloss.reshape(1))
+    check(getattr(lib(), 'cnuda_' + name)(ptr(feat), ptr(mask), ptr(ind), ptr(target), *pairs, ptr(out2), ptr(up),
+                                          ptr(grad), *ctx.args, stream()), name)
+    return grad
+
+
 class _RegL1(Function):
     @staticmethod
     def forward(ctx, feat, mask, ind, target, periodic, weight, angle_weight):
         require_gpu(feat, mask, ind, target)
         feat = f32c(feat)
-        if mask.dtype != torch.uint8 or ind.dtype != torch.int64 or target.dtype != torch.float32:
-            raise RuntimeError("reg_l1: expected reg_mask uint8, ind int64, target float32 "
-                               "(datasets/coco.py:168-174), got %s/%s/%s" % (mask.dtype, ind.dtype, target.dtype))
-        if not (mask.is_contiguous() and ind.is_contiguous() and target.is_contiguous()):
-            raise RuntimeError("reg_l1: batch tensors must be contiguous (target is updated in place)")
+        _l1_batch_check('reg_l1', 'reg_mask uint8, ind int64, target float32 (datasets/coco.py:168-174)',
+                        mask, ind, target)
         B, ch, H, W = feat.shape
         M = ind.shape[1]
         out2 = torch.empty(2, dtype=torch.float32, device=feat.device)
-        check(lib().cnuda_reg_l1_forward(ptr(feat), ptr(mask), ptr(ind), ptr(target), ptr(out2), B, M, ch, H * W,
-                                         1 if periodic else 0, float(weight), float(angle_weight), stream()),
-              'reg_l1_forward')
         ctx.args = (B, M, ch, H * W, 1 if periodic else 0, float(weight), float(angle_weight))
-        ctx.save_for_backward(feat, mask, ind, target, out2)
-        den = out2[1].clone()                      # expanded-mask sum + 1e-4
-        ctx.mark_non_differentiable(den)
-        return out2[0].clone(), den
+        check(lib().cnuda_reg_l1_forward(ptr(feat), ptr(mask), ptr(ind), ptr(target), ptr(out2), *ctx.args, stream()),
+              'reg_l1_forward')
+        return _l1_forward_tail(ctx, feat, mask, ind, target, out2)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gloss, _gden):
-        feat, mask, ind, target, out2 = ctx.saved_tensors
-        grad = torch.empty_like(feat)
-        up = f32c(gloss.reshape(1))
-        check(lib().cnuda_reg_l1_backward(ptr(feat), ptr(mask), ptr(ind), ptr(target), ptr(out2), ptr(up), ptr(grad),
-                                          *ctx.args, stream()), 'reg_l1_backward')
-        return grad, None, None, None, None, None, None
+        return _l1_backward(ctx, gloss, 'reg_l1_backward'), None, None, None, None, None, None
 
 
 def reg_l1_loss(feat, mask, ind, target, periodic=False, weight=1.0, angle_weight=1.0, return_den=False):
@@ -1040,11 +1053,8 @@ class _KpsL1(Function):
     def forward(ctx, feat, mask, ind, target, pairs, use_l1, weight, distance_weight):
         require_gpu(feat, mask, ind, target)
         feat = f32c(feat)
-        if mask.dtype != torch.uint8 or ind.dtype != torch.int64 or target.dtype != torch.float32:
-            raise RuntimeError("kps_l1: expected kp_reg_mask uint8, ind int64, kps float32 "
-                               "(datasets/coco.py:183-189), got %s/%s/%s" % (mask.dtype, ind.dtype, target.dtype))
-        if not (mask.is_contiguous() and ind.is_contiguous() and target.is_contiguous()):
-            raise RuntimeError("kps_l1: batch tensors must be contiguous (target is updated in place)")
+        _l1_batch_check('kps_l1', 'kp_reg_mask uint8, ind int64, kps float32 (datasets/coco.py:183-189)',
+                        mask, ind, target)
         B, ch, H, W = feat.shape
         M = ind.shape[1]
         if ch % 2 or tuple(target.shape) != (B, M, ch) or tuple(mask.shape) != (B, M, ch):
@@ -1056,20 +1066,12 @@ class _KpsL1(Function):
         check(lib().cnuda_kps_l1_forward(ptr(feat), ptr(mask), ptr(ind), ptr(target), ptr(pairs), ptr(out2), *ctx.args,
                                          stream()), 'kps_l1_forward')
         ctx.pairs = pairs
-        ctx.save_for_backward(feat, mask, ind, target, out2)
-        den = out2[1].clone()
-        ctx.mark_non_differentiable(den)
-        return out2[0].clone(), den
+        return _l1_forward_tail(ctx, feat, mask, ind, target, out2)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gloss, _gden):
-        feat, mask, ind, target, out2 = ctx.saved_tensors
-        grad = torch.empty_like(feat)
-        up = f32c(gloss.reshape(1))
-        check(lib().cnuda_kps_l1_backward(ptr(feat), ptr(mask), ptr(ind), ptr(target), ptr(ctx.pairs), ptr(out2), ptr(up),
-                                          ptr(grad), *ctx.args, stream()), 'kps_l1_backward')
-        return grad, None, None, None, None, None, None, None
+        return _l1_backward(ctx, gloss, 'kps_l1_backward', ptr(ctx.pairs)), None, None, None, None, None, None, None
 
 
 def kps_l1_loss(feat, mask, ind, target, pairs=None, use_l1=False, weight=1.0, distance_weight=0.1, return_den=False):
@@ -1079,124 +1081,70 @@ def kps_l1_loss(feat, mask, ind, target, pairs=None, use_l1=False, weight=1.0, d
     return (loss, den) if return_den else loss
 
 
-class _SoftmaxLoss(Function):
+class _LogitsLoss(Function):
+    """The losses of the logits alone.  `spec` = (stem, flat, workspace, is_map) names cnuda_<stem>_forward/_backward and
+    their argument layout: logits, [extra scalars if flat], out, shape, [extra scalars if not flat], [loss workspace],
+    stream -- the backward takes (upstream, grad) in the place of out and no workspace.  The shape is (numel) when
+    flat, (B, C, HW) otherwise; the result is a scalar with a scalar upstream, or (is_map) a tensor like the logits
+    with a full upstream tensor."""
+
     @staticmethod
-    def forward(ctx, logits, kind):
+    def forward(ctx, logits, spec, *extra):
+        stem, flat, workspace, is_map = spec
         require_gpu(logits)
         logits = f32c(logits)
-        B, C = logits.shape[0], logits.shape[1]
-        HW = logits.numel() // (B * C)
-        out = torch.empty(1, dtype=torch.float32, device=logits.device)
-        wp, wn = _loss_ws(logits)
-        check(lib().cnuda_softmax_loss_forward(ptr(logits), ptr(out), B, C, HW, kind, wp, wn, stream()),
-              'softmax_loss_forward')
-        ctx.args = (B, C, HW, kind)
+        if flat:
+            lead, shape = extra, (logits.numel(),)
+        else:
+            B, C = logits.shape[0], logits.shape[1]
+            lead, shape = (), (B, C, logits.numel() // (B * C)) + extra
+        out = torch.empty_like(logits) if is_map else torch.empty(1, dtype=torch.float32, device=logits.device)
+        ws = _loss_ws(logits) if workspace else ()
+        check(getattr(lib(), 'cnuda_%s_forward' % stem)(ptr(logits), *lead, ptr(out), *shape, *ws, stream()),
+              stem + '_forward')
+        ctx.call = (stem, is_map, lead, shape, len(extra))
         ctx.save_for_backward(logits)
-        return out[0].clone()
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gloss):
-        (logits,) = ctx.saved_tensors
-        grad = torch.empty_like(logits)
-        up = f32c(gloss.reshape(1))
-        check(lib().cnuda_softmax_loss_backward(ptr(logits), ptr(up), ptr(grad), *ctx.args, stream()),
-              'softmax_loss_backward')
-        return grad, None
-
-
-def entropy_loss(hm_logits):
-    return _SoftmaxLoss.apply(hm_logits, 0)
-
-
-def max_square_loss(hm_logits):
-    return _SoftmaxLoss.apply(hm_logits, 1)
-
-
-class _EntropyEtaLoss(Function):
-    @staticmethod
-    def forward(ctx, logits, eta):
-        require_gpu(logits)
-        logits = f32c(logits)
-        B, C = logits.shape[0], logits.shape[1]
-        HW = logits.numel() // (B * C)
-        out = torch.empty(1, dtype=torch.float32, device=logits.device)
-        wp, wn = _loss_ws(logits)
-        check(lib().cnuda_entropy_eta_loss_forward(ptr(logits), ptr(out), B, C, HW, float(eta), wp, wn, stream()),
-              'entropy_eta_loss_forward')
-        ctx.args = (B, C, HW, float(eta))
-        ctx.save_for_backward(logits)
-        return out[0].clone()
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gloss):
-        (logits,) = ctx.saved_tensors
-        grad = torch.empty_like(logits)
-        up = f32c(gloss.reshape(1))
-        check(lib().cnuda_entropy_eta_loss_backward(ptr(logits), ptr(up), ptr(grad), *ctx.args, stream()),
-              'entropy_eta_loss_backward')
-        return grad, None
-
-
-def entropy_eta_loss(hm_logits, eta):
-    """EntropyLoss(eta) (losses/entropy.py:17-22): mean over pixels of (e^2 + 1e-30)^eta, e the normalised softmax
-    entropy over the channels."""
-    return _EntropyEtaLoss.apply(hm_logits, eta)
-
-
-class _EntropyMap(Function):
-    @staticmethod
-    def forward(ctx, logits):
-        require_gpu(logits)
-        logits = f32c(logits)
-        B, C = logits.shape[0], logits.shape[1]
-        HW = logits.numel() // (B * C)
-        out = torch.empty_like(logits)
-        check(lib().cnuda_entropy_map_forward(ptr(logits), ptr(out), B, C, HW, stream()), 'entropy_map_forward')
-        ctx.args = (B, C, HW)
-        ctx.save_for_backward(logits)
-        return out
+        return out if is_map else out[0].clone()
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
         (logits,) = ctx.saved_tensors
+        stem, is_map, lead, shape, n_extra = ctx.call
         grad = torch.empty_like(logits)
-        check(lib().cnuda_entropy_map_backward(ptr(logits), ptr(f32c(g)), ptr(grad), *ctx.args, stream()),
-              'entropy_map_backward')
-        return grad
+        up = f32c(g if is_map else g.reshape(1))
+        check(getattr(lib(), 'cnuda_%s_backward' % stem)(ptr(logits), *lead, ptr(up), ptr(grad), *shape, stream()),
+              stem + '_backward')
+        return (grad, None) + (None,) * n_extra
+
+
+#                     stem            flat  workspace  is_map        extra scalars
+_SOFTMAX_LOSS     = ('softmax_loss',     False, True,  False)      # kind: 0 entropy, 1 max-squares
+_ENTROPY_ETA_LOSS = ('entropy_eta_loss', False, True,  False)      # eta
+_ENTROPY_MAP      = ('entropy_map',      False, False, True)
+_BCE_CONST        = ('bce_const',        True,  False, False)      # label
+
+
+def entropy_loss(hm_logits):
+    return _LogitsLoss.apply(hm_logits, _SOFTMAX_LOSS, 0)
+
+
+def max_square_loss(hm_logits):
+    return _LogitsLoss.apply(hm_logits, _SOFTMAX_LOSS, 1)
+
+
+def entropy_eta_loss(hm_logits, eta):
+    """EntropyLoss(eta) (losses/entropy.py:17-22): mean over pixels of (e^2 + 1e-30)^eta, e the normalised softmax
+    entropy over the channels."""
+    return _LogitsLoss.apply(hm_logits, _ENTROPY_ETA_LOSS, float(eta))
 
 
 def entropy_map(hm):
-    return _EntropyMap.apply(hm)
-
-
-class _BceConst(Function):
-    @staticmethod
-    def forward(ctx, logits, label):
-        require_gpu(logits)
-        logits = f32c(logits)
-        out = torch.empty(1, dtype=torch.float32, device=logits.device)
-        check(lib().cnuda_bce_const_forward(ptr(logits), float(label), ptr(out), logits.numel(), stream()),
-              'bce_const_forward')
-        ctx.label = float(label)
-        ctx.save_for_backward(logits)
-        return out[0].clone()
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gloss):
-        (logits,) = ctx.saved_tensors
-        grad = torch.empty_like(logits)
-        up = f32c(gloss.reshape(1))
-        check(lib().cnuda_bce_const_backward(ptr(logits), ctx.label, ptr(up), ptr(grad), logits.numel(), stream()),
-              'bce_const_backward')
-        return grad, None
+    return _LogitsLoss.apply(hm, _ENTROPY_MAP)
 
 
 def bce_with_logits_const(logits, label):
-    return _BceConst.apply(logits, label)
+    return _LogitsLoss.apply(logits, _BCE_CONST, float(label))
 
 
 # ---------------------------------------------------------------------------

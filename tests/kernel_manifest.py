@@ -217,7 +217,7 @@ MANIFEST = {
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_keypoint_detection_loss_golden',
     ],
-    'focal_finalize_kernel': [
+    'finalize_kernel<FocalEpilogue>': [
         'tests/test_gpu_losses.py::test_detection_loss_golden',
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_keypoint_detection_loss_golden',
@@ -390,7 +390,7 @@ MANIFEST = {
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_keypoint_detection_loss_golden',
     ],
-    'scalar_finalize_kernel': [
+    'finalize_kernel<ScaleEpilogue>': [
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_uda_losses_golden',
         'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
@@ -449,13 +449,21 @@ MANIFEST = {
         'tests/test_gpu_ops.py::test_conv2d_fwd_bwd[stem7x7',
         'tests/test_gpu_ops.py::test_convolution_epilogue_leaves_batchnorm_statistics[B2C3H24W72Co16k7s1g2',
     ],
-    'softmax_loss_bwd_kernel': [
+    'softmax_grad_kernel<EntropyTerm>': [
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_uda_losses_golden',
         'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
     ],
-    'softmax_loss_fwd_kernel': [
+    'softmax_grad_kernel<MaxSquareTerm>': [
+        'tests/test_gpu_losses.py::test_uda_losses_golden',
+        'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
+    ],
+    'softmax_reduce_kernel<EntropyTerm>': [
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
+        'tests/test_gpu_losses.py::test_uda_losses_golden',
+        'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
+    ],
+    'softmax_reduce_kernel<MaxSquareTerm>': [
         'tests/test_gpu_losses.py::test_uda_losses_golden',
         'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
     ],
