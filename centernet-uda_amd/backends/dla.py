@@ -566,9 +566,17 @@ class DLASeg(nn.Module):
         self.ida_up(y, 0, len(y), fan)
         return y[-1].take()
 
+    def _head_order(self, dense=('hm',)):
+        """The heads in the order they are evaluated: those whose gradient is a dense map (`dense`) LAST, so that the
+        backward pass runs them first -- their input gradient takes the feature map's slot with a plain write and the
+        others (the source half of a batched step; a position-sparse gradient's scatter) add theirs on top."""
+        return sorted(self.heads, key=lambda h: h in dense)
+
     def forward(self, x):
         feat = self.features(x)
-        return {head: getattr(self, head)(f) for head, f in zip(self.heads, fork(feat, len(self.heads)))}
+        order = self._head_order()
+        out = {head: getattr(self, head)(f) for head, f in zip(order, fork(feat, len(order)))}
+        return {h: out[h] for h in self.heads}        # (the dictionary keeps the heads' own order)
 
     def forward_domains(self, source, target, target_grad_heads=('hm',)):
         """Both domains' forward passes of a UDA step (uda/entropy_minimization.py:18-19) as ONE pass over the
@@ -592,7 +600,7 @@ class DLASeg(nn.Module):
         # one alias of the feature map per head (hip_runtime.fanout).  The heads that only see the source half come first:
         # the backward pass then runs the whole-batch heads first, their gradient takes the map's slot with a plain write
         # and the source-half heads add theirs on top of its leading images
-        order = sorted(self.heads, key=lambda h: h in target_grad_heads)
+        order = self._head_order(target_grad_heads)
         for head, f in zip(order, fork(feat, len(order))):
             fc = getattr(self, head)
             if head in target_grad_heads or not torch.is_grad_enabled():

@@ -136,6 +136,9 @@ class _Sig:
     cnuda_add = (_I, [_P] * 3 + [_LL, _P])
     cnuda_act_backward = (_I, [_P] * 3 + [_LL, _F, _P])
     cnuda_conv1x1_backward_data_act = (_I, [_P] * 4 + [_I] * 3 + [_LL, _F, _P])
+    cnuda_head_backward_sparse_supported = (_I, [_I] * 13)
+    cnuda_head_backward_sparse_workspace_bytes = (c_size_t, [_I] * 9)
+    cnuda_head_backward_sparse = (_I, [_P] * 12 + [_I] * 9 + [_F] + _WS)
     cnuda_copy_channels = (_I, [_P, _P, _I, _I, _LL, _I, _I, _I, _I, _P])
     cnuda_split_offset_mask = (_I, [_P] * 3 + [_I, _I, _LL, _P])
     cnuda_split_offset_mask_backward = (_I, [_P] * 4 + [_I, _I, _LL, _P])

@@ -3,6 +3,7 @@ gfx950 kernels from libcenternet_uda_hip.so on torch's current HIP stream;
 torch contributes tensors (device memory), the autograd tape and nothing else.
 """
 import ctypes
+import os
 
 import torch
 from torch.autograd import Function
@@ -194,6 +195,31 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act_slope=-1.0, pack_token
                                                                box, norm, None))
 
 
+# CNUDA_HEAD_SPARSE=0 (or ops.HEAD_SPARSE = False): a head whose gradient is the gather + masked-L1 loss's takes the dense
+# backward like every other (A/B measurements: profiles/ab_bench.sh - CNUDA_HEAD_SPARSE=0)
+HEAD_SPARSE = os.environ.get('CNUDA_HEAD_SPARSE', '1') != '0'
+# The size rule of the sparse head backward, held here only: it is taken while HEAD_SPARSE_RATIO * M <= H * W.  Its cost
+# grows with M (two 1x1 GEMMs over B * M rows, a gather, a scatter), the dense cost with H * W.  Measured on the real head
+# (64 -> 256 -> 2, B = 16, every row active; profiles/head_sparse_ab.txt): the two meet at H * W = 19 M on the 128 x 128
+# map (5 M on the 32 x 32 map, where both are launch-bound); twice the larger, rounded up.
+HEAD_SPARSE_RATIO = 40
+
+
+def _mark_sparse_rows(grad, ind, mask, B, M, HW):
+    """`grad` [B, ch, HW] is zero outside the cells ind[b, m] with mask[b, m] set (_RegL1.backward wrote it so).  The mark is
+    an attribute of this tensor OBJECT and names the version it was written at: a sum of two gradients, a hook's result,
+    a retain_grad copy or a clone is another object and carries none."""
+    grad._cnuda_sparse_rows = (ind, mask, B, M, HW, grad._version)
+
+
+def _sparse_rows_of(gy, B, HW):
+    """The (ind, mask, M) of a valid mark on `gy` for a head of B images and HW pixels, consumed; else None."""
+    mark = gy.__dict__.pop('_cnuda_sparse_rows', None)
+    if mark is None or mark[5] != gy._version or mark[2] != B or mark[4] != HW or not gy.is_contiguous():
+        return None
+    return mark[0], mark[1], mark[3]
+
+
 class _ConvActConv1x1(Function):
     """A detection head, `nn.Sequential(Conv2d(C, Ch, k, padding) + ReLU, Conv2d(Ch, Co, 1))` (dla.py:474-483), as one
     tape node: the two forward launches are the ones two `_Conv2d` nodes make; backward computes the hidden map's
@@ -231,6 +257,11 @@ class _ConvActConv1x1(Function):
         if gy.data_ptr() % 16:                 # (a view at an odd offset: the fused pass reads 16 bytes at a time)
             gy = gy.clone()
         B, Ch, Co = g1[0], g1[4], g2[4]
+        rows = _sparse_rows_of(gy, B, hidden.shape[2] * hidden.shape[3])
+        if rows is not None and HEAD_SPARSE:
+            sparse = _ConvActConv1x1._backward_sparse(ctx, gy, *rows)
+            if sparse is not None:
+                return sparse
         gx = gw1 = gb1 = gw2 = gb2 = None
         if ctx.needs_input_grad[3] or (ctx.has_b2 and ctx.needs_input_grad[4]):
             gw2, gb2 = _conv_wgrad(g2, hidden, gy, w2, b2)
@@ -252,6 +283,41 @@ class _ConvActConv1x1(Function):
             _conv_dgrad(g1, gh, w1, part, addend, addend2, ctx.token1)
         if ctx.needs_input_grad[1] or (ctx.has_b1 and ctx.needs_input_grad[2]):
             gw1, gb1 = _conv_wgrad(g1, x, gh, w1, b1)
+        return gx, gw1, gb1, gw2, gb2, None, None, None, None, None
+
+    @staticmethod
+    def _backward_sparse(ctx, gy, ind, mask, M):
+        """backward() for a `gy` that is zero outside ind[b, m] where mask[b, m] (cnuda_head_backward_sparse): no gradient of
+        the hidden map, no full-size GEMM.  The share of x's gradient is ADDED to the slot's buffer -- the consumer class of
+        DCN's atomics and the max-pool scatter -- or to a zero-filled tensor that takes an empty slot.  -> backward()'s
+        result, or None where the dense path has to run: a geometry the library does not take, a map too small for the
+        size rule, a slot whose buffer belongs to somebody else."""
+        x, w1, b1, w2, b2, hidden = ctx.saved_tensors
+        B, C, H, W, Ch, kh, kw, sh, sw, ph, pw = ctx.g1
+        Co = ctx.g2[4]
+        L = lib()
+        HW = hidden.shape[2] * hidden.shape[3]
+        if HEAD_SPARSE_RATIO * M > HW or \
+                not L.cnuda_head_backward_sparse_supported(B, M, C, H, W, Ch, Co, kh, kw, sh, sw, ph, pw):
+            return None
+        gx = part = None
+        if ctx.needs_input_grad[0]:
+            slot = ctx.slot
+            if slot is not None and slot.buf is not None and not slot.owned:
+                return None
+            gx = accumulate_in_place(slot)
+            if gx is None:
+                gx = claim(slot, torch.zeros(ctx.full or x.shape, dtype=torch.float32, device=x.device))
+            part = gx[:B]
+        gw1 = gb1 = gw2 = gb2 = gw1_buf = gb1_buf = gw2_buf = gb2_buf = None
+        if ctx.needs_input_grad[1] or (ctx.has_b1 and ctx.needs_input_grad[2]):
+            (gw1_buf, gw1), (gb1_buf, gb1) = _param_grad(w1), _param_grad(b1)
+        if ctx.needs_input_grad[3] or (ctx.has_b2 and ctx.needs_input_grad[4]):
+            (gw2_buf, gw2), (gb2_buf, gb2) = _param_grad(w2), _param_grad(b2)
+        wp, wn = _ws(L.cnuda_head_backward_sparse_workspace_bytes(B, M, C, H, W, Ch, Co, kh, kw), x)
+        check(L.cnuda_head_backward_sparse(ptr(gy), ptr(ind), ptr(mask), ptr(x), ptr(hidden), ptr(w1), ptr(w2), ptr(part),
+                                           ptr(gw1_buf), ptr(gb1_buf), ptr(gw2_buf), ptr(gb2_buf), B, M, C, H, W, Ch, Co, kh, kw,
+                                           ctx.act_slope, wp, wn, stream()), 'head_backward_sparse')
         return gx, gw1, gb1, gw2, gb2, None, None, None, None, None
 
 
@@ -1011,13 +1077,17 @@ def _l1_forward_tail(ctx, feat, mask, ind, target, out2):
     return out2[0].clone(), den
 
 
-def _l1_backward(ctx, gloss, name, *pairs):
-    """-> gradient w.r.t. feat; `pairs`: the pointer the keypoint entry point takes between target and out2."""
+def _l1_backward(ctx, gloss, name, *pairs, rows_mark=False):
+    """-> gradient w.r.t. feat; `pairs`: the pointer the keypoint entry point takes between target and out2.
+    rows_mark: mask is [B, M] -- the dense map also says where it can be non-zero (_mark_sparse_rows: a detection head's
+    backward then skips the zeros, _ConvActConv1x1._backward_sparse)."""
     feat, mask, ind, target, out2 = ctx.saved_tensors
     grad = torch.empty_like(feat)
     up = f32c(gloss.reshape(1))
     check(getattr(lib(), 'cnuda_' + name)(ptr(feat), ptr(mask), ptr(ind), ptr(target), *pairs, ptr(out2), ptr(up),
                                           ptr(grad), *ctx.args, stream()), name)
+    if rows_mark and tuple(mask.shape) == tuple(ind.shape):
+        _mark_sparse_rows(grad, ind, mask, feat.shape[0], ind.shape[1], feat.shape[2] * feat.shape[3])
     return grad
 
 
@@ -1039,7 +1109,7 @@ class _RegL1(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gloss, _gden):
-        return _l1_backward(ctx, gloss, 'reg_l1_backward'), None, None, None, None, None, None
+        return _l1_backward(ctx, gloss, 'reg_l1_backward', rows_mark=True), None, None, None, None, None, None
 
 
 def reg_l1_loss(feat, mask, ind, target, periodic=False, weight=1.0, angle_weight=1.0, return_den=False):

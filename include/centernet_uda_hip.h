@@ -572,6 +572,25 @@ int cnuda_act_backward(const float* grad_y, const float* y, float* grad_x, long 
  * grad_hidden [B, Ch, HW] (HW % 4 == 0), grad_y [B, Co, HW]; channels summed in increasing order. */
 int cnuda_conv1x1_backward_data_act(const float* grad_y, const float* weight, const float* hidden, float* grad_hidden,
                                     int B, int Co, int Ch, long long HW, float slope, cnuda_stream_t stream);
+/* The whole backward of a detection head -- conv(C -> Ch, kh x kw, stride 1, "same" padding) + act + conv1x1(Ch -> Co) --
+ * for a grad_y [B, Co, HW] that is zero outside the cells ind[b][m] with mask[b][m] != 0 (the gradient of the gather +
+ * masked-L1 loss, cnuda_reg_l1_backward).  The active rows (mask set, 0 <= ind < HW, first of the rows of its image with that
+ * ind: the dense map already holds the sum of duplicates) are gathered into compact [channels][R] matrices, R = B * M
+ * rounded up to 4, inactive rows zero; the parameter gradients and the patch gradients are 1x1 convolution calls over
+ * them (cnuda_conv2d_backward_weight / _backward_data: fixed-order sums), the patch gradients are added to grad_x by plain
+ * read-add-write -- rows with no other row within kh - 1 pixels in parallel, the others of an image in row order -- so
+ * every result is run-to-run bit-reproducible.  x, hidden: the B images the head saw; grad_x [B, C, H, W] is ADDED to (nullable); grad_w1 [Ch, C, kh, kw],
+ * grad_b1 [Ch], grad_w2 [Co, Ch], grad_b2 [Co] are written (each nullable).  Values: those of cnuda_conv2d_backward_weight,
+ * cnuda_conv1x1_backward_data_act and cnuda_conv2d_backward_data on the dense map up to the order of the sums.
+ * _supported: stride 1, 1 <= Co <= 8, odd kh == kw <= 7 with ph == pw == (kh - 1) / 2, M <= 4096, B * M < 2^20. */
+int cnuda_head_backward_sparse_supported(int B, int M, int C, int H, int W, int Ch, int Co, int kh, int kw, int sh, int sw,
+                                         int ph, int pw);
+size_t cnuda_head_backward_sparse_workspace_bytes(int B, int M, int C, int H, int W, int Ch, int Co, int kh, int kw);
+int cnuda_head_backward_sparse(const float* grad_y, const long long* ind, const unsigned char* mask, const float* x,
+                               const float* hidden, const float* w1, const float* w2, float* grad_x, float* grad_w1,
+                               float* grad_b1, float* grad_w2, float* grad_b2, int B, int M, int C, int H, int W, int Ch,
+                               int Co, int kh, int kw, float slope, void* workspace, size_t workspace_bytes,
+                               cnuda_stream_t stream);
 int cnuda_copy_channels(const float* src, float* dst, int B, int Cn, long long HW,
                         int Csrc, int src_off, int Cdst, int dst_off, cnuda_stream_t stream);
 int cnuda_split_offset_mask(const float* om, float* offset, float* mask, int B, int taps, long long HW,
