@@ -368,23 +368,29 @@ const void* g_refresh_table = nullptr;        // the device buffer the current j
 }  // namespace
 }  // namespace cnuda
 
-extern "C" int cnuda_pack_refresh(const void* params, size_t params_bytes, unsigned long long old_epoch,
-                                  unsigned long long new_epoch, void* table, size_t table_bytes,
-                                  cnuda_stream_t stream) {
+extern "C" int cnuda_pack_refresh_ranges(const void* const* params, const size_t* params_bytes, int ranges,
+                                         unsigned long long old_epoch, unsigned long long new_epoch, void* table,
+                                         size_t table_bytes, cnuda_stream_t stream) {
     using namespace cnuda;
+    CNUDA_REQUIRE(ranges >= 0 && (ranges == 0 || (params && params_bytes)), "cnuda_pack_refresh_ranges: null ranges");
     std::lock_guard<std::mutex> lock(g_pack_mutex);
-    if (!g_pack_arena || g_pack_slots.empty()) return 0;
-    const char* lo = static_cast<const char*>(params);
-    const char* hi = lo + params_bytes;
+    if (!g_pack_arena || g_pack_slots.empty() || ranges == 0) return 0;
+    auto rewritten = [&](const char* src) {
+        for (int r = 0; r < ranges; ++r) {
+            const char* lo = static_cast<const char*>(params[r]);
+            if (src >= lo && src < lo + params_bytes[r]) return true;
+        }
+        return false;
+    };
     hipStream_t st = (hipStream_t)stream;
-    // jobs: slots whose source lies inside the arena and whose image was current in the epoch that just ended
+    // jobs: slots whose source lies inside a rewritten buffer and whose image was current in the epoch that just ended
     // (anything else refills lazily on its next use)
     std::vector<PackSlot*> live;
     std::vector<PackJob> jobs;
     unsigned blocks = 0;
     for (auto& kv : g_pack_slots) {
         const char* src = static_cast<const char*>(kv.first.src);
-        if (src < lo || src >= hi || kv.first.token == 0) continue;
+        if (kv.first.token == 0 || !rewritten(src)) continue;
         if ((kv.second.version >> 32) != (old_epoch & 0xffffffffull)) continue;
         live.push_back(&kv.second);
         PackJob j;
@@ -416,6 +422,12 @@ extern "C" int cnuda_pack_refresh(const void* params, size_t params_bytes, unsig
                        (int)g_refresh_jobs.size());
     for (PackSlot* sl : live) sl->version = ((new_epoch & 0xffffffffull) << 32) | (sl->version & 0xffffffffull);
     return check_launch("cnuda_pack_refresh");
+}
+
+extern "C" int cnuda_pack_refresh(const void* params, size_t params_bytes, unsigned long long old_epoch,
+                                  unsigned long long new_epoch, void* table, size_t table_bytes,
+                                  cnuda_stream_t stream) {
+    return cnuda_pack_refresh_ranges(&params, &params_bytes, 1, old_epoch, new_epoch, table, table_bytes, stream);
 }
 
 extern "C" int cnuda_pack_stamp(unsigned long long token, unsigned long long version) {

@@ -69,14 +69,19 @@ class CenterNet(nn.Module):
         return (dets[:, :, :4], dets[:, :, 4], dets[:, :, 5]) + extra
 
 
-def build_model(experiment, model_spec, without_decode_detections, max_detections, nms=3, use_last=True):
-    """export.py:59-85: backend from `{'name', 'params'}`, weights from the experiment folder if present."""
+def build_model(experiment, model_spec, without_decode_detections, max_detections, nms=3, use_last=True,
+                state_key='state_dict'):
+    """export.py:59-85: backend from `{'name', 'params'}`, weights from the experiment folder if present.
+    state_key: the checkpoint entry to load ('teacher_state_dict': the mean teacher of a uda.MeanTeacher run); a
+    checkpoint without it is a KeyError that names the file."""
     module = import_module("backends.%s" % model_spec['name'])
     backend = getattr(module, 'build')(**model_spec['params'])
     ckpt = Path(experiment) / ('model_last.pth' if use_last else 'model_best.pth')
     if ckpt.exists():
         checkpoint = torch.load(ckpt, map_location='cpu', weights_only=False)
-        backend.load_state_dict(checkpoint['state_dict'])
+        if state_key not in checkpoint:
+            raise KeyError("%s holds no %r (its entries: %s)" % (ckpt, state_key, ', '.join(sorted(checkpoint))))
+        backend.load_state_dict(checkpoint[state_key])
         print("Restore weights %s successful!" % ckpt)
     else:
         print("No weights were found in folder %s" % experiment)

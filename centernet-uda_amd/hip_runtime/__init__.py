@@ -184,6 +184,9 @@ class _Sig:
     cnuda_pack_cache_attach = (_I, [_P, c_size_t])
     cnuda_pack_stamp = (_I, [ctypes.c_ulonglong, ctypes.c_ulonglong])
     cnuda_pack_refresh = (_I, [_P, ctypes.c_size_t, ctypes.c_ulonglong, ctypes.c_ulonglong, _P, ctypes.c_size_t, _P])
+    cnuda_pack_refresh_ranges = (_I, [_P, _P, _I, ctypes.c_ulonglong, ctypes.c_ulonglong, _P, ctypes.c_size_t, _P])
+    cnuda_ema_update = (_I, [_P, _I, ctypes.c_uint, _F, _F, _P])
+    cnuda_pseudo_labels = (_I, [_P] * 6 + [_I] * 6 + [_F, _P])
     cnuda_pack_cache_used = (c_size_t, [])
     cnuda_pack_cache_fills = (ctypes.c_ulonglong, [])
     cnuda_pack_cache_resets = (ctypes.c_ulonglong, [])
@@ -214,8 +217,20 @@ _PARAM_EPOCH = 0
 def bump_param_epoch(rewritten=None):
     """`rewritten`: the flat tensor whose contents just changed (the fused Adam's parameter arena).  Every packed weight
     image of the pack cache that was built from it in the epoch that ends here is rebuilt by one launch and carried
-    into the new epoch (cnuda_pack_refresh) -- instead of ~150 small pack launches spread over the next step."""
+    into the new epoch (cnuda_pack_refresh) -- instead of ~150 small pack launches spread over the next step.
+    A list or tuple of such tensors: all of them were rewritten since the last bump (cnuda_pack_refresh_ranges)."""
     global _PARAM_EPOCH
+    if rewritten is not None and not isinstance(rewritten, torch.Tensor):
+        # several buffers rewritten since the last bump (a student's arena and its mean teacher's flat copy): ONE epoch
+        # step and one refresh launch carry the images of all of them.  Two bumps in a row would strand both models'
+        # images: the second one only carries what the first one's epoch built, which is nothing.
+        several = [t for t in rewritten if t is not None]
+        if len(several) > 1:
+            return _bump_several(several)
+        rewritten = several[0] if several else None
+    if _HELD is not None:                       # inside a `single_param_epoch` block: its end bumps once for all
+        _HELD.append(rewritten)
+        return
     old = _PARAM_EPOCH
     _PARAM_EPOCH += 1
     if rewritten is not None and rewritten.is_cuda and _PACK['arena'] is not None and not _PACK['off']:
@@ -223,6 +238,48 @@ def bump_param_epoch(rewritten=None):
             _PACK['table'] = torch.empty(1 << 18, dtype=torch.uint8, device=rewritten.device)
         check(lib().cnuda_pack_refresh(ptr(rewritten), rewritten.numel() * rewritten.element_size(), old, _PARAM_EPOCH,
                                        ptr(_PACK['table']), _PACK['table'].numel(), stream()), 'pack_refresh')
+
+
+def _bump_several(buffers):
+    global _PARAM_EPOCH
+    if _HELD is not None:
+        _HELD.extend(buffers)
+        return
+    old = _PARAM_EPOCH
+    _PARAM_EPOCH += 1
+    buffers = [t for t in buffers if t.is_cuda]
+    if buffers and _PACK['arena'] is not None and not _PACK['off']:
+        if _PACK.get('table') is None or _PACK['table'].device != buffers[0].device:
+            _PACK['table'] = torch.empty(1 << 18, dtype=torch.uint8, device=buffers[0].device)
+        n = len(buffers)
+        ptrs = (c_void_p * n)(*[t.data_ptr() for t in buffers])
+        sizes = (c_size_t * n)(*[t.numel() * t.element_size() for t in buffers])
+        check(lib().cnuda_pack_refresh_ranges(ptrs, sizes, n, old, _PARAM_EPOCH, ptr(_PACK['table']),
+                                              _PACK['table'].numel(), stream()), 'pack_refresh_ranges')
+
+
+_HELD = None        # the buffers of the bumps deferred by the open `single_param_epoch` block (None: no block is open)
+
+
+class single_param_epoch:
+    """with single_param_epoch(): optimizer.step(); plan.update(decay)
+    Every bump_param_epoch inside the block is deferred; the block ends with ONE bump that carries all their buffers
+    (none, if nothing bumped).  The parameter epoch does not move inside the block, so NOTHING that reads packed
+    weights -- no forward, no backward -- may run between the first deferred bump and the end of the block: the block
+    is for back-to-back updates only.  Blocks do not nest."""
+
+    def __enter__(self):
+        global _HELD
+        if _HELD is not None:
+            raise RuntimeError("single_param_epoch blocks do not nest")
+        _HELD = []
+        return self
+
+    def __exit__(self, *exc):
+        global _HELD
+        held, _HELD = _HELD, None
+        if held:
+            bump_param_epoch([t for t in held if t is not None] or None)
 
 
 # Buffer epoch: bumped by every train-mode BatchNorm call (the statistics kernel rewrites running_mean / running_var /

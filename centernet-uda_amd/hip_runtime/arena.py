@@ -49,6 +49,16 @@ def grad_sink(param):
 class ParamArena:
     ALIGN = 64          # elements; keeps every tensor 256-byte aligned inside the arena
 
+    @classmethod
+    def layout(cls, params):
+        """-> (offsets, numel): where an arena over `params` puts each of them (in elements) and how long it is.  A
+        second flat buffer laid out like a model's arena (a mean teacher's parameters) is built from this."""
+        offsets, off = [], 0
+        for p in params:
+            offsets.append(off)
+            off += (p.numel() + cls.ALIGN - 1) // cls.ALIGN * cls.ALIGN
+        return offsets, off
+
     def __init__(self, params):
         self.params = list(params)
         if not self.params:

@@ -1342,3 +1342,120 @@ def meter_update(values, n, sums, counts, last):
                            "least %d elements" % S)
     table = (ctypes.c_void_p * S)(*[v.data_ptr() for v in values])
     check(lib().cnuda_meter_update(table, S, float(n), ptr(sums), ptr(counts), ptr(last), stream()), 'meter_update')
+
+
+# ---------------------------------------------------------------------------
+# Mean teacher (csrc/teacher.hip)
+# ---------------------------------------------------------------------------
+EMA_PER_BLOCK = 4096            # elements (float32 EMA) or bytes (copy) per workgroup: csrc/teacher.hip kEmaPerBlock
+
+
+def ema_segment_table(segments):
+    """[(dst address, src address, count, kind)] -> (the table as a numpy record array with the layout of
+    csrc/teacher.hip's EmaSegment, total workgroups).  Segments of no elements are left out."""
+    import numpy as np
+    dtype = np.dtype([('dst', '<u8'), ('src', '<u8'), ('count', '<i8'), ('kind', '<i4'), ('block0', '<u4')])
+    rows, blocks = [], 0
+    for dst, src, count, kind in segments:
+        if count <= 0:
+            continue
+        rows.append((dst, src, count, kind, blocks))
+        blocks += (count + EMA_PER_BLOCK - 1) // EMA_PER_BLOCK
+    if blocks >= 1 << 31:
+        raise RuntimeError("EmaPlan: %d workgroups exceed one launch" % blocks)
+    return np.array(rows, dtype=dtype), blocks
+
+
+class EmaPlan:
+    """dst_tensors[i] <- EMA of itself and src_tensors[i], all pairs in ONE launch (cnuda_ema_update).
+
+    A float32 pair is an element-wise `t = (t * d) + (s * omd)` with omd = float32(1) - float32(d): numpy's float32
+    result bit for bit.  Any other dtype (integer buffers: num_batches_tracked) is copied byte for byte.  Tensors are
+    contiguous device tensors of pairwise equal dtype and element count; a slice that starts at an odd element is fine.
+    The segment table is built and uploaded once; `update` compares the tensors' addresses with the ones it was
+    built from and rebuilds it when one moved (load_state_dict with assign, `.to()`, a re-pointed arena)."""
+
+    def __init__(self, dst_tensors, src_tensors):
+        self.dst, self.src = list(dst_tensors), list(src_tensors)
+        if len(self.dst) != len(self.src):
+            raise RuntimeError("EmaPlan: %d destinations for %d sources" % (len(self.dst), len(self.src)))
+        require_gpu(*self.dst, *self.src)
+        for i, (t, s) in enumerate(zip(self.dst, self.src)):
+            if t.dtype != s.dtype or t.numel() != s.numel() or t.device != s.device:
+                raise RuntimeError("EmaPlan: pair %d differs in dtype, length or device (%s %d %s / %s %d %s)"
+                                   % (i, t.dtype, t.numel(), t.device, s.dtype, s.numel(), s.device))
+            if not t.is_contiguous() or not s.is_contiguous():
+                raise RuntimeError("EmaPlan: pair %d is not contiguous" % i)
+            if t.numel() and t.dtype == torch.float32 and (t.data_ptr() % 4 or s.data_ptr() % 4):
+                raise RuntimeError("EmaPlan: pair %d is not 4-byte aligned" % i)
+        self._addresses = None
+        self._table = None
+        self._blocks = 0
+        self._rows = 0
+        self.uploads = 0                # times the table was (re)built
+        self._build()
+
+    def _current(self):
+        return [t.data_ptr() for t in self.dst] + [s.data_ptr() for s in self.src]
+
+    def _build(self):
+        segments = []
+        for t, s in zip(self.dst, self.src):
+            n = t.numel()
+            lo_t, lo_s, nbytes = t.data_ptr(), s.data_ptr(), n * t.element_size()
+            if n and lo_t < lo_s + nbytes and lo_s < lo_t + nbytes:
+                raise RuntimeError("EmaPlan: a destination overlaps its source")
+            if t.dtype == torch.float32:
+                segments.append((lo_t, lo_s, n, 0))
+            else:
+                segments.append((lo_t, lo_s, nbytes, 1))
+        table, self._blocks = ema_segment_table(segments)
+        self._rows = len(table)
+        self._addresses = self._current()
+        self._table = None
+        if self._rows:
+            host = torch.from_numpy(table.view('u1').reshape(-1).copy())
+            self._table = host.to(self.dst[0].device)          # (pageable and blocking: once per layout)
+        self.uploads += 1
+
+    def update(self, decay):
+        import numpy as np
+        d = np.float32(decay)
+        if not 0.0 <= float(d) < 1.0:
+            raise ValueError("EmaPlan.update: decay=%r outside [0, 1)" % (decay,))
+        if self._current() != self._addresses:
+            self._build()
+        if not self._rows:
+            return
+        omd = np.float32(1) - d
+        check(lib().cnuda_ema_update(ptr(self._table), self._rows, self._blocks, float(d), float(omd), stream()),
+              'ema_update')
+
+
+def pseudo_labels(dets, thresholds, map_width, *, rotated=False, mirror=False, min_size=0.0):
+    """A decoded detection table -> the inputs of datasets.targets.encode_targets at output-map resolution
+    (cnuda_pseudo_labels; include/centernet_uda_hip.h).  dets [B, K, 6] (or [B, K, 7] with rotated) float32 as
+    decode_detection leaves it, thresholds [C] float32 on the device.  -> {'classes' [B, K] int32, 'counts' [B] int32,
+    'kept' 0-dim float32 (the mean of counts), and 'boxes' [B, K, 4] float64 or, rotated, 'corners' [B, K, 4, 2]
+    float64}: the surviving rows first, in input order, zeros behind them.  One launch, nothing read back."""
+    require_gpu(dets, thresholds)
+    ncol = 7 if rotated else 6
+    if dets.dim() != 3 or dets.shape[2] != ncol or dets.numel() == 0:
+        raise RuntimeError("pseudo_labels: dets must be a non-empty [B, K, %d], got %s" % (ncol, tuple(dets.shape)))
+    if thresholds.dtype != torch.float32 or thresholds.dim() != 1 or thresholds.numel() == 0 \
+            or thresholds.device != dets.device:
+        raise RuntimeError("pseudo_labels: thresholds must be a float32 [C] tensor on dets' device")
+    if int(map_width) < 1:
+        raise RuntimeError("pseudo_labels: map_width=%r" % (map_width,))
+    dets, thresholds = f32c(dets.detach()), thresholds.contiguous()
+    B, K, _ = dets.shape
+    dev = dets.device
+    geometry = torch.empty((B, K, 4, 2) if rotated else (B, K, 4), dtype=torch.float64, device=dev)
+    out = {'classes': torch.empty((B, K), dtype=torch.int32, device=dev),
+           'counts': torch.empty((B,), dtype=torch.int32, device=dev),
+           'kept': torch.empty((), dtype=torch.float32, device=dev),
+           'corners' if rotated else 'boxes': geometry}
+    check(lib().cnuda_pseudo_labels(ptr(dets), ptr(thresholds), ptr(geometry), ptr(out['classes']), ptr(out['counts']),
+                                    ptr(out['kept']), B, K, thresholds.numel(), 1 if rotated else 0,
+                                    1 if mirror else 0, int(map_width), float(min_size), stream()), 'pseudo_labels')
+    return out

@@ -1,7 +1,7 @@
 """Run a trained model over images: detections in source-image pixels, with mirror and multi-scale test-time
 augmentation ("Prediction").
 
-    python predict.py RUN_DIR IMAGE_OR_DIR_OR_GLOB... [--out results.json] [--best]
+    python predict.py RUN_DIR IMAGE_OR_DIR_OR_GLOB... [--out results.json] [--best] [--teacher]
         [--flip] [--scales 0.75,1,1.25] [--soft-nms] [--score-threshold T]
         [--batch-size N] [--num-workers N] [--gpu I] [--annotation-file F]
         [--flip-pairs 1-2,3-4]
@@ -476,6 +476,8 @@ def parse_args(argv=None):
     ap.add_argument('inputs', nargs='+', help="image files, directories or glob patterns")
     ap.add_argument('--out', default='results.json', help="the COCO results file (default: %(default)s)")
     ap.add_argument('--best', action='store_true', help="load model_best.pth instead of model_last.pth")
+    ap.add_argument('--teacher', action='store_true',
+                    help="load the mean teacher (teacher_state_dict) of a uda.MeanTeacher run instead of the student")
     ap.add_argument('--flip', action='store_true', help="average with the left-right mirror")
     ap.add_argument('--scales', type=_scales, default=(1.0,), help="comma-separated test scales (default: 1)")
     ap.add_argument('--soft-nms', action='store_true', help="soft-NMS for a single scale too")
@@ -521,6 +523,7 @@ def settings_from_run(args):
         'flip_pairs': args.flip_pairs,
     }
     return {'backend': spec, 'predictor': predictor, 'use_last': not args.best, 'gpu': int(gpu or 0),
+            'state_key': 'teacher_state_dict' if getattr(args, 'teacher', False) else 'state_dict',
             'batch_size': int(cfg.get('batch_size', 16) if args.batch_size is None else args.batch_size),
             'num_workers': int(cfg.get('num_workers', 16) if args.num_workers is None else args.num_workers)}
 
@@ -536,7 +539,7 @@ def main(argv=None):
     device = torch.device('cuda', settings['gpu'])
     kwargs = dict(settings['predictor'])
     model = export.build_model(args.run_dir, settings['backend'], False, kwargs['max_detections'],
-                               use_last=settings['use_last'])
+                               use_last=settings['use_last'], state_key=settings['state_key'])
     predictor = Predictor(model.backend.to(device).eval(), kwargs.pop('input_size'), **kwargs)
     began = time.perf_counter()
     records = list(predict_files(predictor, files, batch_size=settings['batch_size'],

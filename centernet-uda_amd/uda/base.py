@@ -87,6 +87,11 @@ class Model:
             if hasattr(m, 'finish_gradient_sync'):
                 m.finish_gradient_sync()
 
+    def _optimizer_step(self):
+        """The parameter update of a training step; a plugin that keeps derived weights (uda.MeanTeacher's teacher)
+        updates them here, right behind it."""
+        self.optimizer.step()
+
     def _detach_stats(self, stats):
         if not self.host_stats:
             return {k: v.detach() for k, v in stats.items()}
@@ -106,7 +111,7 @@ class Model:
         if is_training:
             loss.backward()
             self._finish_backward()
-            self.optimizer.step()
+            self._optimizer_step()
         stats["total_loss"] = loss
         outputs["stats"] = self._detach_stats(stats)
         return outputs
@@ -143,7 +148,7 @@ class Model:
                     det_loss.backward()
                 uda_loss.backward()
             self._finish_backward()
-            self.optimizer.step()
+            self._optimizer_step()
         stats = dict(stats, **uda_stats)
         stats["total_loss"] = det_loss + uda_loss
         outputs["stats"] = self._detach_stats(stats)

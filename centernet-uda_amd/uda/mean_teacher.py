@@ -1,0 +1,225 @@
+"""Mean-teacher self-training ("Mean teacher"): a detection loss on TARGET images, against pseudo-labels from an
+exponential-moving-average copy of the network.  No counterpart in the reference, whose UDA methods only regularise the
+target-domain heat map.
+
+A training step, with `n` EMA updates done so far:
+
+  1. n < burn_in_steps: `Model.step` on the source batch; no teacher forward, no `pseudo_*` statistics.
+  2. otherwise the teacher (eval mode, no tape) sees `target_domain_input`: sigmoid_clamp_ on `hm`, decode_detection
+     (K = cfg.max_detections), hip_runtime.ops.pseudo_labels (per-class score thresholds, minimum extent, the mirror),
+     datasets.targets.encode_targets -- a batch like the loader's, built on the device, nothing read back;
+  3. the student's step is `step_with_target_term` over source | target (the mirrored target with `mirror_student`),
+     target term `pseudo_weight * centernet_loss(target outputs, pseudo batch)`; its statistics are logged under the
+     loss's own names prefixed `pseudo_` (unweighted) plus `pseudo_boxes`, the mean number of pseudo-labels per image;
+  4. right behind optimizer.step(): decay_t = min(decay, (1 + n) / (10 + n)), one cnuda_ema_update launch over the
+     teacher's flat parameter buffer and every buffer, n += 1 -- during burn-in too.
+
+The teacher is a copy of the unwrapped backend made in `to()`.  It is not a submodule of the backend (the backend's
+state_dict, the optimizer and a data-parallel wrapper never see it); its trainable parameters are views of one flat
+float32 buffer laid out like the student's arena, so that they are ONE segment of the update against
+`arena.flat_param`; frozen parameters stay as copied."""
+import copy
+
+import torch
+
+import hip_runtime as hr
+from uda.base import Model
+from utils import helper
+
+
+def decay_at(decay, n):
+    """The EMA decay of update number n (0-based): the warm-up (1 + n) / (10 + n) until it reaches `decay`."""
+    return min(float(decay), (1.0 + n) / (10.0 + n))
+
+
+class MeanTeacher(Model):
+    target_grad_heads = ('hm', 'wh', 'reg')
+
+    def __init__(self, pseudo_weight, decay=0.999, score_threshold=0.4, burn_in_steps=0, mirror_student=True,
+                 min_size=2.0, evaluate_teacher=False):
+        super().__init__()
+        if not 0.0 <= float(decay) < 1.0:
+            raise ValueError("MeanTeacher: decay=%r outside [0, 1)" % (decay,))
+        if not float(pseudo_weight) >= 0.0:
+            raise ValueError("MeanTeacher: pseudo_weight=%r is negative" % (pseudo_weight,))
+        if int(burn_in_steps) < 0:
+            raise ValueError("MeanTeacher: burn_in_steps=%r is negative" % (burn_in_steps,))
+        self.pseudo_weight, self.decay = float(pseudo_weight), float(decay)
+        self.score_threshold = (float(score_threshold) if isinstance(score_threshold, (int, float))
+                                else [float(v) for v in score_threshold])
+        self.burn_in_steps, self.mirror_student = int(burn_in_steps), bool(mirror_student)
+        self.min_size, self.evaluate_teacher = float(min_size), bool(evaluate_teacher)
+        self.teacher = None
+        self.teacher_flat = None            # the teacher's trainable parameters, laid out like the student's arena
+        self.teacher_updates = 0            # n
+        self._pairs = None                  # (teacher trainable parameters, student's), in the student's order
+        self._plan, self._plan_anchor = None, None
+        self._thresholds = None
+        self._pending = None                # a checkpoint's teacher entries, loaded before the teacher existed
+
+    # -- set-up ------------------------------------------------------------------------
+    def _model_params(self):
+        return self.cfg.model.backend.params
+
+    def _threshold_list(self):
+        C = int(self._model_params().num_classes)
+        if isinstance(self.score_threshold, list):
+            if len(self.score_threshold) != C:
+                raise ValueError("MeanTeacher: score_threshold lists %d values for num_classes=%d"
+                                 % (len(self.score_threshold), C))
+            return list(self.score_threshold)
+        return [self.score_threshold] * C
+
+    def init_done(self):
+        if int(self._model_params().get('num_keypoints', 0) or 0) > 0:
+            raise ValueError("MeanTeacher: num_keypoints=%r: keypoint pseudo-labels are not built; train a model "
+                             "without the keypoint head" % (self._model_params().num_keypoints,))
+        self._threshold_list()
+
+    def _build_teacher(self):
+        """A copy of the (unwrapped, already moved) backend whose storage is built here: the student's parameters may be
+        views of an arena, and copy.deepcopy of a view clones the whole underlying buffer once per parameter."""
+        from hip_runtime.arena import ParamArena
+        student = helper._unwrap(self.backend)
+        trainable = [p for p in student.parameters() if p.requires_grad]
+        offsets, numel = ParamArena.layout(trainable)
+        dev = trainable[0].device if trainable else next(student.parameters()).device
+        self.teacher_flat = torch.zeros(numel, dtype=torch.float32, device=dev)
+        memo, mine = {}, []
+        with torch.no_grad():
+            for p, o in zip(trainable, offsets):
+                view = self.teacher_flat[o:o + p.numel()].view(p.shape)
+                view.copy_(p)
+                mine.append(torch.nn.Parameter(view, requires_grad=False))
+                memo[id(p)] = mine[-1]
+            for p in student.parameters():
+                if id(p) not in memo:
+                    memo[id(p)] = torch.nn.Parameter(p.detach().clone(), requires_grad=False)
+            for b in student.buffers():
+                memo[id(b)] = b.detach().clone()
+        self.teacher = copy.deepcopy(student, memo).eval()
+        assert all(not p.requires_grad for p in self.teacher.parameters())
+        self._pairs = (mine, trainable)
+        self._plan = None
+
+    def to(self, device, parallel=False, global_normalizers=True):
+        self.backend.to(device)
+        self._build_teacher()
+        self._thresholds = torch.tensor(self._threshold_list(), dtype=torch.float32, device=device)
+        if self._pending is not None:
+            self._apply_checkpoint(*self._pending)
+            self._pending = None
+        super().to(device, parallel, global_normalizers)
+
+    # -- the EMA -----------------------------------------------------------------------
+    def _student_flat(self, trainable):
+        """The student's arena buffer, if the teacher's flat buffer is laid out like it (the optimizer's arena over
+        the trainable parameters in module order); None: a stock optimizer, or groups in another order."""
+        from hip_runtime.arena import _BY_PTR
+        hit = _BY_PTR.get(trainable[0].data_ptr())
+        arena = hit[0]() if hit is not None else None
+        if arena is None or arena.numel != self.teacher_flat.numel() or len(arena.params) != len(trainable) \
+                or any(a is not b for a, b in zip(arena.params, trainable)) or not arena.valid():
+            return None
+        return arena.flat_param
+
+    def _ema_plan(self):
+        mine, theirs = self._pairs
+        anchor = theirs[0].data_ptr() if theirs else 0
+        if self._plan is None or anchor != self._plan_anchor:
+            from hip_runtime.ops import EmaPlan
+            student = helper._unwrap(self.backend)
+            flat = self._student_flat(theirs) if theirs else None
+            if flat is not None:
+                dst, src = [self.teacher_flat], [flat]
+            else:                                       # the same launch, one segment per parameter
+                dst, src = [p.data for p in mine], [p.data for p in theirs]
+            dst += list(self.teacher.buffers())
+            src += list(student.buffers())
+            self._plan, self._plan_anchor = EmaPlan(dst, src), anchor
+        return self._plan
+
+    def _optimizer_step(self):
+        # the optimizer's bump and the teacher's share ONE parameter epoch: the packed weights of both models are
+        # carried by one refresh launch (two bumps in a row would strand both)
+        with hr.single_param_epoch():
+            self.optimizer.step()
+            self._ema_plan().update(decay_at(self.decay, self.teacher_updates))
+            hr.bump_param_epoch(self.teacher_flat)
+        hr.bump_buffer_epoch()          # the teacher's running statistics moved: BatchNorm-folded copies are stale
+        self.teacher_updates += 1
+
+    # -- the step ----------------------------------------------------------------------
+    def pseudo_batch(self, target_input):
+        """The teacher's detections on `target_input` as a batch for the detection loss (+ 'kept')."""
+        from backends.decode import decode_detection
+        from datasets.targets import encode_targets
+        from hip_runtime import ops
+        rotated = bool(self._model_params().rotated_boxes)
+        with torch.no_grad():
+            heads = self.teacher(target_input)
+            hm = ops.sigmoid_clamp_(heads['hm'])
+            dets = decode_detection(hm, heads['wh'], heads['reg'], K=self.cfg.max_detections, rotated=rotated)
+            H, W = hm.shape[2:]
+            labels = ops.pseudo_labels(dets, self._thresholds, W, rotated=rotated, mirror=self.mirror_student,
+                                       min_size=self.min_size)
+            batch = encode_targets(labels.get('boxes'), labels['classes'], labels['counts'], hm.shape[1], H, W,
+                                   corners=labels.get('corners'))
+        batch['kept'] = labels['kept']
+        return batch
+
+    def step(self, data, is_training=True):
+        if not is_training:
+            if not self.evaluate_teacher:
+                return Model.step(self, data, False)
+            student, self.backend = self.backend, self.teacher
+            try:
+                return Model.step(self, data, False)
+            finally:
+                self.backend = student
+        if self.teacher_updates < self.burn_in_steps:
+            return Model.step(self, data, True)
+        self._to_device(data)
+        pseudo = self.pseudo_batch(data['target_domain_input'])
+        view = dict(data)                   # the caller's batch keeps its tensors
+        if self.mirror_student:
+            from predict import mirror_input
+            view['target_domain_input'] = mirror_input(data['target_domain_input'])
+
+        def target_term(target_outputs, _):
+            # (a shallow copy: the loss rebinds `hm` to probabilities, the returned outputs keep the logits)
+            loss, stats = self.centernet_loss(dict(target_outputs), pseudo)
+            stats = {'pseudo_' + k: v for k, v in stats.items()}
+            stats['pseudo_boxes'] = pseudo['kept']
+            return loss * self.pseudo_weight, stats
+        return self.step_with_target_term(view, True, target_term)
+
+    # -- checkpoints -------------------------------------------------------------------
+    def _apply_checkpoint(self, state_dict, updates):
+        with torch.no_grad():
+            if state_dict is not None:
+                self.teacher.load_state_dict(state_dict)
+            else:                           # a checkpoint without a teacher: the freshly loaded student
+                student = helper._unwrap(self.backend)
+                for mine, theirs in ((self.teacher.parameters(), student.parameters()),
+                                     (self.teacher.buffers(), student.buffers())):
+                    for t, s in zip(mine, theirs):
+                        t.copy_(s)
+        if updates is not None:
+            self.teacher_updates = int(updates)
+
+    def load_model(self, path, resume=False):
+        extra = {}
+        epoch = helper.load_model(self.backend, self.optimizer, self.scheduler, path, resume, extra=extra)
+        if extra.get('found'):
+            found = (extra.get('teacher_state_dict'), extra.get('teacher_updates') if resume else None)
+            if self.teacher is None:
+                self._pending = found
+            else:
+                self._apply_checkpoint(*found)
+        return epoch
+
+    def save_model(self, path, epoch, with_optimizer=False):
+        extra = {'teacher_state_dict': self.teacher.state_dict(), 'teacher_updates': self.teacher_updates}
+        helper.save_model(self.backend, path, epoch, self.optimizer if with_optimizer else None,
+                          self.scheduler if with_optimizer else None, extra=extra)

@@ -111,15 +111,19 @@ def _unwrap(model):
     return model.module if hasattr(model, 'module') and isinstance(model.module, torch.nn.Module) else model
 
 
-def load_model(model, optimizer, scheduler, path, resume=False):
+def load_model(model, optimizer, scheduler, path, resume=False, extra=None):
     """Returns the start epoch: 1 if the file is missing, 0 for `pretrained`,
-    saved epoch + 1 for `resume` (utils/helper.py:85-90,128)."""
+    saved epoch + 1 for `resume` (utils/helper.py:85-90,128).  extra: a dict that takes 'found': True and whatever
+    the checkpoint holds beside the wire format's four keys (uda.MeanTeacher's teacher)."""
     path = Path(path)
     if not path.exists():
         log.warning("Model path %s does not exists!", path)
         return 1
     checkpoint = torch.load(path, map_location='cpu', weights_only=False)
     epoch = checkpoint["epoch"] if resume else 0
+    if extra is not None:
+        extra['found'] = True
+        extra.update({k: v for k, v in checkpoint.items() if k not in ('epoch', 'state_dict', 'optimizer', 'scheduler')})
     incoming = {}
     for k, v in checkpoint['state_dict'].items():
         # DataParallel checkpoints carry a 'module.' prefix ('module_list...' is a real name)
@@ -144,8 +148,9 @@ def load_model(model, optimizer, scheduler, path, resume=False):
     return (epoch + 1) if resume else epoch
 
 
-def save_model(model, path, epoch, optimizer=None, scheduler=None):
-    data = {'epoch': epoch, 'state_dict': _unwrap(model).state_dict()}
+def save_model(model, path, epoch, optimizer=None, scheduler=None, extra=None):
+    """extra: further entries beside the wire format's keys, which stay as they are."""
+    data = dict(extra or {}, epoch=epoch, state_dict=_unwrap(model).state_dict())
     if optimizer is not None:
         data['optimizer'] = optimizer.state_dict()
         if scheduler is not None:

@@ -72,6 +72,12 @@ unsigned long long cnuda_pack_cache_resets(void);
  * list; rewritten only when the set of images changes).  No reference counterpart. */
 int cnuda_pack_refresh(const void* params, size_t params_bytes, unsigned long long old_epoch,
                        unsigned long long new_epoch, void* table, size_t table_bytes, cnuda_stream_t stream);
+/* The same for `ranges` rewritten buffers at once (host arrays params[i], params_bytes[i]): a step that rewrote a
+ * student's arena AND a teacher's flat buffer carries both models' images into `new_epoch` with one launch and one
+ * table.  ranges == 1 is cnuda_pack_refresh. */
+int cnuda_pack_refresh_ranges(const void* const* params, const size_t* params_bytes, int ranges,
+                              unsigned long long old_epoch, unsigned long long new_epoch, void* table,
+                              size_t table_bytes, cnuda_stream_t stream);
 
 /* Measurement aid (bench.py roofline leg), not part of the reference's surface:
  * cnuda_prof_enable(n) pre-creates n hipEvent pairs; cnuda_prof_arm(tag) makes
@@ -903,6 +909,35 @@ int cnuda_soft_nms_merge(const float* boxes, const float* scores, const int* cla
                          const int* ncand, float* out_boxes, float* out_scores, int* out_classes, float* out_kps,
                          int* counts, int B, int N, int C, int J, int max_detections, float threshold,
                          void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+
+/* -------------------------------------------------------------------------
+ * Mean teacher (uda/mean_teacher.py; csrc/teacher.hip; DESIGN.md, "Mean teacher").  No reference counterpart.  No
+ * atomics: every result is independent of scheduling.  Caller's stream.
+ * ---------------------------------------------------------------------- */
+/* One launch over a DEVICE-resident table of `segments` entries of 32 bytes each,
+ *   { void* dst; const void* src; long long count; int kind; unsigned block0; }
+ * kind 0: count float32 elements, dst[i] = (dst[i] * decay) + (src[i] * one_minus_decay): two rounded products and one
+ *         rounded sum, never contracted -- numpy's float32 `t * d + s * omd` bit for bit.  one_minus_decay must be
+ *         float32(1) - decay, decay in [0, 1).  Both pointers 4-byte aligned; 16-byte accesses are taken only at
+ *         elements where BOTH are 16-byte aligned (a scalar head and tail around them), scalar accesses otherwise.
+ * kind 1: count bytes, dst[i] = src[i] (integer buffers such as num_batches_tracked); any alignment.
+ * A segment owns the workgroups block0 .. block0 + ceil(count / 4096) - 1 (none when count == 0); block0 is the running
+ * sum over the table and `blocks` its total.  dst and src ranges must not overlap.  The table's contents are the caller's
+ * responsibility (hip_runtime.ops.EmaPlan); segments == 0 or blocks == 0 launch nothing. */
+int cnuda_ema_update(const void* table, int segments, unsigned blocks, float decay, float one_minus_decay,
+                     cnuda_stream_t stream);
+/* A decoded detection table to the inputs of cnuda_encode_targets_modes, at output-map resolution.  dets [B,K,6]
+ * (x1, y1, x2, y2, score, class) or, rotated, [B,K,7] (cx, cy, w, h, angle in degrees, score, class); thresholds [C]
+ * float32.  A row survives iff its class is an integer in [0, C), score >= thresholds[class] (float32, equality keeps),
+ * its geometry columns are all finite and both extents (x2 - x1 and y2 - y1 in double; w and h when rotated) are
+ * >= min_size.  Survivors are compacted to the front in input order (stable); the other rows of every output are zero.
+ *   classes [B,K] int32, counts [B] int32, kept: one float32 = float32(double(sum of counts) / B);
+ *   geometry, axis-aligned: [B,K,4] float64 (x1, y1, x2, y2), with mirror != 0 (map_width - x2, y1, map_width - x1, y2);
+ *   geometry, rotated: [B,K,4,2] float64, the vertices of cnuda_project_detections (centre + (-w/2,-h/2), (w/2,-h/2),
+ *     (w/2,h/2), (-w/2,h/2) rotated by the angle, in double), with mirror != 0 every vertex's x -> map_width - x. */
+int cnuda_pseudo_labels(const float* dets, const float* thresholds, double* geometry, int* classes, int* counts,
+                        float* kept, int B, int K, int C, int rotated, int mirror, int map_width, float min_size,
+                        cnuda_stream_t stream);
 
 #ifdef __cplusplus
 }
