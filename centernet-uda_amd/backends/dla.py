@@ -35,6 +35,7 @@ import warnings
 import torch
 from torch import nn
 
+from backends.common import conv_to_bn, freeze, head_table, hub_checkpoint_path, make_head
 from hip_runtime import nn as hnn
 from hip_runtime import ops
 from hip_runtime.fanout import fork
@@ -118,10 +119,6 @@ def unfold_batchnorm(model):
             m._fold = None
 
 
-def _conv(cin, cout, k, stride=1):
-    return hnn.Conv2d(cin, cout, k, stride=stride, padding=k // 2, bias=False, emit_stats=True)    # (every caller: conv -> BatchNorm)
-
-
 def _norm_on_load_ok(cin, cout, k):
     """Does a k x k / stride 1 convolution cin -> cout of this library normalise its input on load?"""
     try:
@@ -137,7 +134,7 @@ class ConvBnRelu(nn.Sequential):
     _fold = None
 
     def __init__(self, cin, cout, k, stride=1):
-        super().__init__(_conv(cin, cout, k, stride), _bn(cout))
+        super().__init__(conv_to_bn(cin, cout, k, stride), _bn(cout))
 
     def fold_batchnorm_(self):
         self._fold = _folded(self[0].weight, self[0].bias, self[1])
@@ -154,7 +151,7 @@ class ConvBn(nn.Sequential):
     _fold = None
 
     def __init__(self, cin, cout):
-        super().__init__(_conv(cin, cout, 1), _bn(cout))
+        super().__init__(conv_to_bn(cin, cout, 1), _bn(cout))
 
     def fold_batchnorm_(self):
         self._fold = _folded(self[0].weight, self[0].bias, self[1])
@@ -170,8 +167,8 @@ class ConvBn(nn.Sequential):
 class BasicBlock(nn.Module):
     def __init__(self, cin, cout, stride=1):
         super().__init__()
-        self.conv1, self.bn1 = _conv(cin, cout, 3, stride), _bn(cout)
-        self.conv2, self.bn2 = _conv(cout, cout, 3), _bn(cout)
+        self.conv1, self.bn1 = conv_to_bn(cin, cout, 3, stride), _bn(cout)
+        self.conv2, self.bn2 = conv_to_bn(cout, cout, 3), _bn(cout)
 
     _fold = None
 
@@ -204,7 +201,7 @@ CAT_FREE_ROOT = os.environ.get('CNUDA_CAT_FREE_ROOT', '1') != '0'     # (A/B mea
 class Root(nn.Module):
     def __init__(self, cin, cout):
         super().__init__()
-        self.conv, self.bn = _conv(cin, cout, 1), _bn(cout)
+        self.conv, self.bn = conv_to_bn(cin, cout, 1), _bn(cout)
 
     _fold = None
 
@@ -316,7 +313,7 @@ def pretrained_path():
     """Where the ImageNet dla34 state dict is looked for: `$CNUDA_DLA34_WEIGHTS`, then the file name
     model_zoo.load_url() would have cached (dla.py:303-304)."""
     env = os.environ.get('CNUDA_DLA34_WEIGHTS')
-    return env if env else os.path.join(torch.hub.get_dir(), 'checkpoints', PRETRAINED_FILE)
+    return env if env else hub_checkpoint_path(PRETRAINED_FILE)
 
 
 def dla34(pretrained=False):
@@ -521,8 +518,7 @@ class DLASeg(nn.Module):
         self.first_level, self.last_level = int(math.log2(down_ratio)), last_level
         self.base = dla34(pretrained=pretrained)
         if freeze_base:
-            for p in self.base.parameters():
-                p.requires_grad = False
+            freeze(self.base)
         channels = self.base.channels
         up_channels = channels[self.first_level:]
         self.dla_up = DLAUp(self.first_level, up_channels, [2 ** i for i in range(len(up_channels))])
@@ -532,10 +528,7 @@ class DLASeg(nn.Module):
         self.heads = dict(heads)
         for head, classes in self.heads.items():
             if head_conv > 0:
-                fc = hnn.Head(
-                    hnn.Conv2d(channels[self.first_level], head_conv, 3, padding=1, bias=True, act_slope=0.0),
-                    hnn.Slot(),     # index of the reference's nn.ReLU (fused into conv '0')
-                    hnn.Conv2d(head_conv, classes, final_kernel, padding=final_kernel // 2, bias=True))
+                fc = make_head(channels[self.first_level], head_conv, classes, final_kernel)
                 last = fc[2]
             else:
                 fc = last = hnn.Conv2d(channels[self.first_level], classes, final_kernel,
@@ -618,8 +611,6 @@ class DLASeg(nn.Module):
 
 
 def build(num_classes, num_keypoints=0, head_conv=256, down_ratio=4, freeze_base=False, rotated_boxes=False):
-    heads = {'hm': num_classes, 'wh': 3 if rotated_boxes else 2, 'reg': 2}
-    if num_keypoints > 0:
-        heads['kps'] = num_keypoints * 2
+    heads = head_table(num_classes, num_keypoints, rotated_boxes)
     return DLASeg('dla34', heads, pretrained='auto', down_ratio=down_ratio, final_kernel=1, last_level=5,
                   head_conv=head_conv, freeze_base=freeze_base, rotated_boxes=rotated_boxes)

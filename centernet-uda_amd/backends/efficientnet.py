@@ -25,18 +25,20 @@ What the reference owns, restated from its file: three up-sampling stages ConvTr
 + ReLU to 256 channels (:163-200), optional skip branches `skip_<id>` = 1x1 convolution (bias) + BN + ReLU from trunk
 blocks SKIP_MAPPINGS[variant] added after the stage whose ReLU has index <id> in `deconv_layers` (:8-29, :71-91,
 :129-134), and per-head 3x3(256->256) + ReLU + 1x1 (:93-110, torch default init).  The `use_upsample` option (bilinear
-x4 + stride-2 convolution instead of the transposed convolution, :176-185; no config sets it) is declined.
+x4 + stride-2 convolution instead of the transposed convolution, :176-185; no config sets it) is declined.  The stages,
+the walk over them, the heads and the checkpoint lookup are backends/common.py's; this file is the trunk, the skip
+branches and where they join.
 
 All layers run on this repo's gfx950 kernels: 1x1 / 3x3 / transposed convolutions on the implicit-GEMM MFMA kernels,
 the depthwise SAME convolution on the depthwise kernels of csrc/spatial.hip, swish, squeeze-and-excite, drop-connect
 and the stem's zero-pad copy on csrc/mbconv.hip.
 """
 import math
-import os
 
 import torch
 from torch import nn
 
+from backends import common
 from hip_runtime import nn as hnn
 from hip_runtime import ops
 from hip_runtime.fanout import fork
@@ -105,9 +107,7 @@ class EfficientNet(nn.Module):
         self._bn1 = bn(head)
         self._fc = nn.Linear(head, 1000)
         self.drop_connect_rate = DROP_CONNECT_RATE
-        with torch.no_grad():
-            for conv in (self._conv_stem, self._conv_head):
-                conv.weight.normal_(0.0, math.sqrt(2.0 / (conv.kernel_size[0] * conv.kernel_size[1] * conv.out_channels)))
+        common.kaiming_fan_out_((self._conv_stem, self._conv_head))
 
     def stem(self, x):
         x = ops.pad_right_bottom(x, self.stem_padding, self.stem_padding)
@@ -121,67 +121,37 @@ class EfficientNet(nn.Module):
         return self.drop_connect_rate * float(idx) / len(self._blocks)
 
 
-class CenterEfficientNet(nn.Module):
+class CenterEfficientNet(common.DeconvBackend):
     def __init__(self, variant, heads, pretrained, freeze_base=False, use_skip=False, rotated_boxes=False,
                  use_upsample=False, num_head_channels=256, num_deconv_channels=(256, 256, 256)):
-        super().__init__()
         if use_upsample:
             raise NotImplementedError("CenterEfficientNet: use_upsample=True (bilinear up-sampling + stride-2 convolution "
                                       "instead of ConvTranspose2d) is not built here; no experiment config sets it")
         assert len(num_deconv_channels) == 3
-        head_conv = num_head_channels
+        base = EfficientNet(variant)
+        super().__init__(base, base._bn1.num_features, freeze_base, rotated_boxes,
+                         deconv_channels=list(num_deconv_channels))
         self.use_skip = use_skip
-        self.deconv_with_bias = False
-        self.down_ratio = 4
         self.variant = variant
-        self.rotated_boxes = rotated_boxes
         self.use_upsample = False
-        self.base = EfficientNet(variant)
         if pretrained:
             self._load_pretrained()
-        self.inplanes = self.base._bn1.num_features
-        if freeze_base:
-            for p in self.base.parameters():
-                p.requires_grad = False
-        self.deconv_layer_channels = list(num_deconv_channels)
-        self.deconv_layers = self._make_deconv_layer(3, self.deconv_layer_channels, [4, 4, 4])
         if self.use_skip:
             for deconv_id, fe_id in SKIP_MAPPINGS[variant].items():
                 in_channels = self.base._blocks[fe_id]._project_conv.out_channels
                 out_channels = self.deconv_layers[deconv_id - 2].out_channels      # -2: conv, bn, relu
                 setattr(self, "skip_%d" % deconv_id, nn.Sequential(
                     hnn.Conv2d(in_channels, out_channels, 1, padding=0), hnn.BatchNorm2d(out_channels), hnn.Slot()))
-        self.heads = heads
-        for head in sorted(self.heads):
-            fc = hnn.Head(
-                hnn.Conv2d(self.deconv_layer_channels[-1], head_conv, 3, padding=1, bias=True, act_slope=0.0),
-                hnn.Slot(),      # index of the reference's nn.ReLU (fused into conv '0')
-                hnn.Conv2d(head_conv, self.heads[head], 1, bias=True))
-            setattr(self, head, fc)
+        self.add_heads(heads, head_conv=num_head_channels)
 
     def _load_pretrained(self):
-        """The reference downloads the ImageNet weights through torch.hub (efficientnet.py:53-56); no network path here:
-        the file is read from the hub checkpoint cache or this raises like a failed download."""
-        path = os.path.join(torch.hub.get_dir(), 'checkpoints', _PRETRAINED[self.variant])
-        if not os.path.isfile(path):
-            raise RuntimeError("efficientnet_%s pretrained=True: %s not found (no download in this build; place the "
-                               "published checkpoint there or pass pretrained=False)" % (self.variant, path))
+        """the published port's ImageNet weights (efficientnet.py:53-56): its names are the trunk's, `_fc` included"""
+        path = common.hub_checkpoint(_PRETRAINED[self.variant], 'efficientnet_%s' % self.variant)
         self.base.load_state_dict(torch.load(path, map_location='cpu'))
 
-    def _get_deconv_cfg(self, deconv_kernel, index):
-        return {4: (4, 1, 0), 3: (3, 1, 1), 2: (2, 0, 0)}[deconv_kernel]      # kernel, padding, output_padding
-
-    def _make_deconv_layer(self, num_layers, num_filters, num_kernels):
-        assert num_layers == len(num_filters) == len(num_kernels)
-        layers = []
-        for i in range(num_layers):
-            kernel, padding, output_padding = self._get_deconv_cfg(num_kernels[i], i)
-            planes = num_filters[i]
-            layers += [hnn.ConvTranspose2d(self.inplanes, planes, kernel, stride=2, padding=padding,
-                                           output_padding=output_padding),
-                       hnn.BatchNorm2d(planes, momentum=0.1), hnn.Slot()]
-            self.inplanes = planes
-        return nn.Sequential(*layers)
+    def skip_branch(self, lid, feature):
+        branch = getattr(self, "skip_%d" % lid)
+        return branch[1](branch[0](feature), relu=True)
 
     def forward_to_deconv(self, x):
         base = self.base
@@ -192,14 +162,7 @@ class CenterEfficientNet(nn.Module):
             x = block(x, drop_connect_rate=base.block_rate(idx))
             if idx in sources:
                 x, skip[sources[idx]] = fork(x, 2)          # the next block's input | the skip branch's
-        x = base.head(x)
-        d = self.deconv_layers
-        for lid in range(0, len(d), 3):          # (ConvTranspose2d, BN, ReLU) triples: BN + ReLU is one kernel
-            x = d[lid + 1](d[lid](x), relu=True)
-            if lid + 2 in skip:                  # the skip branch joins after the stage's ReLU (:129-134)
-                branch = getattr(self, "skip_%d" % (lid + 2))
-                x = ops.add(branch[1](branch[0](skip[lid + 2]), relu=True), x)
-        return x
+        return self.upsample(base.head(x), skip)      # ids 2 and 5: the branch joins after the stage's ReLU (:129-134)
 
     def forward(self, x):
         x = self.forward_to_deconv(x)
@@ -211,8 +174,6 @@ def build(num_classes, variant='b0', num_keypoints=0, pretrained=True, freeze_ba
     if variant not in VARIANTS:
         raise NotImplementedError("EfficientNet variant %s is not implemented (built here: %s)"
                                   % (variant, ', '.join(sorted(VARIANTS))))
-    heads = {'hm': num_classes, 'wh': 2 if not rotated_boxes else 3, 'reg': 2}
-    if num_keypoints > 0:
-        heads['kps'] = num_keypoints * 2
+    heads = common.head_table(num_classes, num_keypoints, rotated_boxes)
     return CenterEfficientNet(variant, heads, pretrained=pretrained, freeze_base=freeze_base,
                               rotated_boxes=rotated_boxes, use_skip=use_skip, **kwargs)

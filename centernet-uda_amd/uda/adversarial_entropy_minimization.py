@@ -77,16 +77,8 @@ class AdversarialEntropyMinimization(Model):
         D = self.discriminator
         for p in D.parameters():
             p.requires_grad = False
-        batched = (self.batch_domains and hasattr(self.backend, 'forward_domains')
-                   and data["input"].shape == data["target_domain_input"].shape)
-        if batched:
-            # one pass over source | target (uda/base.py step_with_target_term explains the equivalence); the
-            # target's heat map feeds the discriminator, its other heads feed nothing
-            out_s, out_t = self.backend.forward_domains(data["input"], data["target_domain_input"],
-                                                        target_grad_heads=self.target_grad_heads)
-        else:
-            out_s = self.backend(data["input"])
-            out_t = self.backend(data["target_domain_input"])
+        # the target's heat map feeds the discriminator, its other heads feed nothing (target_grad_heads)
+        out_s, out_t, batched = self.forward_both(data)
         fool_logits = D(entropy_map(out_t["hm"]))
         outputs = {"source_domain": out_s, "target_domain": out_t}
 

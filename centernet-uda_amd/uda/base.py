@@ -116,6 +116,17 @@ class Model:
         outputs["stats"] = self._detach_stats(stats)
         return outputs
 
+    def forward_both(self, data):
+        """-> (source outputs, target outputs, batched).  batched: `batch_domains` is set, the backend offers
+        `forward_domains` and the two batches have one shape -- then both went through the backend as one pass over
+        source | target (per-domain BatchNorm statistics, Q6; only `target_grad_heads` record a tape on the target
+        half) and the caller back-propagates the SUM of its losses once: the same gradients as the reference's two
+        forward / two backward calls up to summation order.  Otherwise: those two forward calls, source first."""
+        source, target = data["input"], data["target_domain_input"]
+        if self.batch_domains and hasattr(self.backend, 'forward_domains') and source.shape == target.shape:
+            return (*self.backend.forward_domains(source, target, target_grad_heads=self.target_grad_heads), True)
+        return self.backend(source), self.backend(target), False
+
     def step_with_target_term(self, data, is_training, target_term):
         """The step shared by the single-loss UDA plugins (uda/entropy_minimization.py:11-43,
         uda/max_squares_minimization.py:11-50): source and target batch both go through the backend in train
@@ -127,17 +138,8 @@ class Model:
         self._to_device(data)
         if is_training:
             self.optimizer.zero_grad()
-        batched = (self.batch_domains and hasattr(self.backend, 'forward_domains')
-                   and data["input"].shape == data["target_domain_input"].shape)
-        if batched:
-            # one pass over source | target (per-domain BatchNorm statistics, Q6), one backward pass of the summed
-            # loss: the same gradients as the reference's two forward / two backward calls up to summation order
-            src, tgt = self.backend.forward_domains(data["input"], data["target_domain_input"],
-                                                    target_grad_heads=self.target_grad_heads)
-            outputs = {"source_domain": src, "target_domain": tgt}
-        else:
-            outputs = {name: self.backend(data[key])
-                       for name, key in (("source_domain", "input"), ("target_domain", "target_domain_input"))}
+        src, tgt, batched = self.forward_both(data)
+        outputs = {"source_domain": src, "target_domain": tgt}
         det_loss, stats = self.centernet_loss(outputs["source_domain"], data)
         uda_loss, uda_stats = target_term(outputs["target_domain"], data)
         if is_training:
