@@ -5,6 +5,7 @@
 //   losses/centernet.py:98-133  RegL1Loss (+ rotated), :192-223 PeriodicRegL1Loss, :136-189 KPSL1Loss
 //   losses/entropy.py:10-28     EntropyLoss      losses/max_square.py:6-14 MaxSquareLoss
 //   utils/image.py:121-124      entropy_map      losses/advent.py:10-18    BCE-with-logits vs constant
+//   image-wise class-balanced max-squares (ICCV 2019, not in the reference): argmax histogram, weights, loss
 // Every loss is a pair (forward -> scalar(s) in device memory, backward ->
 // gradient w.r.t. the logits given a device-resident upstream scalar).
 // The shared pieces keep every order of operations and so the bits: tests/test_gpu_loss_bits.py.
@@ -316,6 +317,124 @@ __global__ void softmax_grad_kernel(const float* __restrict__ x, const float* __
         }
     }
 }
+// ---------------- image-wise class-balanced max-squares (Chen, Xue, Cai, ICCV 2019, section 3.3) ----------------
+//   a[b,p] = argmax_c x[b,c,p] on the LOGITS, lowest channel on a tie;  hist[b,c] = #{p : a[b,p] == c}
+//   w[b,c] = 1 / max(hist^ratio * HW^(1-ratio), 1);  loss = -sum v^2 w[b,a] / (2 B C)   
+// The three kernels below take the argmax from this one walk, so a pixel counts for the class whose weight it gets.
+constexpr int kIwMaxClasses = 1024;   // the per-workgroup LDS table (4 KiB) of the histogram and of the weights
+constexpr int kIwBallotClasses = 16;  // up to here a wave counts a class with one ballot + popcount, no LDS atomics
+__device__ __forceinline__ int argmax_channel(const float* __restrict__ px, int C, size_t HW) {
+    float best = px[0];
+    int a = 0;
+    for (int c = 1; c < C; ++c) {
+        const float v = px[(size_t)c * HW];
+        if (v > best) { best = v; a = c; }   // strict: the lowest channel keeps a tie
+    }
+    return a;
+}
+// grid (gx, gy): blockIdx.y walks the images, the gx workgroups of a row share one image's pixels.  Ballot: lane c of
+// every wave keeps class c's count in a register, the table holds one row per wave.  Otherwise: one LDS integer atomic
+// per pixel.  Either way one global integer atomic per (workgroup, image, class that occurred): integer adds commute, the
+// counts are exact whatever the order.
+template <bool Ballot>
+__global__ __launch_bounds__(kT) void argmax_hist_kernel(const float* __restrict__ x, int* __restrict__ hist, int B,
+                                                         int C, long long HW) {
+    __shared__ int table[kIwMaxClasses];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const float* xb = x + (size_t)b * C * HW;
+        int mine = 0;
+        if (!Ballot) {
+            for (int c = threadIdx.x; c < C; c += kT) table[c] = 0;
+            __syncthreads();
+        }
+        for (long long base = (long long)blockIdx.x * kT; base < HW; base += (long long)gridDim.x * kT) {   // wave-uniform
+            const long long hw = base + threadIdx.x;
+            const bool live = hw < HW;
+            const int a = live ? argmax_channel(xb + hw, C, (size_t)HW) : -1;
+            if (Ballot) {
+                for (int c = 0; c < C; ++c) {
+                    const int n = __popcll(__ballot(a == c));
+                    if (lane == c) mine += n;
+                }
+            } else if (live) {
+                atomicAdd(&table[a], 1);
+            }
+        }
+        if (Ballot) {
+            if (lane < C) table[wid * kIwBallotClasses + lane] = mine;
+            __syncthreads();
+            if (threadIdx.x < C) {
+                int n = 0;
+                for (int w = 0; w < kT / kWave; ++w) n += table[w * kIwBallotClasses + threadIdx.x];
+                if (n) atomicAdd(hist + (size_t)b * C + threadIdx.x, n);
+            }
+        } else {
+            __syncthreads();
+            for (int c = threadIdx.x; c < C; c += kT)
+                if (table[c]) atomicAdd(hist + (size_t)b * C + c, table[c]);
+        }
+        __syncthreads();   // the table is the next image's
+    }
+}
+__device__ __forceinline__ float iw_weight(int count, float ratio, float hw_pow) {
+    return 1.0f / fmaxf(powf((float)count, ratio) * hw_pow, 1.0f);
+}
+// blockIdx.x = by * gx + bx: row `by` of gy walks the images, its gx workgroups share one image's pixels and each
+// turns that image's counts into its own LDS copy of the weights; the first of them also saves them for the backward.
+__global__ __launch_bounds__(kT) void iw_max_square_reduce_kernel(const float* __restrict__ x, const int* __restrict__ hist,
+                                                                  float ratio, float* __restrict__ weights,
+                                                                  double* __restrict__ partial, int B, int C,
+                                                                  long long HW, int gx, int gy) {
+    __shared__ double red[16];
+    __shared__ float w[kIwMaxClasses];
+    const int bx = blockIdx.x % gx, by = blockIdx.x / gx;
+    const float hw_pow = powf((float)HW, 1.0f - ratio);
+    double acc[1] = {};
+    for (int b = by; b < B; b += gy) {
+        __syncthreads();   // the previous image's weights are read no more
+        for (int c = threadIdx.x; c < C; c += kT) {
+            const float wc = iw_weight(hist[(size_t)b * C + c], ratio, hw_pow);
+            w[c] = wc;
+            if (bx == 0) weights[(size_t)b * C + c] = wc;
+        }
+        __syncthreads();
+        for (long long hw = (long long)bx * kT + threadIdx.x; hw < HW; hw += (long long)gx * kT) {
+            const SoftmaxPixel p(x, (long long)b * HW + hw, C, HW);
+            float s = 0.0f;
+            for (int c = 0; c < C; ++c) {
+                const float v = p.v(c);
+                s += v * v;
+            }
+            acc[0] += (double)(s * w[argmax_channel(p.px, C, p.HW)]);
+        }
+    }
+    store_partials(acc, partial, red);
+}
+// dx_j = k v_j (2 v_j - sum_i 2 v_i^2), k = upstream * scale * w[b, a]: MaxSquareTerm's gradient with the pixel's weight
+// in the coefficient; the weights are constants of the backward pass
+__global__ void iw_max_square_grad_kernel(const float* __restrict__ x, const float* __restrict__ weights,
+                                          const float* __restrict__ upstream, float scale, float* __restrict__ grad,
+                                          int B, int C, long long HW) {
+    const float up = upstream[0] * scale;
+    const long long total = (long long)B * HW;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const SoftmaxPixel p(x, i, C, HW);
+        float dot = 0.0f;
+        for (int c = 0; c < C; ++c) {
+            const float v = p.v(c);
+            dot += v * (2.0f * v);
+        }
+        const float k = up * weights[(size_t)(i / HW) * C + argmax_channel(p.px, C, p.HW)];
+        float* pg = grad + p.base;
+        for (int c = 0; c < C; ++c) {
+            const float v = p.v(c);
+            pg[(size_t)c * p.HW] = k * v * (2.0f * v - dot);
+        }
+    }
+}
+
 // entropy_map: out_c = -f(v_c) / log2(C)
 __global__ void entropy_map_fwd_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int C,
                                        long long HW) {
@@ -622,6 +741,53 @@ extern "C" int cnuda_entropy_eta_loss_backward(const float* logits, const float*
                   "cnuda_entropy_eta_loss_backward: bad arguments");
     return softmax_loss_backward<EtaEntropyTerm>("cnuda_entropy_eta_loss_backward", logits, upstream, grad_logits, B, C,
                                                  HW, eta, (hipStream_t)stream);
+}
+// The grid of the two image-wise kernels: gy rows over the images, gx workgroups per row, gx * gy <= kLossBlocks.
+struct IwGrid { int gx, gy; };
+static IwGrid iw_grid(int B, long long HW) {
+    const int gy = B < kLossBlocks ? B : kLossBlocks;
+    const long long want = (HW + kT - 1) / kT, cap = kLossBlocks / gy;
+    return {(int)(want < cap ? want : cap), gy};
+}
+extern "C" int cnuda_argmax_histogram(const float* logits, int32_t* hist, int B, int C, long long HW,
+                                      cnuda_stream_t stream) {
+    CNUDA_REQUIRE(logits && hist && B > 0 && C > 0 && HW > 0 && HW <= 0x7fffffffLL, "cnuda_argmax_histogram: bad arguments");
+    CNUDA_REQUIRE(C <= kIwMaxClasses, "cnuda_argmax_histogram: %d classes, the workgroup's table holds %d", C, kIwMaxClasses);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(hist, 0, (size_t)B * C * sizeof(int32_t), st) != hipSuccess)
+        return check_launch("cnuda_argmax_histogram(memset)");
+    const IwGrid g = iw_grid(B, HW);
+    if (C <= kIwBallotClasses)
+        CNUDA_LAUNCH(argmax_hist_kernel<true>, dim3(g.gx, g.gy), dim3(kT), 0, st, logits, (int*)hist, B, C, HW);
+    else
+        CNUDA_LAUNCH(argmax_hist_kernel<false>, dim3(g.gx, g.gy), dim3(kT), 0, st, logits, (int*)hist, B, C, HW);
+    return check_launch("cnuda_argmax_histogram");
+}
+static double iw_max_square_scale(int B, int C) { return -1.0 / (2.0 * (double)B * (double)C); }
+extern "C" int cnuda_iw_max_square_forward(const float* logits, const int32_t* hist, float ratio, float* weights_out,
+                                           float* out1, int B, int C, long long HW, void* workspace,
+                                           size_t workspace_bytes, cnuda_stream_t stream) {
+    CNUDA_REQUIRE(logits && hist && weights_out && out1 && B > 0 && C > 0 && HW > 0,
+                  "cnuda_iw_max_square_forward: bad arguments");
+    CNUDA_REQUIRE(ratio >= 0.0f && ratio <= 1.0f, "cnuda_iw_max_square_forward: ratio %g outside [0, 1]", (double)ratio);
+    CNUDA_REQUIRE(C <= kIwMaxClasses, "cnuda_iw_max_square_forward: %d classes, the workgroup's table holds %d", C,
+                  kIwMaxClasses);
+    hipStream_t st = (hipStream_t)stream;
+    const IwGrid g = iw_grid(B, HW);
+    // reduced_loss sizes its grid from an item count: gx * gy workgroups' worth of threads gives exactly this grid
+    return reduced_loss("cnuda_iw_max_square_forward", workspace, workspace_bytes, (long long)g.gx * g.gy * kT, st,
+                        ScaleEpilogue{iw_max_square_scale(B, C)}, out1, [&](int blocks, double* partial) {
+        CNUDA_LAUNCH(iw_max_square_reduce_kernel, dim3(blocks), dim3(kT), 0, st, logits, (const int*)hist, ratio,
+                     weights_out, partial, B, C, HW, g.gx, g.gy);
+    });
+}
+extern "C" int cnuda_iw_max_square_backward(const float* logits, const float* weights, const float* upstream,
+                                            float* grad_logits, int B, int C, long long HW, cnuda_stream_t stream) {
+    CNUDA_REQUIRE(logits && weights && upstream && grad_logits && B > 0 && C > 0 && HW > 0,
+                  "cnuda_iw_max_square_backward: bad arguments");
+    CNUDA_LAUNCH(iw_max_square_grad_kernel, dim3(stream_grid((long long)B * HW, kT)), dim3(kT), 0, (hipStream_t)stream,
+                 logits, weights, upstream, (float)iw_max_square_scale(B, C), grad_logits, B, C, HW);
+    return check_launch("cnuda_iw_max_square_backward");
 }
 extern "C" int cnuda_entropy_map_forward(const float* logits, float* out, int B, int C, long long HW,
                                          cnuda_stream_t stream) {

@@ -1213,6 +1213,63 @@ def entropy_map(hm):
     return _LogitsLoss.apply(hm, _ENTROPY_MAP)
 
 
+def _class_histogram(logits):
+    """logits: contiguous fp32 [B, C, ...] on the GPU -> int32 [B, C]"""
+    B, C = logits.shape[0], logits.shape[1]
+    hist = torch.empty((B, C), dtype=torch.int32, device=logits.device)
+    check(lib().cnuda_argmax_histogram(ptr(logits), ptr(hist), B, C, logits.numel() // (B * C), stream()),
+          'argmax_histogram')
+    return hist
+
+
+def class_histogram(hm_logits):
+    """hm_logits [B, C, H, W] -> int32 [B, C]: how many pixels of each image every class wins, the argmax taken on the
+    logits with the lowest channel on a tie (np.argmax(x, 1)).  No gradient, no read-back."""
+    require_gpu(hm_logits)
+    return _class_histogram(f32c(hm_logits.detach()))
+
+
+class _IWMaxSquare(Function):
+    """_LogitsLoss's sibling with a saved side tensor: the [B, C] class weights the forward derives from the argmax
+    histogram are constants of the backward pass."""
+
+    @staticmethod
+    def forward(ctx, logits, ratio):
+        require_gpu(logits)
+        logits = f32c(logits)
+        B, C = logits.shape[0], logits.shape[1]
+        shape = (B, C, logits.numel() // (B * C))
+        hist = _class_histogram(logits)
+        weights = torch.empty((B, C), dtype=torch.float32, device=logits.device)
+        out = torch.empty(1, dtype=torch.float32, device=logits.device)
+        check(lib().cnuda_iw_max_square_forward(ptr(logits), ptr(hist), ratio, ptr(weights), ptr(out), *shape,
+                                                *_loss_ws(logits), stream()), 'iw_max_square_forward')
+        ctx.shape = shape
+        ctx.save_for_backward(logits, weights)
+        return out[0].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        logits, weights = ctx.saved_tensors
+        grad = torch.empty_like(logits)
+        up = f32c(g.reshape(1))
+        check(lib().cnuda_iw_max_square_backward(ptr(logits), ptr(weights), ptr(up), ptr(grad), *ctx.shape, stream()),
+              'iw_max_square_backward')
+        return grad, None
+
+
+def iw_max_square_loss(hm_logits, ratio=0.2):
+    """Max-squares with the image-wise class-balanced weighting factor (Chen, Xue, Cai, ICCV 2019):
+    -sum(softmax(hm)^2 * w[argmax]) / (2 B C),  w[b, c] = 1 / max(hist[b, c]^ratio * HW^(1 - ratio), 1),
+    hist = class_histogram(hm).  The published form has no 1/2; it is here because MaxSquareLoss has it, so ratio = 0
+    is MaxSquareLoss.  The weights carry no gradient."""
+    ratio = float(ratio)
+    if not 0.0 <= ratio <= 1.0:
+        raise ValueError("iw_max_square_loss: ratio must be in [0, 1], got %r" % (ratio,))
+    return _IWMaxSquare.apply(hm_logits, ratio)
+
+
 def bce_with_logits_const(logits, label):
     return _LogitsLoss.apply(logits, _BCE_CONST, float(label))
 

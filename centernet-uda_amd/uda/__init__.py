@@ -8,6 +8,7 @@ _PLUGINS = {
     'Model': 'uda.base',
     'EntropyMinimization': 'uda.entropy_minimization',
     'MaxSquaresMinimization': 'uda.max_squares_minimization',
+    'IWMaxSquaresMinimization': 'uda.max_squares_minimization',
     'AdversarialEntropyMinimization': 'uda.adversarial_entropy_minimization',
     'MeanTeacher': 'uda.mean_teacher',
 }

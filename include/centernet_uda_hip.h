@@ -651,6 +651,18 @@ int cnuda_entropy_eta_loss_forward(const float* logits, float* out1, int B, int 
                                    void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
 int cnuda_entropy_eta_loss_backward(const float* logits, const float* upstream, float* grad_logits,
                                     int B, int C, long long HW, float eta, cnuda_stream_t stream);
+/* Image-wise class-balanced max-squares (Chen, Xue, Cai, ICCV 2019; the reference ships only the plain form).
+ *   a[b,p] = argmax_c logits[b,c,p], the lowest channel on a tie;  hist[b,c] = #{p : a[b,p] == c}  (int32, sums to HW)
+ *   w[b,c] = 1 / max(hist[b,c]^ratio * HW^(1-ratio), 1)  (float32);  out1 = -sum_{b,c,p} v^2 w[b,a[b,p]] / (2 B C),
+ *   v = softmax over C: the published form divided by 2 as MaxSquareLoss is, so ratio = 0 gives MaxSquareLoss.
+ * argmax_histogram clears `hist` itself; forward writes the weights [B*C] that backward reads.  C <= 1024 (the
+ * workgroup's LDS table), 0 <= ratio <= 1.  No call synchronises; integer counts and fp64 sums: the same bits every run. */
+int cnuda_argmax_histogram(const float* logits, int32_t* hist, int B, int C, long long HW, cnuda_stream_t stream);
+int cnuda_iw_max_square_forward(const float* logits, const int32_t* hist, float ratio, float* weights_out, float* out1,
+                                int B, int C, long long HW, void* workspace, size_t workspace_bytes,
+                                cnuda_stream_t stream);
+int cnuda_iw_max_square_backward(const float* logits, const float* weights, const float* upstream, float* grad_logits,
+                                 int B, int C, long long HW, cnuda_stream_t stream);
 int cnuda_bce_const_forward(const float* logits, float label, float* out1, long long n, cnuda_stream_t stream);
 int cnuda_bce_const_backward(const float* logits, float label, const float* upstream, float* grad_logits,
                              long long n, cnuda_stream_t stream);
