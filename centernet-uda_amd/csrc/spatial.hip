@@ -489,8 +489,7 @@ __global__ void add_kernel(const float* a, const float* b, float* out, long long
 }
 // gx = gy * (y > 0 ? 1 : slope)      (ReLU: slope 0; LeakyReLU(0.2): slope 0.2)
 __global__ void act_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ y, float* __restrict__ gx,
-                               long long n, float slope) {
-    const long long n4 = n >> 2;
+                               long long n4, long long n, float slope) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         const float4 g = reinterpret_cast<const float4*>(gy)[i], v = reinterpret_cast<const float4*>(y)[i];
         reinterpret_cast<float4*>(gx)[i] = make_float4(v.x > 0.0f ? g.x : g.x * slope, v.y > 0.0f ? g.y : g.y * slope,
@@ -530,15 +529,16 @@ __global__ __launch_bounds__(kT) void conv1x1_dgrad_act_kernel(const float* __re
     }
 }
 // Row-wise kernels: grid (chunks of a row, rows); a row is one (image, channel) plane of HW floats, so the
-// channel bookkeeping is per workgroup and the inner loop is 16-byte copies when HW % 4 == 0.
+// channel bookkeeping is per workgroup and the inner loop is 16-byte copies when `vec`: HW % 4 == 0 and every tensor
+// 16-byte aligned (rows_vec_ok, decided by the host); else 4-byte copies of the same values.
 // copy a [B, Cn, HW] block between tensors with Csrc / Cdst channels at channel offsets
 __global__ void copy_channels_kernel(const float* __restrict__ src, float* __restrict__ dst, int rows, int Cn,
-                                     long long HW, int Csrc, int src_off, int Cdst, int dst_off) {
+                                     long long HW, int Csrc, int src_off, int Cdst, int dst_off, int vec) {
     for (int row = blockIdx.y; row < rows; row += gridDim.y) {
         const int b = row / Cn, c = row - b * Cn;
         const float* s = src + ((size_t)b * Csrc + src_off + c) * HW;
         float* d = dst + ((size_t)b * Cdst + dst_off + c) * HW;
-        if ((HW & 3) == 0) {
+        if (vec) {
             for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (HW >> 2); i += (long long)gridDim.x * blockDim.x)
                 reinterpret_cast<float4*>(d)[i] = reinterpret_cast<const float4*>(s)[i];
         } else {
@@ -549,13 +549,13 @@ __global__ void copy_channels_kernel(const float* __restrict__ src, float* __res
 }
 // om [B, 3T, HW] -> offset [B, 2T, HW] (channels 0..2T-1 unchanged) and mask = sigmoid(channels 2T..3T-1)
 __global__ void split_offset_mask_kernel(const float* __restrict__ om, float* __restrict__ offset,
-                                         float* __restrict__ mask, int rows, int T, long long HW) {
+                                         float* __restrict__ mask, int rows, int T, long long HW, int vec) {
   for (int row = blockIdx.y; row < rows; row += gridDim.y) {
     const int b = row / (3 * T), c = row - b * 3 * T;
     const float* s = om + (size_t)row * HW;
     const bool is_mask = c >= 2 * T;
     float* d = is_mask ? mask + ((size_t)b * T + (c - 2 * T)) * HW : offset + ((size_t)b * 2 * T + c) * HW;
-    if ((HW & 3) == 0) {
+    if (vec) {
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (HW >> 2); i += (long long)gridDim.x * blockDim.x) {
             float4 v = reinterpret_cast<const float4*>(s)[i];
             if (is_mask) {
@@ -572,14 +572,14 @@ __global__ void split_offset_mask_kernel(const float* __restrict__ om, float* __
 }
 __global__ void split_offset_mask_bwd_kernel(const float* __restrict__ goff, const float* __restrict__ gmask,
                                              const float* __restrict__ mask, float* __restrict__ gom, int rows,
-                                             int T, long long HW) {
+                                             int T, long long HW, int vec) {
   for (int row = blockIdx.y; row < rows; row += gridDim.y) {
     const int b = row / (3 * T), c = row - b * 3 * T;
     float* d = gom + (size_t)row * HW;
     const bool is_mask = c >= 2 * T;
     const float* g = is_mask ? gmask + ((size_t)b * T + (c - 2 * T)) * HW : goff + ((size_t)b * 2 * T + c) * HW;
     const float* m = mask + ((size_t)b * T + (is_mask ? c - 2 * T : 0)) * HW;
-    if ((HW & 3) == 0) {
+    if (vec) {
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (HW >> 2); i += (long long)gridDim.x * blockDim.x) {
             float4 v = reinterpret_cast<const float4*>(g)[i];
             if (is_mask) {
@@ -835,9 +835,7 @@ extern "C" int cnuda_dwconvt2d_add_forward(const float* x, const float* w, const
     if (upsample && s == 2 && rows == 4 && (H & 1) == 0 && (W & 1) == 0)
         CNUDA_LAUNCH(dwconvt_fwd_k4s2_kernel, dim3(ceil_div((long long)(H / 2) * (W / 2), kT), B * C), dim3(kT), 0,
                            (hipStream_t)stream, x, w, skip, y, C, H, W);
-    else if (upsample && s == 2 && rows == 4)
-        CNUDA_LAUNCH((dwconvt_fwd_f_kernel<2, 4>), fgrid, dim3(kT), 0, (hipStream_t)stream, x, w, skip, y, C, H, W);
-    else if (upsample && s == 2)
+    else if (upsample && s == 2)         // (rows == 4 means H and W even here: the branch above has taken it)
         CNUDA_LAUNCH((dwconvt_fwd_f_kernel<2, 1>), fgrid, dim3(kT), 0, (hipStream_t)stream, x, w, skip, y, C, H, W);
     else if (upsample && rows == 4)
         CNUDA_LAUNCH((dwconvt_fwd_f_kernel<4, 4>), fgrid, dim3(kT), 0, (hipStream_t)stream, x, w, skip, y, C, H, W);
@@ -882,7 +880,7 @@ static int dwconv_forward(const char* who, const float* x, const float* w, float
 #define CNUDA_DWV(K, S, PL) CNUDA_LAUNCH((dwconv_fwd_vec_kernel<K, S, PL>), grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, pt)
 #define CNUDA_DWP(K, S) do { if (pl == 0) CNUDA_DWV(K, S, 0); else if (pl == 1) CNUDA_DWV(K, S, 1); else CNUDA_DWV(K, S, 2); } while (0)
         if (k == 3 && s == 1) CNUDA_DWP(3, 1);
-        else if (k == 3) CNUDA_DWP(3, 2);
+        else if (k == 3) CNUDA_DWP(3, 2);      // (no geometry reaches <3, 2, 2>: W % 4 == 0 and left padding 2 make Wo odd)
         else if (s == 1) CNUDA_DWP(5, 1);
         else CNUDA_DWP(5, 2);
 #undef CNUDA_DWP
@@ -1017,8 +1015,10 @@ extern "C" int cnuda_add(const float* a, const float* b, float* out, long long n
 extern "C" int cnuda_act_backward(const float* grad_y, const float* y, float* grad_x, long long n, float slope,
                                   cnuda_stream_t stream) {
     CNUDA_REQUIRE(grad_y && y && grad_x && n > 0, "cnuda_act_backward: bad arguments");
-    CNUDA_LAUNCH(act_bwd_kernel, dim3(stream_grid(n, kT)), dim3(kT), 0, (hipStream_t)stream, grad_y, y, grad_x, n,
-                       slope);
+    // 16-byte accesses for the aligned quads; a view at an odd offset takes the scalar loop, as in cnuda_add
+    const bool aligned = (((uintptr_t)grad_y | (uintptr_t)y | (uintptr_t)grad_x) & 15) == 0;
+    CNUDA_LAUNCH(act_bwd_kernel, dim3(stream_grid(n, kT)), dim3(kT), 0, (hipStream_t)stream, grad_y, y, grad_x,
+                       aligned ? n / 4 : 0, n, slope);
     return check_launch("cnuda_act_backward");
 }
 extern "C" int cnuda_conv1x1_backward_data_act(const float* grad_y, const float* weight, const float* hidden,
@@ -1046,6 +1046,9 @@ extern "C" int cnuda_conv1x1_backward_data_act(const float* grad_y, const float*
 #undef CNUDA_C1
     return check_launch("cnuda_conv1x1_backward_data_act");
 }
+static int rows_vec_ok(long long HW, const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
+    return (HW & 3) == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
 extern "C" int cnuda_copy_channels(const float* src, float* dst, int B, int Cn, long long HW, int Csrc, int src_off,
                                    int Cdst, int dst_off, cnuda_stream_t stream) {
     CNUDA_REQUIRE(src && dst && B > 0 && Cn > 0 && HW > 0, "cnuda_copy_channels: bad arguments");
@@ -1055,7 +1058,7 @@ extern "C" int cnuda_copy_channels(const float* src, float* dst, int B, int Cn, 
     const long long rows = (long long)B * Cn;
     CNUDA_REQUIRE(rows < (1ll << 31), "cnuda_copy_channels: too many planes");
     CNUDA_LAUNCH(copy_channels_kernel, dim3(chunks, (unsigned)(rows < 65535 ? rows : 65535)), dim3(kT), 0,
-                       (hipStream_t)stream, src, dst, (int)rows, Cn, HW, Csrc, src_off, Cdst, dst_off);
+                       (hipStream_t)stream, src, dst, (int)rows, Cn, HW, Csrc, src_off, Cdst, dst_off, rows_vec_ok(HW, src, dst));
     return check_launch("cnuda_copy_channels");
 }
 extern "C" int cnuda_split_offset_mask(const float* om, float* offset, float* mask, int B, int taps, long long HW,
@@ -1065,7 +1068,7 @@ extern "C" int cnuda_split_offset_mask(const float* om, float* offset, float* ma
     const long long rows = (long long)B * 3 * taps;
     CNUDA_REQUIRE(rows < (1ll << 31), "cnuda_split_offset_mask: too many planes");
     CNUDA_LAUNCH(split_offset_mask_kernel, dim3(chunks, (unsigned)(rows < 65535 ? rows : 65535)), dim3(kT), 0,
-                       (hipStream_t)stream, om, offset, mask, (int)rows, taps, HW);
+                       (hipStream_t)stream, om, offset, mask, (int)rows, taps, HW, rows_vec_ok(HW, om, offset, mask));
     return check_launch("cnuda_split_offset_mask");
 }
 extern "C" int cnuda_split_offset_mask_backward(const float* grad_offset, const float* grad_mask, const float* mask,
@@ -1076,6 +1079,7 @@ extern "C" int cnuda_split_offset_mask_backward(const float* grad_offset, const 
     const long long rows = (long long)B * 3 * taps;
     CNUDA_REQUIRE(rows < (1ll << 31), "cnuda_split_offset_mask_backward: too many planes");
     CNUDA_LAUNCH(split_offset_mask_bwd_kernel, dim3(chunks, (unsigned)(rows < 65535 ? rows : 65535)), dim3(kT), 0,
-                       (hipStream_t)stream, grad_offset, grad_mask, mask, grad_om, (int)rows, taps, HW);
+                       (hipStream_t)stream, grad_offset, grad_mask, mask, grad_om, (int)rows, taps, HW,
+                       rows_vec_ok(HW, grad_offset, grad_mask, mask, grad_om));
     return check_launch("cnuda_split_offset_mask_backward");
 }

@@ -550,4 +550,48 @@ MANIFEST = {
         'tests/test_gpu_ops.py::test_convolution_epilogue_leaves_batchnorm_statistics',
         'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
     ],
+    # ---- the plane-wise operators' dispatch forms that no benched step launches (MobileNetV2 / EfficientNet trunks, odd
+    # shapes, views off 16-byte alignment): tests/test_gpu_spatial_forms.py selects each by shape and asserts it by name ----
+    **{'dwconv_fwd_vec_kernel<%d, %d, %d>' % f: [
+        'tests/test_gpu_spatial_forms.py::test_depthwise_every_vector_forward_form[k%ds%dpl%d_' % f]
+       for f in [(3, 1, 0), (3, 1, 1), (3, 1, 2), (3, 2, 0), (3, 2, 1), (5, 1, 0), (5, 1, 1), (5, 1, 2), (5, 2, 0), (5, 2, 1),
+                 (5, 2, 2)]},
+    **{'dwconv_fwd_kernel<%d>' % k: ['tests/test_gpu_spatial_forms.py::test_depthwise_both_scalar_forward_forms[k%d_' % k,
+                                     'tests/test_gpu_spatial_forms.py::test_depthwise_vector_forms_give_the_scalar_forms_bits[%d-' % k]
+       for k in (3, 5)},
+    **{'dwconv_bwd_data_kernel<%d, 4>' % k: ['tests/test_gpu_spatial_forms.py::test_depthwise_every_vector_forward_form[k%d' % k,
+                                             'tests/test_gpu_spatial_forms.py::test_depthwise_beyond_the_workgroup_cap[260-256-%d-' % k]
+       for k in (3, 5)},
+    **{'dwconv_bwd_data_kernel<%d, 1>' % k: ['tests/test_gpu_spatial_forms.py::test_depthwise_both_scalar_forward_forms[k%d_7x9' % k,
+                                             'tests/test_gpu_spatial_forms.py::test_depthwise_vector_forms_give_the_scalar_forms_bits[%d-' % k]
+       for k in (3, 5)},
+    **{'dwconv_bwd_weight_kernel<%d>' % k: ['tests/test_gpu_spatial_forms.py::test_depthwise_every_vector_forward_form[k%d' % k,
+                                            'tests/test_gpu_spatial_forms.py::test_depthwise_both_scalar_forward_forms[k%d_' % k]
+       for k in (3, 5)},
+    'dwconvt_fwd_kernel': [
+        'tests/test_gpu_spatial_forms.py::test_depthwise_transposed_every_forward_form[dwconvt_fwd_kernel',
+        'tests/test_gpu_spatial_forms.py::test_depthwise_transposed_any_geometry[3-2-1',
+    ],
+    'dwconvt_fwd_f_kernel<4, 1>': [
+        'tests/test_gpu_spatial_forms.py::test_depthwise_transposed_every_forward_form[dwconvt_fwd_f_kernel<4, 1>',
+    ],
+    'dwconvt_bwd_kernel<4>': [
+        'tests/test_gpu_spatial_forms.py::test_depthwise_transposed_any_geometry[4-1-1',
+        'tests/test_gpu_spatial_forms.py::test_depthwise_transposed_any_geometry[4-4-0',
+        'tests/test_gpu_spatial_forms.py::test_depthwise_transposed_k4s2_backward_gives_the_generic_kernels_input_gradient',
+    ],
+    'dwconvt_bwd_data_kernel': [
+        'tests/test_gpu_spatial_forms.py::test_depthwise_transposed_any_geometry[3-2-1',
+        'tests/test_gpu_spatial_forms.py::test_depthwise_transposed_any_geometry[16-8-4',
+    ],
+    'dwconvt_bwd_weight_kernel': [
+        'tests/test_gpu_spatial_forms.py::test_depthwise_transposed_any_geometry[3-2-1',
+        'tests/test_gpu_spatial_forms.py::test_depthwise_transposed_any_geometry[16-8-4',
+    ],
+    'maxpool_bwd_tail_kernel': [
+        'tests/test_gpu_spatial_forms.py::test_maxpool_scalar_kernels_and_the_uncovered_tail[shape0',
+        'tests/test_gpu_spatial_forms.py::test_maxpool_scalar_kernels_and_the_uncovered_tail[shape1',
+    ],
+    **{'conv1x1_dgrad_act_kernel<%d>' % co: ['tests/test_gpu_spatial_forms.py::test_head_gradient_every_output_count[%d-' % co]
+       for co in (1, 4, 5, 7, 8)},
 }

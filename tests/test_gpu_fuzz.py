@@ -97,6 +97,38 @@ def test_conv_transpose2d_random_geometry(case):
     _close(dw.grad, w.grad, what='gw')
 
 
+def _depthwise_cases(n, seed):
+    rs = np.random.RandomState(seed)
+    out = []
+    while len(out) < n:
+        k, s, p = int(rs.choice([3, 5])), int(rs.choice([1, 2, 3])), int(rs.randint(0, 4))
+        B, C, H = int(rs.randint(1, 4)), int(rs.choice([1, 3, 5, 8])), int(rs.randint(2, 21))
+        W = 4 * int(rs.randint(1, 6)) if rs.randint(2) else int(rs.randint(2, 21))      # about half take the 16-byte forms
+        if H + 2 * p < k or W + 2 * p < k:
+            continue
+        out.append((B, C, H, W, k, s, p))
+    return out
+
+
+@pytest.mark.parametrize('case', _depthwise_cases(16, 31), ids=lambda c: 'B%dC%dH%dW%dk%ds%dp%d' % c)
+def test_depthwise_conv2d_random_geometry(case):
+    """ops.depthwise_conv2d (cnuda_dwconv2d_*: any stride and padding) against an fp64 grouped convolution"""
+    from hip_runtime import ops
+    B, C, H, W, k, s, p = case
+    g = torch.Generator().manual_seed(sum(v * 31 ** i for i, v in enumerate(case)) % 100000)
+    x, w = torch.randn(B, C, H, W, generator=g), torch.randn(C, 1, k, k, generator=g) / k
+    xr, wr = x.double().requires_grad_(True), w.double().requires_grad_(True)
+    y = F.conv2d(xr, wr, None, s, p, 1, C)
+    gy = torch.randn(y.shape, generator=g)
+    y.backward(gy.double())
+    dx, dw = x.to(DEV).requires_grad_(True), w.to(DEV).requires_grad_(True)
+    dy = ops.depthwise_conv2d(dx, dw, s, p)
+    dy.backward(gy.to(DEV))
+    _close(dy, y, what='y')
+    _close(dx.grad, xr.grad, what='gx')
+    _close(dw.grad, wr.grad, what='gw')
+
+
 def _dcn_cases(n, seed):
     rs = np.random.RandomState(seed)
     out = []
