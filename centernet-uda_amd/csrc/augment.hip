@@ -9,6 +9,7 @@
 // -ffp-contract=off and hipcc's correctly rounded fp32 divide), so colour and warp are bit-identical to the numpy
 // restatement in tests/augment_oracle.py.  The gather is byte-granular and lives on L2; no rate is claimed for it.
 #include "common.h"
+#include "philox.h"
 
 namespace cnuda {
 namespace {
@@ -93,26 +94,13 @@ __global__ __launch_bounds__(256) void augment_color_kernel(const unsigned char*
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// noise: Philox4x32-10 (Salmon et al., SC'11), key = the 64-bit seed, counter = (pixel index, image id)
+// noise: Philox4x32-10 (philox.h), key = the 64-bit seed, counter = (pixel index, image id)
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0, c[1] = lo1, c[2] = n2, c[3] = lo0;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-}
-
 // one standard normal deviate per (seed, image id, pixel): Box-Muller on two 23-bit uniforms in (0, 1)
 __device__ __forceinline__ float normal_deviate(unsigned long long seed, long long id, long long pixel) {
-    uint32_t c[4] = {(uint32_t)pixel, (uint32_t)((unsigned long long)pixel >> 32), (uint32_t)id,
-                     (uint32_t)((unsigned long long)id >> 32)};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float u1 = ((float)(c[0] >> 9) + 0.5f) * (1.0f / 8388608.0f);
-    const float u2 = ((float)(c[1] >> 9) + 0.5f) * (1.0f / 8388608.0f);
+    uint32_t c[4];
+    philox_pixel_block(seed, id, pixel, c);
+    const float u1 = philox_uniform(c[0]), u2 = philox_uniform(c[1]);
     return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
 

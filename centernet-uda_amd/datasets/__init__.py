@@ -9,4 +9,5 @@ cv2.  Image decoding stays on the host."""
 from .augment import (AugmentParams, Augmentation, augment_images, build_batch, transform_boxes,   # noqa: F401
                       transform_points)
 from .prepare import prepare_input   # noqa: F401
+from .strong_view import StrongView, StrongViewParams   # noqa: F401  (the function: datasets.strong_view.strong_view)
 from .targets import encode_targets   # noqa: F401

@@ -190,6 +190,8 @@ class _Sig:
     cnuda_pack_refresh_ranges = (_I, [_P, _P, _I, ctypes.c_ulonglong, ctypes.c_ulonglong, _P, ctypes.c_size_t, _P])
     cnuda_ema_update = (_I, [_P, _I, ctypes.c_uint, _F, _F, _P])
     cnuda_pseudo_labels = (_I, [_P] * 6 + [_I] * 6 + [_F, _P])
+    cnuda_strong_view_pivot = (_I, [_P] * 5 + [_I] * 3 + [_P])
+    cnuda_strong_view = (_I, [_P] * 7 + [_I] + [_P] * 2 + [ctypes.c_ulonglong, _P] + [_I] * 3 + [_P])
     cnuda_pack_cache_used = (c_size_t, [])
     cnuda_pack_cache_fills = (ctypes.c_ulonglong, [])
     cnuda_pack_cache_resets = (ctypes.c_ulonglong, [])

@@ -11,6 +11,7 @@ _PLUGINS = {
     'IWMaxSquaresMinimization': 'uda.max_squares_minimization',
     'AdversarialEntropyMinimization': 'uda.adversarial_entropy_minimization',
     'MeanTeacher': 'uda.mean_teacher',
+    'WeakStrongTeacher': 'uda.mean_teacher',
 }
 __all__ = sorted(_PLUGINS)
 

@@ -8,9 +8,9 @@ A training step, with `n` EMA updates done so far:
   2. otherwise the teacher (eval mode, no tape) sees `target_domain_input`: sigmoid_clamp_ on `hm`, decode_detection
      (K = cfg.max_detections), hip_runtime.ops.pseudo_labels (per-class score thresholds, minimum extent, the mirror),
      datasets.targets.encode_targets -- a batch like the loader's, built on the device, nothing read back;
-  3. the student's step is `step_with_target_term` over source | target (the mirrored target with `mirror_student`),
-     target term `pseudo_weight * centernet_loss(target outputs, pseudo batch)`; its statistics are logged under the
-     loss's own names prefixed `pseudo_` (unweighted) plus `pseudo_boxes`, the mean number of pseudo-labels per image;
+  3. the student's step is `step_with_target_term` over source | `student_view(target)` (the mirrored target with
+     `mirror_student`; WeakStrongTeacher: the strong view of it), target term
+     `pseudo_weight * centernet_loss(target outputs, pseudo batch)`; its statistics are logged under the loss's own names prefixed `pseudo_` (unweighted) plus `pseudo_boxes`, the mean number of pseudo-labels per image;
   4. right behind optimizer.step(): decay_t = min(decay, (1 + n) / (10 + n)), one cnuda_ema_update launch over the
      teacher's flat parameter buffer and every buffer, n += 1 -- during burn-in too.
 
@@ -168,6 +168,14 @@ class MeanTeacher(Model):
         batch['kept'] = labels['kept']
         return batch
 
+    def student_view(self, target_input):
+        """What the student sees of the target batch the teacher labelled: the mirror with `mirror_student` (the
+        pseudo-labels are mirrored with it), else the batch itself.  Never writes `target_input`."""
+        if self.mirror_student:
+            from predict import mirror_input
+            return mirror_input(target_input)
+        return target_input
+
     def step(self, data, is_training=True):
         if not is_training:
             if not self.evaluate_teacher:
@@ -182,9 +190,7 @@ class MeanTeacher(Model):
         self._to_device(data)
         pseudo = self.pseudo_batch(data['target_domain_input'])
         view = dict(data)                   # the caller's batch keeps its tensors
-        if self.mirror_student:
-            from predict import mirror_input
-            view['target_domain_input'] = mirror_input(data['target_domain_input'])
+        view['target_domain_input'] = self.student_view(data['target_domain_input'])
 
         def target_term(target_outputs, _):
             # (a shallow copy: the loss rebinds `hm` to probabilities, the returned outputs keep the logits)
@@ -223,3 +229,28 @@ class MeanTeacher(Model):
         extra = {'teacher_state_dict': self.teacher.state_dict(), 'teacher_updates': self.teacher_updates}
         helper.save_model(self.backend, path, epoch, self.optimizer if with_optimizer else None,
                           self.scheduler if with_optimizer else None, extra=extra)
+
+
+class WeakStrongTeacher(MeanTeacher):
+    """MeanTeacher whose student trains on a STRONG view of the target batch ("Strong view"): the teacher labels
+    `target_domain_input` as it is; the student sees its mirror (with `mirror_student`) through colour jitter, grayscale,
+    gaussian blur and random erasing (datasets/strong_view.py, csrc/strongview.hip) -- photometric or occluding, so the
+    teacher's boxes stay valid.  `strong_view`: the sampler's mapping (None: its defaults); the other arguments are
+    MeanTeacher's.  Step n (= teacher_updates, which the checkpoint carries) draws from
+    np.random.default_rng([cfg.seed, 0x57534B, n]) with fill counters n B .. n B + B - 1: a resumed run continues the
+    same stream.  Burn-in, evaluation, checkpoints and statistics are the parent's."""
+
+    def __init__(self, pseudo_weight, strong_view=None, **mean_teacher_arguments):
+        super().__init__(pseudo_weight, **mean_teacher_arguments)
+        from datasets.strong_view import StrongView
+        self.strong_view = StrongView(strong_view)
+
+    def student_view(self, target_input):
+        import numpy as np
+        from datasets.strong_view import strong_view
+        x = super().student_view(target_input)
+        B, _, H, W = x.shape
+        n = self.teacher_updates
+        params = self.strong_view.sample(B, H, W, np.random.default_rng([int(self.cfg.seed), 0x57534B, n]),
+                                         first_id=n * B)
+        return strong_view(x, params, self.cfg.normalize.mean, self.cfg.normalize.std)

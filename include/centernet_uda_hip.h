@@ -951,6 +951,38 @@ int cnuda_pseudo_labels(const float* dets, const float* thresholds, double* geom
                         float* kept, int B, int K, int C, int rotated, int mirror, int map_width, float min_size,
                         cnuda_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * Strong view (datasets/strong_view.py, uda.WeakStrongTeacher; csrc/strongview.hip; DESIGN.md, "Strong view").  No
+ * reference counterpart.  Colour jitter, grayscale, gaussian blur and random erasing on a normalised batch
+ * x [B,3,H,W] f32 (channel 0 = R), drawn on the host and applied from per-image DEVICE tables.  Every float32 step is
+ * one IEEE operation in the written order, only + - * / min max: numpy's float32 arithmetic bit for bit.  Caller's stream.
+ * With v_c = clamp(x_c * std_c + mean_c, 0, 1) and luma(v) = (0.299f v_R + 0.587f v_G) + 0.114f v_B:
+ * ---------------------------------------------------------------------- */
+/* pivot[b] = the mean luma of image b before any step: q = (unsigned)rintf(luma(v) * 65536.0f) per pixel, summed in
+ * 64-bit integers (atomics on an integer: the same bits on every run), pivot = (float)((double)sum / (65536.0 H W)).
+ * mean, std [3] and pivot [B] on the device; workspace: 16 B bytes on the device, 8-byte aligned, cleared here. */
+int cnuda_strong_view_pivot(const float* x, const float* mean, const float* std, float* pivot, void* workspace,
+                            int B, int H, int W, cnuda_stream_t stream);
+/* y [B,3,H,W] f32, a buffer that does not overlap x (x is never written).  Tables, all on the device:
+ *   photo [B,4] f32 (brightness fb, contrast fc, saturation fs, gray flag 0 / 1); taps [B,13] f32 with radius [B] int32
+ *   (image b blurs with taps[b, 0 .. 2 radius[b]]; radius is clamped to 0..max_radius, max_radius <= 6 is the caller's
+ *   statement of the largest one); rects [B,3,4] int32 (x0, y0, x1, y1) half-open, empty when x1 <= x0 or y1 <= y0;
+ *   ids [B] int64; pivot [B] f32, read only for images with fc != 1 (cnuda_strong_view_pivot).
+ * Per image, in this order; a factor that is exactly 1 skips its step:
+ *   1 brightness  v_c = min(v_c fb, 1)                          2 contrast    v_c = clamp((v_c - pivot) fc + pivot, 0, 1)
+ *   3 saturation  g = luma(v), v_c = clamp((v_c - g) fs + g, 0, 1)   4 gray   v_c = luma(v)
+ *   5 blur        horizontal pass, its float32 result kept, then the vertical pass; each is acc = 0, then for k
+ *                 ascending acc = acc + taps[k] v[at + k - radius] with neighbour indices clamped to the image;
+ *                 radius 0 skips it
+ *   6 out         y_c = (v_c - mean_c) / std_c
+ * Inside a non-empty rectangle y_c = (u_c * 2 - 1) * 1.7320508f instead, u_c = ((float)(word_c >> 9) + 0.5f) / 2^23,
+ * word_0..2 from the Philox4x32-10 block with key = seed and counter = (pixel index y W + x, ids[b]): the value of a
+ * pixel depends on (seed, id, pixel) alone.  An image with fb = fc = fs = 1, no gray and radius 0 is neutral: outside
+ * rectangles y has x's bits (the round trip through v is not exact and is not taken). */
+int cnuda_strong_view(const float* x, float* y, const float* mean, const float* std, const float* photo,
+                      const float* taps, const int* radius, int max_radius, const int* rects, const long long* ids,
+                      unsigned long long seed, const float* pivot, int B, int H, int W, cnuda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
