@@ -1516,3 +1516,84 @@ def pseudo_labels(dets, thresholds, map_width, *, rotated=False, mirror=False, m
                                     ptr(out['kept']), B, K, thresholds.numel(), 1 if rotated else 0,
                                     1 if mirror else 0, int(map_width), float(min_size), stream()), 'pseudo_labels')
     return out
+
+
+# ---------------------------------------------------------------------------
+# Dense teacher (csrc/dense.hip; DESIGN.md, "Dense teacher")
+# ---------------------------------------------------------------------------
+def _check_ratio(who, ratio):
+    ratio = float(ratio)
+    if not 0.0 < ratio <= 1.0:
+        raise ValueError("%s: ratio must be in (0, 1], got %r" % (who, ratio))
+    return ratio
+
+
+def dense_select(teacher_hm, ratio):
+    """teacher_hm [B, C, H, W] logits -> (tau [B] float32, count [B] int32): per image the k-th largest channel-max
+    score, k = max(1, floor(ratio H W)), and how many positions reach it (every tie counts, so count >= k; -0 equals
+    +0; a NaN score is never selected).  The mask is `score >= tau[b]`.  Two launches, no gradient, no read-back."""
+    ratio = _check_ratio('dense_select', ratio)
+    require_gpu(teacher_hm)
+    if teacher_hm.dim() != 4 or teacher_hm.numel() == 0:
+        raise RuntimeError("dense_select: teacher_hm must be a non-empty [B, C, H, W], got %s" % (tuple(teacher_hm.shape),))
+    hm = f32c(teacher_hm.detach())
+    B, C, H, W = hm.shape
+    tau = torch.empty(B, dtype=torch.float32, device=hm.device)
+    count = torch.empty(B, dtype=torch.int32, device=hm.device)
+    ws = _ws(lib().cnuda_dense_select_workspace_bytes(B, H * W), hm)
+    check(lib().cnuda_dense_select(ptr(hm), ratio, ptr(tau), ptr(count), B, C, H * W, *ws, stream()), 'dense_select')
+    return tau, count
+
+
+class _DenseTeacher(Function):
+    """_IWMaxSquare's sibling with two differentiable inputs: the teacher's maps, tau and the forward's five results are
+    constants of the backward pass."""
+
+    @staticmethod
+    def forward(ctx, hm, wh, teacher_hm, teacher_wh, tau, count, mirror, hm_weight, wh_weight):
+        require_gpu(hm, wh, teacher_hm, teacher_wh, tau, count)
+        hm, wh, teacher_hm, teacher_wh = f32c(hm), f32c(wh), f32c(teacher_hm), f32c(teacher_wh)
+        B, C, H, W = hm.shape
+        out5 = torch.empty(5, dtype=torch.float32, device=hm.device)
+        check(lib().cnuda_dense_teacher_forward(ptr(hm), ptr(wh), ptr(teacher_hm), ptr(teacher_wh), ptr(tau), ptr(count),
+                                                ptr(out5), B, C, H, W, mirror, hm_weight, wh_weight, *_loss_ws(hm),
+                                                stream()), 'dense_teacher_forward')
+        ctx.call = (B, C, H, W, mirror, hm_weight, wh_weight)
+        ctx.save_for_backward(hm, wh, teacher_hm, teacher_wh, tau, out5)
+        stats = out5.clone()
+        ctx.mark_non_differentiable(stats)
+        return out5[0].clone(), stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gstats):
+        hm, wh, teacher_hm, teacher_wh, tau, out5 = ctx.saved_tensors
+        grad_hm, grad_wh = torch.empty_like(hm), torch.empty_like(wh)
+        up = f32c(g.reshape(1))
+        check(lib().cnuda_dense_teacher_backward(ptr(hm), ptr(wh), ptr(teacher_hm), ptr(teacher_wh), ptr(tau), ptr(out5),
+                                                 ptr(up), ptr(grad_hm), ptr(grad_wh), *ctx.call, stream()),
+              'dense_teacher_backward')
+        return (grad_hm, grad_wh) + (None,) * 7
+
+
+def dense_teacher_loss(hm, wh, teacher_hm, teacher_wh, tau, count, *, mirror, hm_weight=1.0, wh_weight=0.1):
+    """Dense Teacher's loss of the student's maps hm [B, C, H, W] (logits) and wh [B, 2, H, W] against the teacher's,
+    inside the selection (tau, count) = dense_select(teacher_hm, ratio); `mirror`: the student saw the mirrored image.
+    -> (hm_weight hm_loss + wh_weight wh_loss, stats [5] = that loss, hm_loss, wh_loss, N, sum u): a quality focal
+    loss (exponent 2) of sigmoid(hm) against sigmoid(teacher_hm) on the selection and 0 elsewhere, over N = sum count;
+    the L1 of the sizes weighted by u = sigmoid(score) (include/centernet_uda_hip.h).  The teacher's tensors carry no
+    gradient."""
+    for name, t in (('teacher_hm', teacher_hm), ('teacher_wh', teacher_wh), ('tau', tau)):
+        if t.requires_grad:
+            raise RuntimeError("dense_teacher_loss: %s requires grad; the teacher is a constant (detach it)" % name)
+    if hm.dim() != 4 or hm.numel() == 0:
+        raise RuntimeError("dense_teacher_loss: hm must be a non-empty [B, C, H, W], got %s" % (tuple(hm.shape),))
+    B, C, H, W = hm.shape
+    for name, t, shape in (('teacher_hm', teacher_hm, (B, C, H, W)), ('wh', wh, (B, 2, H, W)),
+                           ('teacher_wh', teacher_wh, (B, 2, H, W)), ('tau', tau, (B,)), ('count', count, (B,))):
+        if tuple(t.shape) != shape:
+            raise RuntimeError("dense_teacher_loss: %s is %s, expected %s" % (name, tuple(t.shape), shape))
+    if tau.dtype != torch.float32 or count.dtype != torch.int32 or not tau.is_contiguous() or not count.is_contiguous():
+        raise RuntimeError("dense_teacher_loss: tau must be contiguous float32 and count contiguous int32")
+    return _DenseTeacher.apply(hm, wh, teacher_hm, teacher_wh, tau, count, 1 if mirror else 0, float(hm_weight),
+                               float(wh_weight))

@@ -12,6 +12,7 @@ _PLUGINS = {
     'AdversarialEntropyMinimization': 'uda.adversarial_entropy_minimization',
     'MeanTeacher': 'uda.mean_teacher',
     'WeakStrongTeacher': 'uda.mean_teacher',
+    'DenseTeacher': 'uda.mean_teacher',
 }
 __all__ = sorted(_PLUGINS)
 

@@ -14,6 +14,10 @@ A training step, with `n` EMA updates done so far:
   4. right behind optimizer.step(): decay_t = min(decay, (1 + n) / (10 + n)), one cnuda_ema_update launch over the
      teacher's flat parameter buffer and every buffer, n += 1 -- during burn-in too.
 
+DenseTeacher replaces 2 and the target term of 3: the teacher's heads stay dense (no decode, no pseudo-labels, no target
+encoding), hip_runtime.ops.dense_select picks the top `ratio` of every image's positions and ops.dense_teacher_loss
+regresses the student's `hm` and `wh` onto the teacher's there ("Dense teacher").
+
 The teacher is a copy of the unwrapped backend made in `to()`.  It is not a submodule of the backend (the backend's
 state_dict, the optimizer and a data-parallel wrapper never see it); its trainable parameters are views of one flat
 float32 buffer laid out like the student's arena, so that they are ONE segment of the update against
@@ -254,3 +258,71 @@ class WeakStrongTeacher(MeanTeacher):
         params = self.strong_view.sample(B, H, W, np.random.default_rng([int(self.cfg.seed), 0x57534B, n]),
                                          first_id=n * B)
         return strong_view(x, params, self.cfg.normalize.mean, self.cfg.normalize.std)
+
+
+class DenseTeacher(WeakStrongTeacher):
+    """The mean teacher without pseudo-boxes ("Dense teacher"; Dense Teacher, Zhou et al., ECCV 2022): the
+    student regresses the teacher's heat map itself.  Per image the top `ratio` of the positions by the teacher's
+    channel-max logit are selected, every tie included (hip_runtime.ops.dense_select); the target term is
+    `pseudo_weight * (hm_weight * quality focal loss + wh_weight * score-weighted L1 of wh)` over that selection
+    (ops.dense_teacher_loss; `reg` takes no part).  No score threshold, no decode, no target encoding.
+
+    The step after burn-in: teacher forward (eval mode, no tape) on `target_domain_input`, dense_select, `student_view`
+    (`strong_view=False`: the plain mirror / identity view; None or a mapping: WeakStrongTeacher's strong view), then
+    `step_with_target_term`.  Statistics behind the source loss's: dense_loss, dense_hm_loss, dense_wh_loss,
+    dense_positions (selected positions per image), dense_score (their mean teacher score).  With a data-parallel
+    backend every rank normalises by its own selection.  The EMA, burn-in, checkpoints and evaluation are the parent's."""
+    target_grad_heads = ('hm', 'wh')
+
+    def __init__(self, pseudo_weight, ratio=0.01, hm_weight=1.0, wh_weight=0.1, strong_view=None, decay=0.999,
+                 burn_in_steps=0, mirror_student=True, evaluate_teacher=False):
+        super().__init__(pseudo_weight, strong_view=None if strong_view is False else strong_view, decay=decay,
+                         burn_in_steps=burn_in_steps, mirror_student=mirror_student, evaluate_teacher=evaluate_teacher)
+        if strong_view is False:
+            self.strong_view = None
+        if not 0.0 < float(ratio) <= 1.0:
+            raise ValueError("DenseTeacher: ratio=%r outside (0, 1]" % (ratio,))
+        for name, v in (('hm_weight', hm_weight), ('wh_weight', wh_weight)):
+            if not float(v) >= 0.0:
+                raise ValueError("DenseTeacher: %s=%r is negative" % (name, v))
+        self.ratio, self.hm_weight, self.wh_weight = float(ratio), float(hm_weight), float(wh_weight)
+
+    def init_done(self):
+        params = self._model_params()
+        if int(params.get('num_keypoints', 0) or 0) > 0:
+            raise ValueError("DenseTeacher: model.backend.params.num_keypoints=%r: the dense loss has no keypoint term; "
+                             "train a model without the keypoint head" % (params.num_keypoints,))
+        if bool(params.get('rotated_boxes', False)):
+            raise ValueError("DenseTeacher: model.backend.params.rotated_boxes is set: wh carries an angle channel "
+                             "whose mirror is a sign flip, which the dense loss does not build")
+
+    def student_view(self, target_input):
+        if self.strong_view is None:
+            return MeanTeacher.student_view(self, target_input)
+        return super().student_view(target_input)
+
+    @staticmethod
+    def dense_stats(stats5, batch_size):
+        """ops.dense_teacher_loss's five results as the step's statistics, in their logged order."""
+        return {'dense_loss': stats5[0], 'dense_hm_loss': stats5[1], 'dense_wh_loss': stats5[2],
+                'dense_positions': stats5[3] / batch_size, 'dense_score': stats5[4] / stats5[3].clamp(min=1.0)}
+
+    def step(self, data, is_training=True):
+        if not is_training or self.teacher_updates < self.burn_in_steps:
+            return super().step(data, is_training)
+        from hip_runtime import ops
+        self._to_device(data)
+        target = data['target_domain_input']
+        with torch.no_grad():
+            heads = self.teacher(target)
+        teacher_hm, teacher_wh = heads['hm'], heads['wh']
+        tau, count = ops.dense_select(teacher_hm, self.ratio)
+        view = dict(data)                   # the caller's batch keeps its tensors
+        view['target_domain_input'] = self.student_view(target)
+
+        def target_term(target_outputs, _):
+            loss, stats5 = ops.dense_teacher_loss(target_outputs['hm'], target_outputs['wh'], teacher_hm, teacher_wh,
+                                                  tau, count, mirror=self.mirror_student, hm_weight=self.hm_weight,
+                                                  wh_weight=self.wh_weight)
+            return loss * self.pseudo_weight, self.dense_stats(stats5, teacher_hm.shape[0])
+        return self.step_with_target_term(view, True, target_term)

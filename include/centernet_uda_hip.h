@@ -983,6 +983,39 @@ int cnuda_strong_view(const float* x, float* y, const float* mean, const float* 
                       const float* taps, const int* radius, int max_radius, const int* rects, const long long* ids,
                       unsigned long long seed, const float* pivot, int B, int H, int W, cnuda_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * Dense teacher (uda.DenseTeacher; csrc/dense.hip; DESIGN.md, "Dense teacher").  No reference counterpart: Dense
+ * Teacher (Zhou et al., ECCV 2022) on CenterNet's heads.  All maps are contiguous fp32; teacher_hm, hm [B,C,H,W] are
+ * LOGITS, teacher_wh, wh [B,2,H,W].  With HW = H W, the score s[b,p] = max_c teacher_hm[b,c,p] (NaN if any channel is),
+ *   k = max(1, floor(ratio HW)) in double, tau[b] = the k-th largest s[b,.], M[b,p] = (s[b,p] >= tau[b]) as floats:
+ * every tie at tau is selected, -0 equals +0 (a zero tau is stored as +0), a NaN score orders below every number and is
+ * never selected; with fewer than k numbers in an image tau[b] = -inf (every number is selected, possibly none).
+ * count[b] = |M[b]| >= k.  Position p = (y, x) of the teacher is p' = (y, W-1-x) of the student with mirror != 0, else p.
+ *   y = sigmoid(teacher_hm) on M else 0, q = sigmoid(hm[p']), bce = max(x,0) - x y + log1p(exp(-|x|)), N = sum count
+ *   hm_loss = sum (y - q)^2 bce / max(N, 1);   u = sigmoid(s) on M else 0
+ *   wh_loss = sum u (|wh[b,0,p'] - teacher_wh[b,0,p]| + |wh[b,1,p'] - teacher_wh[b,1,p]|) / (sum u + 1e-4)
+ *   out5 = {hm_weight hm_loss + wh_weight wh_loss, hm_loss, wh_loss, N, sum u}
+ * Integer counters and fp64 sums in a fixed order: the same bits every run.  No call synchronises or reads back.
+ * 0 < ratio <= 1, C <= 1024 (the class limit of the library's per-image tables), HW < 2^31.
+ * ---------------------------------------------------------------------- */
+/* Bytes of device workspace cnuda_dense_select needs (the [B,HW] score keys); 0 for an invalid shape. */
+size_t cnuda_dense_select_workspace_bytes(int B, long long HW);
+/* tau [B] float32, count [B] int32.  Two launches: the channel-max score keys, then one workgroup per image selects. */
+int cnuda_dense_select(const float* teacher_hm, double ratio, float* tau, int32_t* count, int B, int C, long long HW,
+                       void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+/* workspace: cnuda_loss_workspace_bytes().  Two launches (the reduction and its one-workgroup tail). */
+int cnuda_dense_teacher_forward(const float* hm, const float* wh, const float* teacher_hm, const float* teacher_wh,
+                                const float* tau, const int32_t* count, float* out5, int B, int C, int H, int W,
+                                int mirror, float hm_weight, float wh_weight, void* workspace, size_t workspace_bytes,
+                                cnuda_stream_t stream);
+/* grad_hm [B,C,H,W] and grad_wh [B,2,H,W] are written whole (zeros included) by ONE launch; upstream: one device float;
+ * out5: what the forward wrote.  d/dx = (q - y) ((q - y)^2 + 2 q (1 - q) bce) / max(N, 1);  d/dwh = u sign(.) /
+ * (sum u + 1e-4), sign(0) = 0. */
+int cnuda_dense_teacher_backward(const float* hm, const float* wh, const float* teacher_hm, const float* teacher_wh,
+                                 const float* tau, const float* out5, const float* upstream, float* grad_hm,
+                                 float* grad_wh, int B, int C, int H, int W, int mirror, float hm_weight,
+                                 float wh_weight, cnuda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
