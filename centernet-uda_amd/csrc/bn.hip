@@ -363,6 +363,21 @@ int plane_splits(long long planes, long long HW, int per_block) {
     return (int)(want < 1 ? 1 : want);
 }
 
+// The whole launch plan of one (B, C, HW, groups) call: the reduction's split and the apply passes' grid.  The entry
+// points and cnuda_bn_plan all come through here.
+struct Plan {
+    Split sp;
+    long long planes;      // workgroups of an apply pass (x its plane splits)
+    int apply_splits;      // gridDim.y of bn_apply_kernel / bn_bwd_apply_kernel
+};
+Plan bn_plan(int B, int C, long long HW, int Bg) {
+    Plan p;
+    p.sp = pick_split(B, C, HW, Bg);
+    p.planes = (long long)B * C / p.sp.ips;
+    p.apply_splits = plane_splits(p.planes, HW, kBnThreads * 4);
+    return p;
+}
+
 }  // namespace
 }  // namespace cnuda
 
@@ -372,6 +387,20 @@ extern "C" size_t cnuda_bn_workspace_bytes(int B, int C, long long HW) {
     const Split sp = pick_split(B, C, HW, 1);          // (ips = 1: the most partials any grouping needs)
     const size_t s_max = sp.S > 64 * 8 ? (size_t)sp.S : (size_t)64 * 8;   // (or 64 folded partials for each of up to 8 groups)
     return (size_t)C * s_max * 2 * sizeof(double) + (size_t)C * 2 * sizeof(float) + 512;
+}
+
+// Which of the run-time forms of the kernels above a geometry takes: the answers of the very pick_split / plane_splits
+// calls that cnuda_bn_train_forward and cnuda_bn_backward make for (B, C, HW, groups).  No GPU needed.
+extern "C" int cnuda_bn_plan(int B, int C, long long HW, int groups, int* per_plane, int* images_per_workgroup,
+                             int* partials, int* apply_splits) {
+    CNUDA_REQUIRE(B > 0 && C > 0 && HW > 0, "cnuda_bn_plan: empty tensor");
+    CNUDA_REQUIRE(groups >= 1 && B % groups == 0, "cnuda_bn_plan: batch %d not divisible into %d groups", B, groups);
+    const Plan pl = bn_plan(B, C, HW, B / groups);
+    if (per_plane) *per_plane = pl.sp.per_plane;
+    if (images_per_workgroup) *images_per_workgroup = pl.sp.ips;
+    if (partials) *partials = pl.sp.S;
+    if (apply_splits) *apply_splits = pl.apply_splits;
+    return 0;
 }
 
 extern "C" int cnuda_bn_train_forward(const float* x, const float* gamma, const float* beta, const float* residual,
@@ -391,14 +420,14 @@ extern "C" int cnuda_bn_train_forward(const float* x, const float* gamma, const 
     CNUDA_REQUIRE(workspace && workspace_bytes >= cnuda_bn_workspace_bytes(B, C, HW),
                   "cnuda_bn_train_forward: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const Split sp = pick_split(B, C, HW, Bg);
+    const Plan pl = bn_plan(B, C, HW, Bg);
+    const Split& sp = pl.sp;
     double* partial = reinterpret_cast<double*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     CNUDA_LAUNCH(bn_reduce_kernel<0>, dim3(C, sp.S), dim3(kBnThreads), 0, st, x, (const float*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
                        (const float*)nullptr, partial, C, HW,
                        sp.chunk, sp.per_plane, sp.ips, sp.S, 0, Bg);
-    const long long planes = (long long)B * C / sp.ips;        // workgroups of the apply pass (x its plane splits)
-    CNUDA_LAUNCH(bn_apply_kernel, dim3((unsigned)planes, plane_splits(planes, HW, kBnThreads * 4)),
+    CNUDA_LAUNCH(bn_apply_kernel, dim3((unsigned)pl.planes, pl.apply_splits),
                        dim3(kBnThreads), 0, st, x, partial, sp.S, count, momentum, eps, save_mean, save_invstd,
                        running_mean, running_var, num_batches_tracked, gamma, beta, residual, y, C, HW, relu, groups, Bg,
                        sp.per_plane, sp.ips, 0);
@@ -435,9 +464,9 @@ extern "C" int cnuda_bn_train_forward_stats(const float* x, const float* stats, 
     CNUDA_REQUIRE((size_t)C * S * 2 * sizeof(double) + 512 <= workspace_bytes, "cnuda_bn_train_forward_stats: workspace");
     double* partial = reinterpret_cast<double*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     CNUDA_LAUNCH(bn_fold_stats_kernel, dim3((C + 15) / 16, S), dim3(256), 0, st, stats, rows, bpg, spl, partial, C, S);
-    const Split sp = pick_split(B, C, HW, Bg);                // (the apply pass's own grid: unchanged)
-    const long long planes = (long long)B * C / sp.ips;
-    CNUDA_LAUNCH(bn_apply_kernel, dim3((unsigned)planes, y ? plane_splits(planes, HW, kBnThreads * 4) : 1),
+    const Plan pl = bn_plan(B, C, HW, Bg);                    // (the apply pass's own grid: unchanged)
+    const Split& sp = pl.sp;
+    CNUDA_LAUNCH(bn_apply_kernel, dim3((unsigned)pl.planes, y ? pl.apply_splits : 1),
                        dim3(kBnThreads), 0, st, x, partial, S, count, momentum, eps, save_mean, save_invstd,
                        running_mean, running_var, num_batches_tracked, gamma, beta, residual, y, C, HW, relu, groups, Bg,
                        sp.per_plane, sp.ips, spl);
@@ -471,13 +500,13 @@ extern "C" int cnuda_bn_backward(const float* grad_y, const float* x, const floa
     hipStream_t st = (hipStream_t)stream;
     const int Bg = B / groups;
     const long long count = (long long)Bg * HW;
-    const Split sp = pick_split(B, C, HW, Bg);
+    const Plan pl = bn_plan(B, C, HW, Bg);
+    const Split& sp = pl.sp;
     uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
     double* partial = reinterpret_cast<double*>(base);
     CNUDA_LAUNCH(bn_reduce_kernel<1>, dim3(C, sp.S), dim3(kBnThreads), 0, st, x, grad_y, y, save_mean,
                        save_invstd, gamma, beta, partial, C, HW, sp.chunk, sp.per_plane, sp.ips, sp.S, relu, Bg);
-    const long long planes = (long long)B * C / sp.ips;
-    CNUDA_LAUNCH(bn_bwd_apply_kernel, dim3((unsigned)planes, plane_splits(planes, HW, kBnThreads * 4)),
+    CNUDA_LAUNCH(bn_bwd_apply_kernel, dim3((unsigned)pl.planes, pl.apply_splits),
                        dim3(kBnThreads), 0, st, grad_y, x, y, save_mean, save_invstd, gamma, beta, partial, sp.S, grad_gamma,
                        grad_beta, grad_x, grad_residual, C, HW, count, relu, groups, Bg, sp.per_plane, sp.ips);
     return check_launch("cnuda_bn_backward");

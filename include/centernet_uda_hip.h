@@ -493,6 +493,14 @@ int cnuda_conv2d_backward_weight(const float* x, const float* grad_y, float* gra
  * (nullable) receives the gradient flowing into the residual branch.
  * ---------------------------------------------------------------------- */
 size_t cnuda_bn_workspace_bytes(int B, int C, long long HW);
+/* The run-time form that train_forward / backward take for this geometry (one kernel body serves all of them, so the
+ * kernel names cannot tell): per_plane = chunks one (image, channel) plane is cut into for the statistics,
+ * images_per_workgroup = images of one channel that one workgroup takes (> 1 only with per_plane == 1), partials = fp64
+ * partial sums per channel (B / images_per_workgroup * per_plane), apply_splits = workgroups per plane (gridDim.y) of
+ * the two apply passes.  Every result pointer is nullable.  Answered by the entry points' own planning code; no GPU
+ * needed.  -1 (cnuda_last_error) for an empty tensor or a batch that `groups` does not divide. */
+int cnuda_bn_plan(int B, int C, long long HW, int groups, int* per_plane, int* images_per_workgroup, int* partials,
+                  int* apply_splits);
 int cnuda_bn_train_forward(const float* x, const float* gamma, const float* beta, const float* residual,
                            float* y, float* save_mean, float* save_invstd,
                            float* running_mean, float* running_var,

@@ -114,21 +114,38 @@ MANIFEST = {
         'tests/test_gpu_ops.py::test_batch_norm_backward_gate_recomputed_from_x_is_the_gate_read_from_y',
         'tests/test_gpu_ops.py::test_batch_norm_train_fwd_bwd_and_running_stats',
         'tests/test_gpu_fuzz.py::test_batch_norm_random_geometry',
+        'tests/test_gpu_bn_forms.py::test_train_every_split_form',
+        'tests/test_gpu_bn_forms.py::test_autograd_path_on_split_forms',
+        'tests/test_gpu_bn_forms.py::test_statistics_of_ill_conditioned_channels',
+        'tests/test_gpu_fuzz.py::test_batch_norm_random_split_geometry',
+        'tests/test_gpu_bn_forms.py::test_statistics_folded_from_block_sums',
     ],
     'bn_bwd_apply_kernel': [
         'tests/test_gpu_ops.py::test_batch_norm_backward_gate_recomputed_from_x_is_the_gate_read_from_y',
         'tests/test_gpu_ops.py::test_batch_norm_train_fwd_bwd_and_running_stats',
         'tests/test_gpu_fuzz.py::test_batch_norm_random_geometry',
+        'tests/test_gpu_bn_forms.py::test_train_every_split_form',
+        'tests/test_gpu_bn_forms.py::test_autograd_path_on_split_forms',
+        'tests/test_gpu_bn_forms.py::test_statistics_of_ill_conditioned_channels',
+        'tests/test_gpu_fuzz.py::test_batch_norm_random_split_geometry',
     ],
     'bn_reduce_kernel<0>': [
         'tests/test_gpu_ops.py::test_batch_norm_backward_gate_recomputed_from_x_is_the_gate_read_from_y',
         'tests/test_gpu_ops.py::test_batch_norm_train_fwd_bwd_and_running_stats',
         'tests/test_gpu_fuzz.py::test_batch_norm_random_geometry',
+        'tests/test_gpu_bn_forms.py::test_train_every_split_form',
+        'tests/test_gpu_bn_forms.py::test_autograd_path_on_split_forms',
+        'tests/test_gpu_bn_forms.py::test_statistics_of_ill_conditioned_channels',
+        'tests/test_gpu_fuzz.py::test_batch_norm_random_split_geometry',
     ],
     'bn_reduce_kernel<1>': [
         'tests/test_gpu_ops.py::test_batch_norm_backward_gate_recomputed_from_x_is_the_gate_read_from_y',
         'tests/test_gpu_ops.py::test_batch_norm_train_fwd_bwd_and_running_stats',
         'tests/test_gpu_fuzz.py::test_batch_norm_random_geometry',
+        'tests/test_gpu_bn_forms.py::test_train_every_split_form',
+        'tests/test_gpu_bn_forms.py::test_autograd_path_on_split_forms',
+        'tests/test_gpu_bn_forms.py::test_statistics_of_ill_conditioned_channels',
+        'tests/test_gpu_fuzz.py::test_batch_norm_random_split_geometry',
     ],
     'conv1x1_dgrad_act_kernel<2>': [
         'tests/test_gpu_ops.py::test_head_pair_is_one_tape_node_with_the_two_layers_values',
@@ -519,6 +536,10 @@ MANIFEST = {
     'maxpool_win_bwd_kernel': ['tests/test_gpu_resnet.py::test_max_pool_window_matches_torch'],
     'bn_fold_stats_kernel': [      # BatchNorm statistics from the producing GEMM's epilogue (round 5)
         'tests/test_gpu_ops.py::test_convolution_epilogue_leaves_batchnorm_statistics',
+        'tests/test_gpu_bn_forms.py::test_statistics_folded_from_block_sums',
+    ],
+    'bn_eval_kernel': [            # eval-mode BatchNorm + residual + ReLU / ReLU6 (validation and prediction, not the benched step)
+        'tests/test_gpu_bn_forms.py::test_eval_forms',
     ],
     'igemm_wgrad_kernel<ConvWBufLoaderC8, 32, 128>': [       # 8 | C, 64 does not: the 16 -> 32 stride-2 convolution (round 5)
         'tests/test_gpu_ops.py::test_conv2d_fwd_bwd[c16_s2',

@@ -209,6 +209,55 @@ def test_batch_norm_random_geometry(case):
     _close(rv_d, rv, 1e-5, 'running_var')
 
 
+def _bn_split_cases(seed):
+    """12 shapes in the three regions where csrc/bn.hip leaves the one-workgroup-per-plane form: four with a plane cut
+    into chunks (HW in [4097, 20000], B * C <= 8), four with several images per workgroup (more than 2048 planes per
+    statistics group, HW in [1, 40]), four with the apply grid cut (HW in [1025, 4096], B * C <= 16); `groups` is drawn
+    from the divisors of B.  -> (B, C, H, W, groups, act, res)"""
+    rs = np.random.RandomState(seed)
+
+    def tail(B):
+        groups = int(rs.choice([d for d in range(1, B + 1) if B % d == 0]))
+        return groups, int(rs.randint(3)), bool(rs.randint(2))
+
+    def plane(lo, hi):
+        while True:
+            H, W = int(rs.randint(1, 200)), int(rs.randint(1, 200))
+            if lo <= H * W <= hi:
+                return H, W
+
+    out = []
+    for _ in range(4):
+        B = int(rs.randint(1, 5))
+        C = int(rs.randint(1, 8 // B + 1))
+        out.append((B, C) + plane(4097, 20000) + tail(B))
+    for _ in range(4):
+        B = int(rs.choice([2, 4, 6, 8]))
+        groups, act, res = tail(B)
+        Bg = B // groups
+        C = int(rs.randint(2048 // Bg + 1, 9000 // Bg + 1))
+        H, W = plane(2 if Bg == 1 else 1, 40)
+        out.append((B, C, H, W, groups, act, res))
+    for _ in range(4):
+        B = int(rs.randint(1, 5))
+        C = int(rs.randint(1, 16 // B + 1))
+        out.append((B, C) + plane(1025, 4096) + tail(B))
+    return out
+
+
+@pytest.mark.parametrize('case', _bn_split_cases(2718), ids=lambda c: 'B%dC%dH%dW%dg%dact%dres%d' % c)
+def test_batch_norm_random_split_geometry(case):
+    """the fp64 oracle (tests/bn_oracle.py), the gate rule and the tolerances of tests/test_gpu_bn_forms.py, through
+    hip_runtime.ops.batch_norm_act"""
+    import test_gpu_bn_forms as forms
+    B, C, H, W, groups, act, res = case
+    c = forms.make_case((B, C, H, W), groups, act, res)
+    print('per_plane %d, images per workgroup %d, partials %d, apply splits %d' % forms.bo.plan(B, C, H * W, groups))
+    got = forms.run_autograd(c)
+    assert got['launched'] == forms.TRAIN_KERNELS, got['launched']
+    forms.check_case(c, got)
+
+
 def _decode_cases(n, seed):
     rs = np.random.RandomState(seed)
     out = []
