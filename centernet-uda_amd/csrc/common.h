@@ -86,6 +86,10 @@ bool wave_specialised();
 bool buffer_addressing();
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+// every pointer given is 16-byte aligned (a null pointer counts as aligned: an absent optional tensor)
+inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
 
 // grid cap for grid-stride memory-bound kernels: 256 CUs x 8 resident blocks
 constexpr int kMaxStreamBlocks = 2048;

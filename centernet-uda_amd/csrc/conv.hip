@@ -47,8 +47,7 @@ struct ConvFwdStatsParams : ConvFwdParams {
 struct ConvFwdSigParams : ConvFwdParams {
     int sig_from;
 };
-// (the expression of cnuda_split_offset_mask, which this replaces: bit-identical masks)
-__device__ __forceinline__ float conv_row_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+// (sigmoid_f32, the expression of cnuda_split_offset_mask, which this replaces: bit-identical masks)
 
 // B[k = tap*C + c][n] = x[b][c][oy*sh - ph + r][ox*sw - pw + s]   (0 outside)
 template <bool FAST>
@@ -196,14 +195,14 @@ struct ConvFwdBufSigLoader : ConvFwdBufLoader {
         __device__ Out(const Params& p, long long n) : ConvFwdLoader<true>::Out(p, n) {}
         __device__ __forceinline__ void store(const Params& p, int m, float v) {
             if (p.bias) v += p.bias[m];
-            if (m >= p.sig_from) v = conv_row_sigmoid(v);
+            if (m >= p.sig_from) v = sigmoid_f32(v);
             base[(size_t)m * HoWo] = v;
         }
         __device__ __forceinline__ void store4(const Params& p, int m, f32x4 v) {
             if (p.bias) v += p.bias[m];
             if (m >= p.sig_from) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = conv_row_sigmoid(v[e]);
+                for (int e = 0; e < 4; ++e) v[e] = sigmoid_f32(v[e]);
             }
             *reinterpret_cast<f32x4*>(base + (size_t)m * HoWo) = v;
         }

@@ -782,7 +782,7 @@ __global__ __launch_bounds__(kThreads) void merge_decode_kernel(
             d[5] = (float)cls;
         } else {
             const float a = wh[((size_t)b * wh_ch + 2) * HW + idx];
-            float sg = 1.0f / (1.0f + expf(-a));
+            float sg = sigmoid_f32(a);
             sg = fminf(fmaxf(sg, 1e-4f), 1.0f - 1e-4f);
             d[0] = xs;
             d[1] = ys;

@@ -288,8 +288,6 @@ __global__ __launch_bounds__(kT) void dense_grad_kernel(DenseMaps m, const float
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
 }  // namespace cnuda
 

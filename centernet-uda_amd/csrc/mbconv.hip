@@ -10,10 +10,9 @@ namespace {
 
 constexpr int kT = 256;
 
-__device__ __forceinline__ float sigmoidf(float v) { return 1.0f / (1.0f + expf(-v)); }
-__device__ __forceinline__ float swishf(float v) { return v * sigmoidf(v); }
+__device__ __forceinline__ float swishf(float v) { return v * sigmoid_f32(v); }
 __device__ __forceinline__ float swish_gradf(float v) {
-    const float s = sigmoidf(v);
+    const float s = sigmoid_f32(v);
     return s + v * s * (1.0f - s);
 }
 
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(kT) void se_gate_fwd_kernel(const float* __restrict
     for (int c = threadIdx.x; c < C; c += kT) {
         float acc = b2[c];
         for (int j = 0; j < Cse; ++j) acc += w2[(size_t)c * Cse + j] * sh[j];
-        gate[(size_t)b * C + c] = sigmoidf(acc);
+        gate[(size_t)b * C + c] = sigmoid_f32(acc);
     }
 }
 // y[i] = x[i] * g[i / HW] (+ add[i / HW] with ADD: the backward's dx = dy*g + dpool/HW).  I: 32-bit indices while the

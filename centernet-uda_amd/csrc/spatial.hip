@@ -13,21 +13,46 @@ namespace {
 
 constexpr int kT = 256;
 
+// ---- the pieces the kernels below share --------------------------------------------
+// grid-stride walk of [first, total) along x, 64-bit
+#define FOR_EACH_INDEX_FROM(i, first, total)                                                        \
+    for (long long i = (first) + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (total); \
+         i += (long long)gridDim.x * blockDim.x)
+#define FOR_EACH_INDEX(i, total) FOR_EACH_INDEX_FROM(i, 0, total)
+// i = (plane * H + y) * W + x
+struct PlaneYX {
+    long long plane;
+    int y, x;
+};
+__device__ __forceinline__ PlaneYX plane_yx(long long i, int H, int W) {
+    return {i / ((long long)W * H), (int)((i / W) % H), (int)(i % W)};
+}
+// the max-pool rule of every scan below: first maximum wins, NaN propagates (ATen's rule)
+__device__ __forceinline__ bool pool_take(float v, float m) { return v > m || v != v; }
+// a channel's n weights into LDS
+__device__ __forceinline__ void stage_weights(float* ws, const float* __restrict__ w, int c, int n) {
+    for (int i = threadIdx.x; i < n; i += kT) ws[i] = w[(size_t)c * n + i];
+    __syncthreads();
+}
+
 // ---- max pool, window k x k, stride k, no padding ---------------------------------
+// the window at src (rows W apart), scanned (dy, dx) ascending -> the arg-max as dy * W + dx, its value in m
+__device__ __forceinline__ int pool_scan(const float* __restrict__ src, int W, int k, float& m) {
+    int arg = 0;
+    m = src[0];
+    for (int dy = 0; dy < k; ++dy)
+        for (int dx = 0; dx < k; ++dx) {
+            const float v = src[dy * W + dx];
+            if (pool_take(v, m)) { m = v; arg = dy * W + dx; }
+        }
+    return arg;
+}
 __global__ void maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long long planes, int H, int W,
                                    int Ho, int Wo, int k) {
-    const long long total = planes * Ho * Wo;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int ox = (int)(i % Wo), oy = (int)((i / Wo) % Ho);
-        const long long p = i / ((long long)Wo * Ho);
-        const float* src = x + (size_t)p * H * W + (size_t)(oy * k) * W + ox * k;
-        float m = src[0];
-        for (int dy = 0; dy < k; ++dy)
-            for (int dx = 0; dx < k; ++dx) {
-                const float v = src[dy * W + dx];
-                if (v > m || v != v) m = v;   // first maximum wins, NaN propagates (ATen's rule)
-            }
+    FOR_EACH_INDEX(i, planes * Ho * Wo) {
+        const PlaneYX o = plane_yx(i, Ho, Wo);
+        float m;
+        pool_scan(x + (size_t)o.plane * H * W + (size_t)(o.y * k) * W + o.x * k, W, k, m);
         y[i] = m;
     }
 }
@@ -35,19 +60,11 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ x, float* __restric
 // accumulate: gx already holds another consumer's share of x's gradient -- only the arg-max cell is touched (+= g)
 __global__ void maxpool_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gy, float* __restrict__ gx,
                                    long long planes, int H, int W, int Ho, int Wo, int k, int accumulate) {
-    const long long total = planes * Ho * Wo;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int ox = (int)(i % Wo), oy = (int)((i / Wo) % Ho);
-        const long long p = i / ((long long)Wo * Ho);
-        const size_t base = (size_t)p * H * W + (size_t)(oy * k) * W + ox * k;
-        float m = x[base];
-        int arg = 0;
-        for (int dy = 0; dy < k; ++dy)
-            for (int dx = 0; dx < k; ++dx) {
-                const float v = x[base + dy * W + dx];
-                if (v > m || v != v) { m = v; arg = dy * W + dx; }
-            }
+    FOR_EACH_INDEX(i, planes * Ho * Wo) {
+        const PlaneYX o = plane_yx(i, Ho, Wo);
+        const size_t base = (size_t)o.plane * H * W + (size_t)(o.y * k) * W + o.x * k;
+        float m;
+        const int arg = pool_scan(x + base, W, k, m);
         const float g = gy[i];
         if (accumulate) {
             gx[base + arg] += g;
@@ -63,16 +80,22 @@ __global__ void maxpool_bwd_kernel(const float* __restrict__ x, const float* __r
 // NaN rule as the scalar kernels: (0,0), (0,1), (1,0), (1,1), first maximum wins, NaN propagates.
 __device__ __forceinline__ void pool2_pick(float a, float b, float c, float d, float& m, int& arg) {
     m = a; arg = 0;
-    if (b > m || b != b) { m = b; arg = 1; }
-    if (c > m || c != c) { m = c; arg = 2; }
-    if (d > m || d != d) { m = d; arg = 3; }
+    if (pool_take(b, m)) { m = b; arg = 1; }
+    if (pool_take(c, m)) { m = c; arg = 2; }
+    if (pool_take(d, m)) { m = d; arg = 3; }
+}
+// window pair i of `total` -> its (plane, output row) flattened, the pair's place q in the row of Wq: input rows 2 row and
+// 2 row + 1.  32-bit division where the index allows (always, in DLA-34)
+__device__ __forceinline__ long long pool2_row(long long i, long long total, int Wq, int& q) {
+    const long long row = total < (1ll << 32) ? (long long)((unsigned)i / (unsigned)Wq) : i / Wq;
+    q = (int)(i - row * Wq);
+    return row;
 }
 __global__ void maxpool2_fwd_vec_kernel(const float4* __restrict__ x, float2* __restrict__ y, long long total /* planes * Ho * Wo / 2 */,
                                         int Wq /* W / 4 */) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        // (plane, output row) flattened: input rows 2 row, 2 row + 1.  32-bit division where the index allows (always, in DLA-34)
-        const long long row = total < (1ll << 32) ? (long long)((unsigned)i / (unsigned)Wq) : i / Wq;
-        const int q = (int)(i - row * Wq);
+    FOR_EACH_INDEX(i, total) {
+        int q;
+        const long long row = pool2_row(i, total, Wq, q);
         const float4 r0 = x[(2 * row) * Wq + q], r1 = x[(2 * row + 1) * Wq + q];
         float m0, m1;
         int a0, a1;
@@ -83,9 +106,9 @@ __global__ void maxpool2_fwd_vec_kernel(const float4* __restrict__ x, float2* __
 }
 __global__ void maxpool2_bwd_vec_kernel(const float4* __restrict__ x, const float2* __restrict__ gy, float4* __restrict__ gx,
                                         long long total, int Wq, int accumulate) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const long long row = total < (1ll << 32) ? (long long)((unsigned)i / (unsigned)Wq) : i / Wq;
-        const int q = (int)(i - row * Wq);
+    FOR_EACH_INDEX(i, total) {
+        int q;
+        const long long row = pool2_row(i, total, Wq, q);
         const long long i0 = (2 * row) * Wq + q, i1 = (2 * row + 1) * Wq + q;
         const float4 r0 = x[i0], r1 = x[i1];
         const float2 g = gy[i];
@@ -105,16 +128,14 @@ __global__ void maxpool2_bwd_vec_kernel(const float4* __restrict__ x, const floa
     }
 }
 inline bool pool2_vec_ok(const void* a, const void* b, const void* c, int H, int W, int k) {
-    return k == 2 && (W & 3) == 0 && (H & 1) == 0 && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
+    return k == 2 && (W & 3) == 0 && (H & 1) == 0 && aligned16(a, b, c);
 }
 
 // rows/cols of x not covered by any window (H % k != 0) get zero gradient
 __global__ void maxpool_bwd_tail_kernel(float* __restrict__ gx, long long planes, int H, int W, int Hc, int Wc) {
-    const long long total = planes * H * W;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int xx = (int)(i % W), yy = (int)((i / W) % H);
-        if (yy >= Hc || xx >= Wc) gx[i] = 0.0f;
+    FOR_EACH_INDEX(i, planes * H * W) {
+        const PlaneYX at = plane_yx(i, H, W);
+        if (at.y >= Hc || at.x >= Wc) gx[i] = 0.0f;
     }
 }
 
@@ -132,20 +153,17 @@ __device__ __forceinline__ int window_argmax(const float* __restrict__ src, int 
             const int ix = ox * s - p + dx;
             if (ix < 0 || ix >= W) continue;
             const float v = src[iy * W + ix];
-            if (arg < 0 || v > m || v != v) { m = v; arg = iy * W + ix; }
+            if (arg < 0 || pool_take(v, m)) { m = v; arg = iy * W + ix; }
         }
     }
     return arg;
 }
 __global__ void maxpool_win_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long long planes, int H,
                                        int W, int Ho, int Wo, int k, int s, int p) {
-    const long long total = planes * Ho * Wo;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int ox = (int)(i % Wo), oy = (int)((i / Wo) % Ho);
-        const long long pl = i / ((long long)Wo * Ho);
+    FOR_EACH_INDEX(i, planes * Ho * Wo) {
+        const PlaneYX o = plane_yx(i, Ho, Wo);
         float m;
-        window_argmax(x + (size_t)pl * H * W, H, W, oy, ox, k, s, p, m);
+        window_argmax(x + (size_t)o.plane * H * W, H, W, o.y, o.x, k, s, p, m);
         y[i] = m;
     }
 }
@@ -154,13 +172,11 @@ __global__ void maxpool_win_fwd_kernel(const float* __restrict__ x, float* __res
 __global__ void maxpool_win_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gy,
                                        float* __restrict__ gx, long long planes, int H, int W, int Ho, int Wo, int k,
                                        int s, int p) {
-    const long long total = planes * H * W;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int ix = (int)(i % W), iy = (int)((i / W) % H);
-        const long long pl = i / ((long long)W * H);
-        const float* src = x + (size_t)pl * H * W;
-        const float* g = gy + (size_t)pl * Ho * Wo;
+    FOR_EACH_INDEX(i, planes * H * W) {
+        const PlaneYX at = plane_yx(i, H, W);
+        const int iy = at.y, ix = at.x;
+        const float* src = x + (size_t)at.plane * H * W;
+        const float* g = gy + (size_t)at.plane * Ho * Wo;
         // windows with oy*s - p <= iy <= oy*s - p + k - 1
         int oy0 = (iy + p - k + s) / s, ox0 = (ix + p - k + s) / s;   // ceil((iy+p-k+1)/s) for non-negative numerators
         if (iy + p - k + 1 <= 0) oy0 = 0;
@@ -183,9 +199,8 @@ __global__ __launch_bounds__(kT) void dwconvt_fwd_kernel(const float* __restrict
                                                          const float* __restrict__ skip, float* __restrict__ y, int C,
                                                          int H, int W, int Ho, int Wo, int k, int s, int p) {
     __shared__ float ws[1024];
-    const int pl = blockIdx.y, c = pl % C;
-    for (int i = threadIdx.x; i < k * k; i += kT) ws[i] = w[(size_t)c * k * k + i];
-    __syncthreads();
+    const int pl = blockIdx.y;
+    stage_weights(ws, w, pl % C, k * k);
     const int o = blockIdx.x * kT + threadIdx.x;
     if (o >= Ho * Wo) return;
     const int oy = o / Wo, ox = o - oy * Wo;
@@ -215,9 +230,8 @@ __global__ __launch_bounds__(kT) void dwconvt_fwd_f_kernel(const float* __restri
                                                            int H, int W) {
     constexpr int K = 2 * F, P = F / 2;
     __shared__ float ws[K * K];
-    const int pl = blockIdx.y, c = pl % C;
-    for (int i = threadIdx.x; i < K * K; i += kT) ws[i] = w[(size_t)c * K * K + i];
-    __syncthreads();
+    const int pl = blockIdx.y;
+    stage_weights(ws, w, pl % C, K * K);
     const int Ho = H * F, Wo = W * F;                       // (H-1)*F - 2*(F/2) + 2F
     const int q = blockIdx.x * kT + threadIdx.x;           // quad of outputs in a band of ROWS rows
     const int qw = Wo >> 2;
@@ -264,9 +278,8 @@ __global__ __launch_bounds__(kT) void dwconvt_fwd_k4s2_kernel(const float* __res
                                                               const float* __restrict__ skip, float* __restrict__ y, int C,
                                                               int H, int W) {
     __shared__ float ws[16];
-    const int pl = blockIdx.y, c = pl % C;
-    if (threadIdx.x < 16) ws[threadIdx.x] = w[(size_t)c * 16 + threadIdx.x];
-    __syncthreads();
+    const int pl = blockIdx.y;
+    stage_weights(ws, w, pl % C, 16);
     const int Wo = 2 * W, qw = W >> 1;                     // blocks of 4 x 4 outputs: (H / 2) x (W / 2)
     const int q = blockIdx.x * kT + threadIdx.x;
     if (q >= qw * (H >> 1)) return;
@@ -314,6 +327,18 @@ __global__ __launch_bounds__(kT) void dwconvt_fwd_k4s2_kernel(const float* __res
 //   gw[c,ky,kx]    = sum_{b,iy,ix} x[b,c,iy,ix] * gy[b,c,iy*s-p+ky, ix*s-p+kx]
 // one workgroup per plane (c, b): gx written directly, K*K partial sums reduced in the block (fixed order)
 // into part[c][b][K*K]; dwconvt_wsum_kernel adds the B partials in order (reproducible, no atomics).
+// the block's K*K tap sums in a fixed order -- lanes, then (wave 0 + wave 1) + (wave 2 + wave 3) -- into part[K*K]
+template <int K>
+__device__ __forceinline__ void store_tap_partials(const float (&acc)[K * K], float (&red)[4][K * K], float* __restrict__ part) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int t = 0; t < K * K; ++t) {
+        const float v = wave_sum(acc[t]);
+        if (lane == 0) red[wid][t] = v;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < K * K; t += kT) part[t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+}
 template <int K>
 __global__ __launch_bounds__(kT) void dwconvt_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ gy, float* __restrict__ gx,
@@ -323,8 +348,7 @@ __global__ __launch_bounds__(kT) void dwconvt_bwd_kernel(const float* __restrict
     __shared__ float red[4][K * K];
     const int c = blockIdx.x, b = blockIdx.y;
     const size_t pl = (size_t)b * C + c;
-    for (int i = threadIdx.x; i < K * K; i += kT) ws[i] = w[(size_t)c * K * K + i];
-    __syncthreads();
+    stage_weights(ws, w, c, K * K);
     const float* xp = x + pl * H * W;
     const float* gp = gy + pl * Ho * Wo;
     float acc[K * K];
@@ -351,16 +375,7 @@ __global__ __launch_bounds__(kT) void dwconvt_bwd_kernel(const float* __restrict
         }
         if (gx) gx[pl * H * W + i] = g;
     }
-    if (!part) return;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t < K * K; ++t) {
-        const float v = wave_sum(acc[t]);
-        if (lane == 0) red[wid][t] = v;
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < K * K; t += kT)
-        part[((size_t)c * B + b) * K * K + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    if (part) store_tap_partials<K>(acc, red, part + ((size_t)c * B + b) * K * K);
 }
 // The same for IDAUp's commonest layer (k = 4, stride 2, padding 1; W even): a thread takes TWO neighbouring input pixels
 // (ix even).  Their windows are the six output columns 2 ix - 1 .. 2 ix + 4 of four output rows: per row one aligned
@@ -374,8 +389,7 @@ __global__ __launch_bounds__(kT) void dwconvt_bwd_k4s2_kernel(const float* __res
     __shared__ float red[4][K * K];
     const int c = blockIdx.x, b = blockIdx.y;
     const size_t pl = (size_t)b * C + c;
-    for (int i = threadIdx.x; i < K * K; i += kT) ws[i] = w[(size_t)c * K * K + i];
-    __syncthreads();
+    stage_weights(ws, w, c, K * K);
     const int Ho = 2 * H, Wo = 2 * W, W2 = W >> 1;
     const float* xp = x + pl * H * W;
     const float* gp = gy + pl * Ho * Wo;
@@ -409,16 +423,7 @@ __global__ __launch_bounds__(kT) void dwconvt_bwd_k4s2_kernel(const float* __res
         }
         if (gx) *reinterpret_cast<float2*>(gx + pl * H * W + iy * W + ix) = make_float2(g0, g1);
     }
-    if (!part) return;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int t = 0; t < K * K; ++t) {
-        const float v = wave_sum(acc[t]);
-        if (lane == 0) red[wid][t] = v;
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < K * K; t += kT)
-        part[((size_t)c * B + b) * K * K + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    if (part) store_tap_partials<K>(acc, red, part + ((size_t)c * B + b) * K * K);
 }
 // gw[c,tap] = sum_b part[(c*B + b)*T + tap], the images in increasing order: the second step of every depthwise weight
 // gradient (transposed and plain)
@@ -434,13 +439,10 @@ __global__ void dwconvt_wsum_kernel(const float* __restrict__ part, float* __res
 __global__ void dwconvt_bwd_data_kernel(const float* __restrict__ gy, const float* __restrict__ w,
                                         float* __restrict__ gx, int B, int C, int H, int W, int Ho, int Wo, int k,
                                         int s, int p) {
-    const long long total = (long long)B * C * H * W;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int ix = (int)(i % W), iy = (int)((i / W) % H);
-        const long long pl = i / ((long long)W * H);
-        const int c = (int)(pl % C);
-        const float* gp = gy + (size_t)pl * Ho * Wo;
+    FOR_EACH_INDEX(i, (long long)B * C * H * W) {
+        const PlaneYX at = plane_yx(i, H, W);
+        const int iy = at.y, ix = at.x, c = (int)(at.plane % C);
+        const float* gp = gy + (size_t)at.plane * Ho * Wo;
         const float* wp = w + (size_t)c * k * k;
         float acc = 0.0f;
         for (int ky = 0; ky < k; ++ky) {
@@ -477,27 +479,29 @@ __global__ __launch_bounds__(kT) void dwconvt_bwd_weight_kernel(const float* __r
 }
 
 // ---- elementwise ------------------------------------------------------------
+// gradient through ReLU (slope 0) / LeakyReLU: g * (y > 0 ? 1 : slope)
+__device__ __forceinline__ float act_gate(float g, float y, float slope) { return y > 0.0f ? g : g * slope; }
+struct Identity {
+    __device__ float operator()(float v) const { return v; }
+};
+// n4 quads of 16 bytes, then the scalar rest (the host passes n4 == 0 for operands off 16-byte alignment)
 // (no __restrict__: out may be a or b -- hip_runtime.fork sums gradients in place)
 __global__ void add_kernel(const float* a, const float* b, float* out, long long n4, long long n) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    FOR_EACH_INDEX(i, n4) {
         const float4 u = reinterpret_cast<const float4*>(a)[i], v = reinterpret_cast<const float4*>(b)[i];
         reinterpret_cast<float4*>(out)[i] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
     }
-    for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x)
-        out[i] = a[i] + b[i];
+    FOR_EACH_INDEX_FROM(i, n4 * 4, n) out[i] = a[i] + b[i];
 }
 // gx = gy * (y > 0 ? 1 : slope)      (ReLU: slope 0; LeakyReLU(0.2): slope 0.2)
 __global__ void act_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ y, float* __restrict__ gx,
                                long long n4, long long n, float slope) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    FOR_EACH_INDEX(i, n4) {
         const float4 g = reinterpret_cast<const float4*>(gy)[i], v = reinterpret_cast<const float4*>(y)[i];
-        reinterpret_cast<float4*>(gx)[i] = make_float4(v.x > 0.0f ? g.x : g.x * slope, v.y > 0.0f ? g.y : g.y * slope,
-                                                       v.z > 0.0f ? g.z : g.z * slope, v.w > 0.0f ? g.w : g.w * slope);
+        reinterpret_cast<float4*>(gx)[i] = make_float4(act_gate(g.x, v.x, slope), act_gate(g.y, v.y, slope),
+                                                       act_gate(g.z, v.z, slope), act_gate(g.w, v.w, slope));
     }
-    for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x)
-        gx[i] = y[i] > 0.0f ? gy[i] : gy[i] * slope;
+    FOR_EACH_INDEX_FROM(i, n4 * 4, n) gx[i] = act_gate(gy[i], y[i], slope);
 }
 // The input gradient of a 1x1 convolution with a handful of output channels (a detection head's last layer,
 // dla.py:474-483: 256 -> classes / 2 / 2) fused with the backward of the activation in front of it:
@@ -524,78 +528,57 @@ __global__ __launch_bounds__(kT) void conv1x1_dgrad_act_kernel(const float* __re
             const float wc = w[(size_t)c * Ch + m];
             o.x += wc * g[c].x; o.y += wc * g[c].y; o.z += wc * g[c].z; o.w += wc * g[c].w;
         }
-        *reinterpret_cast<float4*>(gh + at) = make_float4(h.x > 0.0f ? o.x : o.x * slope, h.y > 0.0f ? o.y : o.y * slope,
-                                                          h.z > 0.0f ? o.z : o.z * slope, h.w > 0.0f ? o.w : o.w * slope);
+        *reinterpret_cast<float4*>(gh + at) = make_float4(act_gate(o.x, h.x, slope), act_gate(o.y, h.y, slope),
+                                                          act_gate(o.z, h.z, slope), act_gate(o.w, h.w, slope));
     }
 }
 // Row-wise kernels: grid (chunks of a row, rows); a row is one (image, channel) plane of HW floats, so the
 // channel bookkeeping is per workgroup and the inner loop is 16-byte copies when `vec`: HW % 4 == 0 and every tensor
 // 16-byte aligned (rows_vec_ok, decided by the host); else 4-byte copies of the same values.
+// d[i] = f(in[i]...) over the row, grid-stride: float4 with f on each of .x .y .z .w when `vec`, else float
+template <typename F, typename... In>
+__device__ __forceinline__ void map_row(int vec, long long HW, float* d, F f, In... in) {
+    if (vec) {
+        FOR_EACH_INDEX(i, HW >> 2) {
+            const auto at = [i](const float* p) { return reinterpret_cast<const float4*>(p)[i]; };
+            reinterpret_cast<float4*>(d)[i] = make_float4(f(at(in).x...), f(at(in).y...), f(at(in).z...), f(at(in).w...));
+        }
+    } else {
+        FOR_EACH_INDEX(i, HW) d[i] = f(in[i]...);
+    }
+}
 // copy a [B, Cn, HW] block between tensors with Csrc / Cdst channels at channel offsets
 __global__ void copy_channels_kernel(const float* __restrict__ src, float* __restrict__ dst, int rows, int Cn,
                                      long long HW, int Csrc, int src_off, int Cdst, int dst_off, int vec) {
     for (int row = blockIdx.y; row < rows; row += gridDim.y) {
         const int b = row / Cn, c = row - b * Cn;
-        const float* s = src + ((size_t)b * Csrc + src_off + c) * HW;
-        float* d = dst + ((size_t)b * Cdst + dst_off + c) * HW;
-        if (vec) {
-            for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (HW >> 2); i += (long long)gridDim.x * blockDim.x)
-                reinterpret_cast<float4*>(d)[i] = reinterpret_cast<const float4*>(s)[i];
-        } else {
-            for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += (long long)gridDim.x * blockDim.x)
-                d[i] = s[i];
-        }
+        map_row(vec, HW, dst + ((size_t)b * Cdst + dst_off + c) * HW, Identity(), src + ((size_t)b * Csrc + src_off + c) * HW);
     }
 }
 // om [B, 3T, HW] -> offset [B, 2T, HW] (channels 0..2T-1 unchanged) and mask = sigmoid(channels 2T..3T-1)
 __global__ void split_offset_mask_kernel(const float* __restrict__ om, float* __restrict__ offset,
                                          float* __restrict__ mask, int rows, int T, long long HW, int vec) {
-  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
-    const int b = row / (3 * T), c = row - b * 3 * T;
-    const float* s = om + (size_t)row * HW;
-    const bool is_mask = c >= 2 * T;
-    float* d = is_mask ? mask + ((size_t)b * T + (c - 2 * T)) * HW : offset + ((size_t)b * 2 * T + c) * HW;
-    if (vec) {
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (HW >> 2); i += (long long)gridDim.x * blockDim.x) {
-            float4 v = reinterpret_cast<const float4*>(s)[i];
-            if (is_mask) {
-                v.x = 1.0f / (1.0f + expf(-v.x)); v.y = 1.0f / (1.0f + expf(-v.y));
-                v.z = 1.0f / (1.0f + expf(-v.z)); v.w = 1.0f / (1.0f + expf(-v.w));
-            }
-            reinterpret_cast<float4*>(d)[i] = v;
-        }
-    } else {
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += (long long)gridDim.x * blockDim.x)
-            d[i] = is_mask ? 1.0f / (1.0f + expf(-s[i])) : s[i];
+    for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+        const int b = row / (3 * T), c = row - b * 3 * T;
+        const float* s = om + (size_t)row * HW;
+        if (c >= 2 * T) map_row(vec, HW, mask + ((size_t)b * T + (c - 2 * T)) * HW, [](float v) { return sigmoid_f32(v); }, s);
+        else map_row(vec, HW, offset + ((size_t)b * 2 * T + c) * HW, Identity(), s);
     }
-  }
 }
 __global__ void split_offset_mask_bwd_kernel(const float* __restrict__ goff, const float* __restrict__ gmask,
                                              const float* __restrict__ mask, float* __restrict__ gom, int rows,
                                              int T, long long HW, int vec) {
-  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
-    const int b = row / (3 * T), c = row - b * 3 * T;
-    float* d = gom + (size_t)row * HW;
-    const bool is_mask = c >= 2 * T;
-    const float* g = is_mask ? gmask + ((size_t)b * T + (c - 2 * T)) * HW : goff + ((size_t)b * 2 * T + c) * HW;
-    const float* m = mask + ((size_t)b * T + (is_mask ? c - 2 * T : 0)) * HW;
-    if (vec) {
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (HW >> 2); i += (long long)gridDim.x * blockDim.x) {
-            float4 v = reinterpret_cast<const float4*>(g)[i];
-            if (is_mask) {
-                const float4 mm = reinterpret_cast<const float4*>(m)[i];
-                v.x = v.x * mm.x * (1.0f - mm.x); v.y = v.y * mm.y * (1.0f - mm.y);
-                v.z = v.z * mm.z * (1.0f - mm.z); v.w = v.w * mm.w * (1.0f - mm.w);
-            }
-            reinterpret_cast<float4*>(d)[i] = v;
+    for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+        const int b = row / (3 * T), c = row - b * 3 * T;
+        float* d = gom + (size_t)row * HW;
+        if (c >= 2 * T) {
+            const size_t at = ((size_t)b * T + (c - 2 * T)) * HW;          // the row's place in mask and gmask
+            map_row(vec, HW, d, [](float g, float m) { return g * m * (1.0f - m); }, gmask + at, mask + at);
+        } else {
+            map_row(vec, HW, d, Identity(), goff + ((size_t)b * 2 * T + c) * HW);
         }
-    } else {
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += (long long)gridDim.x * blockDim.x)
-            d[i] = is_mask ? g[i] * m[i] * (1.0f - m[i]) : g[i];
     }
-  }
 }
-
 
 // ---------------- depthwise convolution (groups == channels), top / left padding given ----------------
 // torchvision MobileNetV2's `ConvBNReLU(hidden, hidden, stride, groups=hidden)` (pt = pl = p) and EfficientNet's MBConv
@@ -757,6 +740,13 @@ __global__ __launch_bounds__(kT) void dwconv_bwd_weight_kernel(const float* __re
 
 using namespace cnuda;
 
+// output sizes: a (max-pool or convolution) window by torch's floor rule, and the transposed convolution
+static int pool_out(int H, int k, int s, int p) { return (H + 2 * p - k) / s + 1; }
+static int convt_out(int H, int k, int s, int p) { return (H - 1) * s - 2 * p + k; }
+// a grid-stride kernel (FOR_EACH_INDEX) over `items`
+#define CNUDA_LAUNCH_1D(kernel, items, stream, ...) \
+    CNUDA_LAUNCH(kernel, dim3(stream_grid(items, kT)), dim3(kT), 0, (hipStream_t)(stream), __VA_ARGS__)
+
 extern "C" int cnuda_maxpool2d_forward(const float* x, float* y, int B, int C, int H, int W, int k,
                                        cnuda_stream_t stream) {
     CNUDA_REQUIRE(x && y && B > 0 && C > 0 && k > 0 && H >= k && W >= k, "cnuda_maxpool2d_forward: bad arguments");
@@ -764,12 +754,11 @@ extern "C" int cnuda_maxpool2d_forward(const float* x, float* y, int B, int C, i
     const long long planes = (long long)B * C;
     if (pool2_vec_ok(x, y, nullptr, H, W, k)) {
         const long long total = planes * Ho * (Wo / 2);
-        CNUDA_LAUNCH(maxpool2_fwd_vec_kernel, dim3(stream_grid(total, kT)), dim3(kT), 0, (hipStream_t)stream,
-                     reinterpret_cast<const float4*>(x), reinterpret_cast<float2*>(y), total, W / 4);
+        CNUDA_LAUNCH_1D(maxpool2_fwd_vec_kernel, total, stream, reinterpret_cast<const float4*>(x), reinterpret_cast<float2*>(y),
+                        total, W / 4);
         return check_launch("cnuda_maxpool2d_forward");
     }
-    CNUDA_LAUNCH(maxpool_fwd_kernel, dim3(stream_grid(planes * Ho * Wo, kT)), dim3(kT), 0, (hipStream_t)stream, x,
-                       y, planes, H, W, Ho, Wo, k);
+    CNUDA_LAUNCH_1D(maxpool_fwd_kernel, planes * Ho * Wo, stream, x, y, planes, H, W, Ho, Wo, k);
     return check_launch("cnuda_maxpool2d_forward");
 }
 extern "C" int cnuda_maxpool2d_backward(const float* x, const float* grad_y, float* grad_x, int B, int C, int H, int W,
@@ -782,18 +771,15 @@ extern "C" int cnuda_maxpool2d_backward_acc(const float* x, const float* grad_y,
                   "cnuda_maxpool2d_backward: bad arguments");
     const int Ho = H / k, Wo = W / k;
     const long long planes = (long long)B * C;
-    hipStream_t st = (hipStream_t)stream;
     if (pool2_vec_ok(x, grad_y, grad_x, H, W, k)) {
         const long long total = planes * Ho * (Wo / 2);
-        CNUDA_LAUNCH(maxpool2_bwd_vec_kernel, dim3(stream_grid(total, kT)), dim3(kT), 0, st, reinterpret_cast<const float4*>(x),
-                     reinterpret_cast<const float2*>(grad_y), reinterpret_cast<float4*>(grad_x), total, W / 4, accumulate);
+        CNUDA_LAUNCH_1D(maxpool2_bwd_vec_kernel, total, stream, reinterpret_cast<const float4*>(x),
+                        reinterpret_cast<const float2*>(grad_y), reinterpret_cast<float4*>(grad_x), total, W / 4, accumulate);
         return check_launch("cnuda_maxpool2d_backward");
     }
     if (!accumulate && (Ho * k != H || Wo * k != W))
-        CNUDA_LAUNCH(maxpool_bwd_tail_kernel, dim3(stream_grid(planes * H * W, kT)), dim3(kT), 0, st, grad_x,
-                           planes, H, W, Ho * k, Wo * k);
-    CNUDA_LAUNCH(maxpool_bwd_kernel, dim3(stream_grid(planes * Ho * Wo, kT)), dim3(kT), 0, st, x, grad_y, grad_x,
-                       planes, H, W, Ho, Wo, k, accumulate);
+        CNUDA_LAUNCH_1D(maxpool_bwd_tail_kernel, planes * H * W, stream, grad_x, planes, H, W, Ho * k, Wo * k);
+    CNUDA_LAUNCH_1D(maxpool_bwd_kernel, planes * Ho * Wo, stream, x, grad_y, grad_x, planes, H, W, Ho, Wo, k, accumulate);
     return check_launch("cnuda_maxpool2d_backward");
 }
 
@@ -801,10 +787,9 @@ extern "C" int cnuda_maxpool2d_window_forward(const float* x, float* y, int B, i
                                               cnuda_stream_t stream) {
     CNUDA_REQUIRE(x && y && B > 0 && C > 0 && k > 0 && s > 0 && p >= 0 && 2 * p <= k && H + 2 * p >= k && W + 2 * p >= k,
                   "cnuda_maxpool2d_window_forward: bad arguments (need 2*padding <= kernel <= padded size)");
-    const int Ho = (H + 2 * p - k) / s + 1, Wo = (W + 2 * p - k) / s + 1;
+    const int Ho = pool_out(H, k, s, p), Wo = pool_out(W, k, s, p);
     const long long planes = (long long)B * C;
-    CNUDA_LAUNCH(maxpool_win_fwd_kernel, dim3(stream_grid(planes * Ho * Wo, kT)), dim3(kT), 0,
-                       (hipStream_t)stream, x, y, planes, H, W, Ho, Wo, k, s, p);
+    CNUDA_LAUNCH_1D(maxpool_win_fwd_kernel, planes * Ho * Wo, stream, x, y, planes, H, W, Ho, Wo, k, s, p);
     return check_launch("cnuda_maxpool2d_window_forward");
 }
 extern "C" int cnuda_maxpool2d_window_backward(const float* x, const float* grad_y, float* grad_x, int B, int C, int H,
@@ -812,10 +797,9 @@ extern "C" int cnuda_maxpool2d_window_backward(const float* x, const float* grad
     CNUDA_REQUIRE(x && grad_y && grad_x && B > 0 && C > 0 && k > 0 && s > 0 && p >= 0 && 2 * p <= k && H + 2 * p >= k &&
                       W + 2 * p >= k,
                   "cnuda_maxpool2d_window_backward: bad arguments");
-    const int Ho = (H + 2 * p - k) / s + 1, Wo = (W + 2 * p - k) / s + 1;
+    const int Ho = pool_out(H, k, s, p), Wo = pool_out(W, k, s, p);
     const long long planes = (long long)B * C;
-    CNUDA_LAUNCH(maxpool_win_bwd_kernel, dim3(stream_grid(planes * H * W, kT)), dim3(kT), 0, (hipStream_t)stream,
-                       x, grad_y, grad_x, planes, H, W, Ho, Wo, k, s, p);
+    CNUDA_LAUNCH_1D(maxpool_win_bwd_kernel, planes * H * W, stream, x, grad_y, grad_x, planes, H, W, Ho, Wo, k, s, p);
     return check_launch("cnuda_maxpool2d_window_backward");
 }
 
@@ -823,27 +807,25 @@ extern "C" int cnuda_dwconvt2d_add_forward(const float* x, const float* w, const
                                            int H, int W, int k, int s, int p, cnuda_stream_t stream) {
     CNUDA_REQUIRE(x && w && y && B > 0 && C > 0 && H > 0 && W > 0 && k > 0 && k <= 32 && s > 0 && p >= 0,
                   "cnuda_dwconvt2d_forward: bad arguments (kernel size 1..32)");
-    const int Ho = (H - 1) * s - 2 * p + k, Wo = (W - 1) * s - 2 * p + k;
+    const int Ho = convt_out(H, k, s, p), Wo = convt_out(W, k, s, p);
     CNUDA_REQUIRE(Ho > 0 && Wo > 0, "cnuda_dwconvt2d_forward: empty output");
     CNUDA_REQUIRE((long long)B * C <= 65535, "cnuda_dwconvt2d_forward: more than 65535 planes");
     // the vector kernels read `skip` and write `y` 16 bytes at a time (and read x 8 bytes at a time): a view at an
     // odd offset takes the scalar kernel
-    const bool aligned16 = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)skip) & 15) == 0;
-    const bool upsample = k == 2 * s && p == s / 2 && (s == 2 || s == 4) && Wo % 4 == 0 && aligned16;   // IDAUp's bilinear-style layers
+    const bool upsample = k == 2 * s && p == s / 2 && (s == 2 || s == 4) && Wo % 4 == 0 && aligned16(x, y, skip);   // IDAUp's bilinear-style layers
     const int rows = (upsample && Ho % 4 == 0 && (long long)Ho * Wo >= 4096) ? 4 : 1;
     const dim3 fgrid(ceil_div((long long)Ho * Wo / 4 / rows, kT), B * C);
+    hipStream_t st = (hipStream_t)stream;
     if (upsample && s == 2 && rows == 4 && (H & 1) == 0 && (W & 1) == 0)
-        CNUDA_LAUNCH(dwconvt_fwd_k4s2_kernel, dim3(ceil_div((long long)(H / 2) * (W / 2), kT), B * C), dim3(kT), 0,
-                           (hipStream_t)stream, x, w, skip, y, C, H, W);
+        CNUDA_LAUNCH(dwconvt_fwd_k4s2_kernel, dim3(ceil_div((long long)(H / 2) * (W / 2), kT), B * C), dim3(kT), 0, st, x, w, skip, y, C, H, W);
     else if (upsample && s == 2)         // (rows == 4 means H and W even here: the branch above has taken it)
-        CNUDA_LAUNCH((dwconvt_fwd_f_kernel<2, 1>), fgrid, dim3(kT), 0, (hipStream_t)stream, x, w, skip, y, C, H, W);
+        CNUDA_LAUNCH((dwconvt_fwd_f_kernel<2, 1>), fgrid, dim3(kT), 0, st, x, w, skip, y, C, H, W);
     else if (upsample && rows == 4)
-        CNUDA_LAUNCH((dwconvt_fwd_f_kernel<4, 4>), fgrid, dim3(kT), 0, (hipStream_t)stream, x, w, skip, y, C, H, W);
+        CNUDA_LAUNCH((dwconvt_fwd_f_kernel<4, 4>), fgrid, dim3(kT), 0, st, x, w, skip, y, C, H, W);
     else if (upsample)
-        CNUDA_LAUNCH((dwconvt_fwd_f_kernel<4, 1>), fgrid, dim3(kT), 0, (hipStream_t)stream, x, w, skip, y, C, H, W);
+        CNUDA_LAUNCH((dwconvt_fwd_f_kernel<4, 1>), fgrid, dim3(kT), 0, st, x, w, skip, y, C, H, W);
     else
-        CNUDA_LAUNCH(dwconvt_fwd_kernel, dim3(ceil_div((long long)Ho * Wo, kT), B * C), dim3(kT), 0,
-                           (hipStream_t)stream, x, w, skip, y, C, H, W, Ho, Wo, k, s, p);
+        CNUDA_LAUNCH(dwconvt_fwd_kernel, dim3(ceil_div((long long)Ho * Wo, kT), B * C), dim3(kT), 0, st, x, w, skip, y, C, H, W, Ho, Wo, k, s, p);
     return check_launch("cnuda_dwconvt2d_forward");
 }
 extern "C" int cnuda_dwconvt2d_forward(const float* x, const float* w, float* y, int B, int C, int H, int W, int k,
@@ -865,30 +847,44 @@ static dim3 dwconv_grid(int planes, long long items) {
     const int g = ceil_div(items, kT);
     return dim3(planes, g < 64 ? g : 64);
 }
+// the kernels' index math is 32-bit
+static int dwconv_sizes_ok(const char* who, int B, int C, int H, int W, int Ho, int Wo) {
+    CNUDA_REQUIRE((long long)B * C <= 2147483647LL && (long long)H * W <= 2147483647LL && (long long)Ho * Wo <= 2147483647LL,
+                  "%s: tensor too large", who);
+    return 0;
+}
+// f(K) with the kernel size, 3 or 5 (the entries have checked it), as a compile-time constant: K.value
+template <typename F>
+static void dispatch_k35(int k, F f) {
+    if (k == 3) f(std::integral_constant<int, 3>());
+    else f(std::integral_constant<int, 5>());
+}
+// step 2 of every depthwise weight gradient: gw = the B partials of `part` added in order
+static void launch_wsum(const float* part, float* gw, int B, int C, int k, hipStream_t st) {
+    CNUDA_LAUNCH(dwconvt_wsum_kernel, dim3(ceil_div((long long)C * k * k, 256)), dim3(256), 0, st, part, gw, B, C, k * k);
+}
 // The launch bodies.  The entry (`who` in messages) has checked its own contract, which is at least: B, C, H, W, Ho,
 // Wo > 0, k 3 or 5, s >= 1, pt, pl >= 0.  Whatever the 16-byte forms do not take goes to the scalar kernels, which are
 // right for every such geometry and accumulate in the same order.
 static int dwconv_forward(const char* who, const float* x, const float* w, float* y, int B, int C, int H, int W, int k,
                           int s, int pt, int pl, int Ho, int Wo, hipStream_t st) {
     CNUDA_REQUIRE(x && w && y, "%s: null pointer", who);
-    CNUDA_REQUIRE((long long)B * C <= 2147483647LL && (long long)H * W <= 2147483647LL && (long long)Ho * Wo <= 2147483647LL,
-                  "%s: tensor too large", who);
+    if (int rc = dwconv_sizes_ok(who, B, C, H, W, Ho, Wo)) return rc;
     // the quad's window, columns S*ox - PL .. S*(ox+3) - PL + k - 1, lies inside [S*ox - 4, S*ox + 4*NV) for S <= 2, PL <= 2, k <= 5
-    const bool vec = (W % 4 == 0) && (Wo % 4 == 0) && pl <= 2 && s <= 2 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+    const bool vec = (W % 4 == 0) && (Wo % 4 == 0) && pl <= 2 && s <= 2 && aligned16(x, y);
     if (vec) {
         const dim3 grid = dwconv_grid(B * C, (long long)Ho * (Wo / 4));
 #define CNUDA_DWV(K, S, PL) CNUDA_LAUNCH((dwconv_fwd_vec_kernel<K, S, PL>), grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, pt)
 #define CNUDA_DWP(K, S) do { if (pl == 0) CNUDA_DWV(K, S, 0); else if (pl == 1) CNUDA_DWV(K, S, 1); else CNUDA_DWV(K, S, 2); } while (0)
-        if (k == 3 && s == 1) CNUDA_DWP(3, 1);
-        else if (k == 3) CNUDA_DWP(3, 2);      // (no geometry reaches <3, 2, 2>: W % 4 == 0 and left padding 2 make Wo odd)
-        else if (s == 1) CNUDA_DWP(5, 1);
-        else CNUDA_DWP(5, 2);
+        dispatch_k35(k, [&](auto K) {           // (no geometry reaches <3, 2, 2>: W % 4 == 0 and left padding 2 make Wo odd)
+            if (s == 1) CNUDA_DWP(K.value, 1);
+            else CNUDA_DWP(K.value, 2);
+        });
 #undef CNUDA_DWP
 #undef CNUDA_DWV
     } else {
         const dim3 grid = dwconv_grid(B * C, (long long)Ho * Wo);
-        if (k == 3) CNUDA_LAUNCH(dwconv_fwd_kernel<3>, grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, s, pt, pl);
-        else CNUDA_LAUNCH(dwconv_fwd_kernel<5>, grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, s, pt, pl);
+        dispatch_k35(k, [&](auto K) { CNUDA_LAUNCH(dwconv_fwd_kernel<K.value>, grid, dim3(kT), 0, st, x, w, y, C, H, W, Ho, Wo, s, pt, pl); });
     }
     return check_launch(who);
 }
@@ -896,26 +892,23 @@ static int dwconv_backward(const char* who, const float* x, const float* w, cons
                            float* grad_w, int B, int C, int H, int W, int k, int s, int pt, int pl, int Ho, int Wo,
                            void* workspace, size_t workspace_bytes, hipStream_t st) {
     CNUDA_REQUIRE(x && w && grad_y, "%s: null pointer", who);
-    CNUDA_REQUIRE((long long)B * C <= 2147483647LL && (long long)H * W <= 2147483647LL && (long long)Ho * Wo <= 2147483647LL,
-                  "%s: tensor too large", who);
+    if (int rc = dwconv_sizes_ok(who, B, C, H, W, Ho, Wo)) return rc;
     if (grad_x) {
-        if (W % 4 == 0 && ((uintptr_t)grad_x & 15) == 0) {
-            const dim3 grid = dwconv_grid(B * C, (long long)H * (W / 4));
-            if (k == 3) CNUDA_LAUNCH((dwconv_bwd_data_kernel<3, 4>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pt, pl);
-            else CNUDA_LAUNCH((dwconv_bwd_data_kernel<5, 4>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pt, pl);
-        } else {
-            const dim3 grid = dwconv_grid(B * C, (long long)H * W);
-            if (k == 3) CNUDA_LAUNCH((dwconv_bwd_data_kernel<3, 1>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pt, pl);
-            else CNUDA_LAUNCH((dwconv_bwd_data_kernel<5, 1>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pt, pl);
-        }
+        const bool vec = W % 4 == 0 && aligned16(grad_x);
+        const dim3 grid = dwconv_grid(B * C, (long long)H * (vec ? W / 4 : W));
+        dispatch_k35(k, [&](auto K) {
+            if (vec) CNUDA_LAUNCH((dwconv_bwd_data_kernel<K.value, 4>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pt, pl);
+            else CNUDA_LAUNCH((dwconv_bwd_data_kernel<K.value, 1>), grid, dim3(kT), 0, st, grad_y, w, grad_x, C, H, W, Ho, Wo, s, pt, pl);
+        });
     }
     if (grad_w) {
         CNUDA_REQUIRE(workspace && workspace_bytes >= dw_workspace_bytes(B, C, k), "%s: workspace too small", who);
         CNUDA_REQUIRE(B <= 65535, "%s: batch > 65535", who);
         float* part = reinterpret_cast<float*>(workspace);
-        if (k == 3) CNUDA_LAUNCH(dwconv_bwd_weight_kernel<3>, dim3(C, B), dim3(kT), 0, st, x, grad_y, part, B, C, H, W, Ho, Wo, s, pt, pl);
-        else CNUDA_LAUNCH(dwconv_bwd_weight_kernel<5>, dim3(C, B), dim3(kT), 0, st, x, grad_y, part, B, C, H, W, Ho, Wo, s, pt, pl);
-        CNUDA_LAUNCH(dwconvt_wsum_kernel, dim3(ceil_div((long long)C * k * k, 256)), dim3(256), 0, st, part, grad_w, B, C, k * k);
+        dispatch_k35(k, [&](auto K) {
+            CNUDA_LAUNCH(dwconv_bwd_weight_kernel<K.value>, dim3(C, B), dim3(kT), 0, st, x, grad_y, part, B, C, H, W, Ho, Wo, s, pt, pl);
+        });
+        launch_wsum(part, grad_w, B, C, k, st);
     }
     return check_launch(who);
 }
@@ -925,8 +918,8 @@ static int dwconv_geom(int B, int C, int H, int W, int k, int s, int p, int& Ho,
     CNUDA_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && s > 0 && p >= 0, "%s: bad arguments", who);
     CNUDA_REQUIRE(k == 3 || k == 5, "%s: kernel size %d (3 and 5 are built)", who, k);
     CNUDA_REQUIRE(H + 2 * p >= k && W + 2 * p >= k, "%s: empty output", who);
-    Ho = (H + 2 * p - k) / s + 1;
-    Wo = (W + 2 * p - k) / s + 1;
+    Ho = pool_out(H, k, s, p);
+    Wo = pool_out(W, k, s, p);
     return 0;
 }
 extern "C" int cnuda_dwconv2d_forward(const float* x, const float* w, float* y, int B, int C, int H, int W, int k,
@@ -972,7 +965,7 @@ extern "C" int cnuda_dwconvt2d_backward(const float* x, const float* w, const fl
                                         void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
     CNUDA_REQUIRE(x && w && grad_y && B > 0 && C > 0 && H > 0 && W > 0 && k > 0 && s > 0 && p >= 0,
                   "cnuda_dwconvt2d_backward: bad arguments");
-    const int Ho = (H - 1) * s - 2 * p + k, Wo = (W - 1) * s - 2 * p + k;
+    const int Ho = convt_out(H, k, s, p), Wo = convt_out(W, k, s, p);
     hipStream_t st = (hipStream_t)stream;
     if ((k == 4 || k == 8) && C <= 65535 && B <= 65535) {
         float* part = nullptr;
@@ -981,23 +974,17 @@ extern "C" int cnuda_dwconvt2d_backward(const float* x, const float* w, const fl
                           "cnuda_dwconvt2d_backward: workspace too small");
             part = (float*)workspace;
         }
-        if (k == 4 && s == 2 && p == 1 && (W & 1) == 0 &&
-            (((uintptr_t)x | (uintptr_t)grad_y | (uintptr_t)grad_x) & 15) == 0)
+        if (k == 4 && s == 2 && p == 1 && (W & 1) == 0 && aligned16(x, grad_y, grad_x))
             CNUDA_LAUNCH(dwconvt_bwd_k4s2_kernel, dim3(C, B), dim3(kT), 0, st, x, w, grad_y, grad_x, part, B, C, H, W);
         else if (k == 4)
-            CNUDA_LAUNCH(dwconvt_bwd_kernel<4>, dim3(C, B), dim3(kT), 0, st, x, w, grad_y, grad_x, part, B, C, H, W,
-                               Ho, Wo, s, p);
+            CNUDA_LAUNCH(dwconvt_bwd_kernel<4>, dim3(C, B), dim3(kT), 0, st, x, w, grad_y, grad_x, part, B, C, H, W, Ho, Wo, s, p);
         else
-            CNUDA_LAUNCH(dwconvt_bwd_kernel<8>, dim3(C, B), dim3(kT), 0, st, x, w, grad_y, grad_x, part, B, C, H, W,
-                               Ho, Wo, s, p);
-        if (grad_w)
-            CNUDA_LAUNCH(dwconvt_wsum_kernel, dim3(ceil_div((long long)C * k * k, 256)), dim3(256), 0, st, part,
-                               grad_w, B, C, k * k);
+            CNUDA_LAUNCH(dwconvt_bwd_kernel<8>, dim3(C, B), dim3(kT), 0, st, x, w, grad_y, grad_x, part, B, C, H, W, Ho, Wo, s, p);
+        if (grad_w) launch_wsum(part, grad_w, B, C, k, st);
         return check_launch("cnuda_dwconvt2d_backward");
     }
     if (grad_x)
-        CNUDA_LAUNCH(dwconvt_bwd_data_kernel, dim3(stream_grid((long long)B * C * H * W, kT)), dim3(kT), 0, st,
-                           grad_y, w, grad_x, B, C, H, W, Ho, Wo, k, s, p);
+        CNUDA_LAUNCH_1D(dwconvt_bwd_data_kernel, (long long)B * C * H * W, st, grad_y, w, grad_x, B, C, H, W, Ho, Wo, k, s, p);
     if (grad_w)
         CNUDA_LAUNCH(dwconvt_bwd_weight_kernel, dim3(C, k * k), dim3(kT), 0, st, x, grad_y, grad_w, B, C, H, W, Ho,
                            Wo, k, s, p);
@@ -1006,19 +993,15 @@ extern "C" int cnuda_dwconvt2d_backward(const float* x, const float* w, const fl
 
 extern "C" int cnuda_add(const float* a, const float* b, float* out, long long n, cnuda_stream_t stream) {
     CNUDA_REQUIRE(a && b && out && n > 0, "cnuda_add: bad arguments");
-    const bool aligned = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0;
-    const long long n4 = aligned ? n / 4 : 0;
-    CNUDA_LAUNCH(add_kernel, dim3(stream_grid(n4 > 0 ? n4 : n, kT)), dim3(kT), 0, (hipStream_t)stream, a, b, out,
-                       n4, n);
+    const long long n4 = aligned16(a, b, out) ? n / 4 : 0;
+    CNUDA_LAUNCH_1D(add_kernel, n4 > 0 ? n4 : n, stream, a, b, out, n4, n);
     return check_launch("cnuda_add");
 }
 extern "C" int cnuda_act_backward(const float* grad_y, const float* y, float* grad_x, long long n, float slope,
                                   cnuda_stream_t stream) {
     CNUDA_REQUIRE(grad_y && y && grad_x && n > 0, "cnuda_act_backward: bad arguments");
     // 16-byte accesses for the aligned quads; a view at an odd offset takes the scalar loop, as in cnuda_add
-    const bool aligned = (((uintptr_t)grad_y | (uintptr_t)y | (uintptr_t)grad_x) & 15) == 0;
-    CNUDA_LAUNCH(act_bwd_kernel, dim3(stream_grid(n, kT)), dim3(kT), 0, (hipStream_t)stream, grad_y, y, grad_x,
-                       aligned ? n / 4 : 0, n, slope);
+    CNUDA_LAUNCH_1D(act_bwd_kernel, n, stream, grad_y, y, grad_x, aligned16(grad_y, y, grad_x) ? n / 4 : 0, n, slope);
     return check_launch("cnuda_act_backward");
 }
 extern "C" int cnuda_conv1x1_backward_data_act(const float* grad_y, const float* weight, const float* hidden,
@@ -1029,7 +1012,7 @@ extern "C" int cnuda_conv1x1_backward_data_act(const float* grad_y, const float*
     CNUDA_REQUIRE(Co >= 1 && Co <= 8, "cnuda_conv1x1_backward_data_act: %d output channels (1..8 are built)", Co);
     CNUDA_REQUIRE((HW & 3) == 0 && B <= 65535, "cnuda_conv1x1_backward_data_act: plane size %lld not a multiple of 4",
                   HW);
-    CNUDA_REQUIRE((((uintptr_t)grad_y | (uintptr_t)hidden | (uintptr_t)grad_hidden) & 15) == 0,
+    CNUDA_REQUIRE(aligned16(grad_y, hidden, grad_hidden),
                   "cnuda_conv1x1_backward_data_act: tensors must be 16-byte aligned");
     // enough workgroups for the chip: channel chunks of >= 32 until there are ~2048
     const long long quads = ceil_div(HW / 4, kT);
@@ -1046,28 +1029,32 @@ extern "C" int cnuda_conv1x1_backward_data_act(const float* grad_y, const float*
 #undef CNUDA_C1
     return check_launch("cnuda_conv1x1_backward_data_act");
 }
+// the row-wise launches: 16-byte copies where the rows allow them, and the grid -- a workgroup per 4,096 floats of a row,
+// up to 65,535 rows along y (the kernels stride over the rest)
 static int rows_vec_ok(long long HW, const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
-    return (HW & 3) == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+    return (HW & 3) == 0 && aligned16(a, b, c, d);
+}
+static dim3 rows_grid(long long HW, long long rows) {
+    const int chunks = (int)((HW / 4 + kT * 4 - 1) / (kT * 4));
+    return dim3(chunks > 0 ? chunks : 1, (unsigned)(rows < 65535 ? rows : 65535));
 }
 extern "C" int cnuda_copy_channels(const float* src, float* dst, int B, int Cn, long long HW, int Csrc, int src_off,
                                    int Cdst, int dst_off, cnuda_stream_t stream) {
     CNUDA_REQUIRE(src && dst && B > 0 && Cn > 0 && HW > 0, "cnuda_copy_channels: bad arguments");
     CNUDA_REQUIRE(src_off >= 0 && dst_off >= 0 && src_off + Cn <= Csrc && dst_off + Cn <= Cdst,
                   "cnuda_copy_channels: channel range out of bounds");
-    const int chunks = (int)((HW / 4 + kT * 4 - 1) / (kT * 4)) > 0 ? (int)((HW / 4 + kT * 4 - 1) / (kT * 4)) : 1;
     const long long rows = (long long)B * Cn;
     CNUDA_REQUIRE(rows < (1ll << 31), "cnuda_copy_channels: too many planes");
-    CNUDA_LAUNCH(copy_channels_kernel, dim3(chunks, (unsigned)(rows < 65535 ? rows : 65535)), dim3(kT), 0,
+    CNUDA_LAUNCH(copy_channels_kernel, rows_grid(HW, rows), dim3(kT), 0,
                        (hipStream_t)stream, src, dst, (int)rows, Cn, HW, Csrc, src_off, Cdst, dst_off, rows_vec_ok(HW, src, dst));
     return check_launch("cnuda_copy_channels");
 }
 extern "C" int cnuda_split_offset_mask(const float* om, float* offset, float* mask, int B, int taps, long long HW,
                                        cnuda_stream_t stream) {
     CNUDA_REQUIRE(om && offset && mask && B > 0 && taps > 0 && HW > 0, "cnuda_split_offset_mask: bad arguments");
-    const int chunks = (int)((HW / 4 + kT * 4 - 1) / (kT * 4)) > 0 ? (int)((HW / 4 + kT * 4 - 1) / (kT * 4)) : 1;
     const long long rows = (long long)B * 3 * taps;
     CNUDA_REQUIRE(rows < (1ll << 31), "cnuda_split_offset_mask: too many planes");
-    CNUDA_LAUNCH(split_offset_mask_kernel, dim3(chunks, (unsigned)(rows < 65535 ? rows : 65535)), dim3(kT), 0,
+    CNUDA_LAUNCH(split_offset_mask_kernel, rows_grid(HW, rows), dim3(kT), 0,
                        (hipStream_t)stream, om, offset, mask, (int)rows, taps, HW, rows_vec_ok(HW, om, offset, mask));
     return check_launch("cnuda_split_offset_mask");
 }
@@ -1075,10 +1062,9 @@ extern "C" int cnuda_split_offset_mask_backward(const float* grad_offset, const 
                                                 float* grad_om, int B, int taps, long long HW, cnuda_stream_t stream) {
     CNUDA_REQUIRE(grad_offset && grad_mask && mask && grad_om && B > 0 && taps > 0 && HW > 0,
                   "cnuda_split_offset_mask_backward: bad arguments");
-    const int chunks = (int)((HW / 4 + kT * 4 - 1) / (kT * 4)) > 0 ? (int)((HW / 4 + kT * 4 - 1) / (kT * 4)) : 1;
     const long long rows = (long long)B * 3 * taps;
     CNUDA_REQUIRE(rows < (1ll << 31), "cnuda_split_offset_mask_backward: too many planes");
-    CNUDA_LAUNCH(split_offset_mask_bwd_kernel, dim3(chunks, (unsigned)(rows < 65535 ? rows : 65535)), dim3(kT), 0,
+    CNUDA_LAUNCH(split_offset_mask_bwd_kernel, rows_grid(HW, rows), dim3(kT), 0,
                        (hipStream_t)stream, grad_offset, grad_mask, mask, grad_om, (int)rows, taps, HW,
                        rows_vec_ok(HW, grad_offset, grad_mask, mask, grad_om));
     return check_launch("cnuda_split_offset_mask_backward");
