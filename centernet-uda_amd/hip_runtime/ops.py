@@ -1099,6 +1099,10 @@ class _RegL1(Function):
         _l1_batch_check('reg_l1', 'reg_mask uint8, ind int64, target float32 (datasets/coco.py:168-174)',
                         mask, ind, target)
         B, ch, H, W = feat.shape
+        if ind.dim() != 2 or ind.shape[0] != B or tuple(mask.shape) != tuple(ind.shape) or \
+                tuple(target.shape) != tuple(ind.shape) + (ch,):      # the kernel walks all three by (B, M, ch)
+            raise RuntimeError("reg_l1: output %s vs ind %s / reg_mask %s / target %s"
+                               % (tuple(feat.shape), tuple(ind.shape), tuple(mask.shape), tuple(target.shape)))
         M = ind.shape[1]
         out2 = torch.empty(2, dtype=torch.float32, device=feat.device)
         ctx.args = (B, M, ch, H * W, 1 if periodic else 0, float(weight), float(angle_weight))

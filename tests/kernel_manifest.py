@@ -233,16 +233,25 @@ MANIFEST = {
         'tests/test_gpu_losses.py::test_detection_loss_golden',
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_keypoint_detection_loss_golden',
+        'tests/test_gpu_loss_forms.py::test_focal[',
+        'tests/test_gpu_loss_forms.py::test_detection_loss_module',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[focal',
     ],
     'finalize_kernel<FocalEpilogue>': [
         'tests/test_gpu_losses.py::test_detection_loss_golden',
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_keypoint_detection_loss_golden',
+        'tests/test_gpu_loss_forms.py::test_focal[',
+        'tests/test_gpu_loss_forms.py::test_detection_loss_module',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[focal',
     ],
     'focal_fwd_kernel': [
         'tests/test_gpu_losses.py::test_detection_loss_golden',
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_keypoint_detection_loss_golden',
+        'tests/test_gpu_loss_forms.py::test_focal[',
+        'tests/test_gpu_loss_forms.py::test_detection_loss_module',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[focal',
     ],
     'igemm_fwd_ws_kernel<128, DcnColsBufLoader, 16>': [
         'tests/test_gpu_fullsize.py::test_full_size_dcn_layer_matches_the_oracle[256to256_32sq',
@@ -401,16 +410,26 @@ MANIFEST = {
         'tests/test_gpu_losses.py::test_detection_loss_golden',
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_keypoint_detection_loss_golden',
+        'tests/test_gpu_loss_forms.py::test_reg_l1[',
+        'tests/test_gpu_loss_forms.py::test_detection_loss_module',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[reg',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[periodic',
     ],
     'regl1_fwd_kernel': [
         'tests/test_gpu_losses.py::test_detection_loss_golden',
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_keypoint_detection_loss_golden',
+        'tests/test_gpu_loss_forms.py::test_reg_l1[',
+        'tests/test_gpu_loss_forms.py::test_detection_loss_module',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[reg',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[periodic',
     ],
     'finalize_kernel<ScaleEpilogue>': [
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_uda_losses_golden',
         'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
+        'tests/test_gpu_loss_forms.py::test_softmax_family',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[softmax',
     ],
     'slab_reduce_few_kernel': [
         'tests/test_gpu_ops.py::test_conv2d_fwd_bwd',
@@ -470,19 +489,27 @@ MANIFEST = {
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_uda_losses_golden',
         'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
+        'tests/test_gpu_loss_forms.py::test_softmax_family',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[softmax',
     ],
     'softmax_grad_kernel<MaxSquareTerm>': [
         'tests/test_gpu_losses.py::test_uda_losses_golden',
         'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
+        'tests/test_gpu_loss_forms.py::test_softmax_family',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[softmax',
     ],
     'softmax_reduce_kernel<EntropyTerm>': [
         'tests/test_gpu_losses.py::test_full_size_losses_vs_oracle_cfg3',
         'tests/test_gpu_losses.py::test_uda_losses_golden',
         'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
+        'tests/test_gpu_loss_forms.py::test_softmax_family',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[softmax',
     ],
     'softmax_reduce_kernel<MaxSquareTerm>': [
         'tests/test_gpu_losses.py::test_uda_losses_golden',
         'tests/test_gpu_dla.py::test_uda_step128_plain_1e4',
+        'tests/test_gpu_loss_forms.py::test_softmax_family',
+        'tests/test_gpu_fuzz.py::test_losses_random_geometry[softmax',
     ],
     # (round 6: DCN.forward reads offsets / mask out of the offset convolution's output; the split pair remains for
     # DCNv2.forward(input, offset, mask)'s callers and CNUDA_DCN_OM=0)
@@ -516,10 +543,10 @@ MANIFEST = {
         'tests/test_gpu_ops.py::test_conv2d_fwd_bwd[disc4x4',
         'tests/test_gpu_fuzz.py::test_conv2d_random_geometry',
     ],
-    'bce_const_fwd_kernel': ['tests/test_gpu_losses.py::test_uda_losses_golden'],
-    'bce_const_bwd_kernel': ['tests/test_gpu_losses.py::test_uda_losses_golden'],
-    'entropy_map_fwd_kernel': ['tests/test_gpu_losses.py::test_uda_losses_golden'],
-    'entropy_map_bwd_kernel': ['tests/test_gpu_losses.py::test_uda_losses_golden'],
+    'bce_const_fwd_kernel': ['tests/test_gpu_losses.py::test_uda_losses_golden', 'tests/test_gpu_loss_forms.py::test_bce_with_logits_const'],
+    'bce_const_bwd_kernel': ['tests/test_gpu_losses.py::test_uda_losses_golden', 'tests/test_gpu_loss_forms.py::test_bce_with_logits_const'],
+    'entropy_map_fwd_kernel': ['tests/test_gpu_losses.py::test_uda_losses_golden', 'tests/test_gpu_loss_forms.py::test_softmax_family'],
+    'entropy_map_bwd_kernel': ['tests/test_gpu_losses.py::test_uda_losses_golden', 'tests/test_gpu_loss_forms.py::test_softmax_family'],
     'conv1x1_dgrad_act_kernel<3>': [          # the rotated-box `wh` head (3 outputs)
         'tests/test_gpu_dla.py::test_dla_forward_backward_golden[rot',
         'tests/test_gpu_dla.py::test_uda_step128_plain_1e4[advent',
@@ -615,4 +642,15 @@ MANIFEST = {
     ],
     **{'conv1x1_dgrad_act_kernel<%d>' % co: ['tests/test_gpu_spatial_forms.py::test_head_gradient_every_output_count[%d-' % co]
        for co in (1, 4, 5, 7, 8)},
+    # ---- the loss kernels that no benched step launches (keypoint heads, the FDA plugin's entropy, the helpers):
+    # tests/test_gpu_loss_forms.py asserts each by name ----
+    **{'kpsl1_%s_kernel' % d: ['tests/test_gpu_loss_forms.py::test_kps_l1[',
+                               'tests/test_gpu_loss_forms.py::test_detection_loss_module[keypoints',
+                               'tests/test_gpu_fuzz.py::test_losses_random_geometry[kps',
+                               'tests/test_gpu_losses.py::test_keypoint_detection_loss_golden'] for d in ('fwd', 'bwd')},
+    **{'softmax_%s_kernel<EtaEntropyTerm>' % d: ['tests/test_gpu_loss_forms.py::test_softmax_family',
+                                                 'tests/test_gpu_fuzz.py::test_losses_random_geometry[softmax']
+       for d in ('reduce', 'grad')},
+    'sigmoid_clamp_kernel': ['tests/test_gpu_loss_forms.py::test_sigmoid_clamp_in_place'],
+    'gather_feat_kernel': ['tests/test_gpu_loss_forms.py::test_gather_feat_and_the_index_out_of_range'],
 }

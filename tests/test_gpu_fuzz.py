@@ -1,10 +1,12 @@
 """MI355X: randomised geometry sweeps of the convolution / transposed-convolution / depthwise / DCN entry points
-against CPU torch (the primitives the oracle is built from).  Seeds are fixed: the cases are the same on every
+against CPU torch (the primitives the oracle is built from), and of BatchNorm and the losses against their fp64 oracles.  Seeds are fixed: the cases are the same on every
 run; they exist to catch tile-edge and padding-class mistakes that the hand-picked shapes miss.  1e-4 of scale."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import loss_oracle
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -256,6 +258,15 @@ def test_batch_norm_random_split_geometry(case):
     got = forms.run_autograd(c)
     assert got['launched'] == forms.TRAIN_KERNELS, got['launched']
     forms.check_case(c, got)
+
+
+@pytest.mark.parametrize('case', loss_oracle.fuzz_cases(), ids=loss_oracle.fuzz_id)
+def test_losses_random_geometry(case):
+    """20 draws of (family, B, C or channels or joints, H, W, M or peaks) through the builders, the fp64 oracle, the exact
+    checks and the bounds of tests/test_gpu_loss_forms.py: the softmax family, focal, masked L1 (plain and periodic) and
+    the keypoint loss with five pairs"""
+    import test_gpu_loss_forms as forms
+    forms.check_fuzz(case)
 
 
 def _decode_cases(n, seed):
