@@ -463,7 +463,8 @@ class _FanPlan:
     aggregation steps): found once by walking the same loops over tensor ids, then every tensor is forked into that many
     aliases when it is produced."""
 
-    def __init__(self, seg, n_feats):
+    def __init__(self, seg, n_feats, low_level=False):
+        """low_level: the plan of DLASeg.features_with_low_level, which also hands out the finest map DLAUp returns: one more reader"""
         import collections
         reads = collections.Counter()
         counter = [n_feats]
@@ -475,6 +476,8 @@ class _FanPlan:
         y = out[:seg.last_level - seg.first_level]
         IDAUp.plan(y, 0, len(y), reads, fresh)
         reads[y[-1]] += 1                      # the map the heads read
+        if low_level:
+            reads[y[0]] += 1                   # the low-level tap, beside the final IDAUp's skip
         self.reads, self.n, self.n_ids = reads, 0, counter[0]
 
     def start(self):
@@ -515,6 +518,7 @@ class DLASeg(nn.Module):
             raise ValueError("only 'dla34' is built (dla.py:521 hard-codes it)")
         self.down_ratio, self.rotated_boxes = down_ratio, rotated_boxes
         self._fan_plan = None       # (n feature maps, _FanPlan): the aggregation's reader counts, walked once
+        self._fan_plan_low = None   # the same with the low-level tap's extra reader
         self.first_level, self.last_level = int(math.log2(down_ratio)), last_level
         self.base = dla34(pretrained=pretrained)
         if freeze_base:
@@ -542,6 +546,11 @@ class DLASeg(nn.Module):
                             m.bias.zero_()
             setattr(self, head, fc)
 
+    @property
+    def low_level_channels(self):
+        """Channels of the low-level tap (features_with_low_level): what a low-level head is built on."""
+        return self.base.channels[self.first_level]
+
     def features(self, x):
         """The [B, 64, H/4, W/4] map every head reads (dla.py:500-505)."""
         feats = self.base(x)
@@ -559,6 +568,26 @@ class DLASeg(nn.Module):
         self.ida_up(y, 0, len(y), fan)
         return y[-1].take()
 
+    def features_with_low_level(self, x):
+        """-> (features(x), the finest map DLAUp returns): `y[0]` below, which the final IDAUp reads once as a skip -- one
+        aggregation stage before the heads' map, with its shape.  A walk of its own, so that features() stays the code it
+        was; the alias plan counts the tap as one more reader of `y[0]`."""
+        feats = self.base(x)
+        if not (torch.is_grad_enabled() and feats[-1].requires_grad):
+            feats = self.dla_up(feats)
+            y = list(feats[:self.last_level - self.first_level])
+            low = y[0]
+            self.ida_up(y, 0, len(y))
+            return y[-1], low
+        if self._fan_plan_low is None or self._fan_plan_low[0] != len(feats):
+            self._fan_plan_low = (len(feats), _FanPlan(self, len(feats), low_level=True))
+        fan = self._fan_plan_low[1].start()
+        feats = self.dla_up(feats, fan)
+        y = list(feats[:self.last_level - self.first_level])
+        low = y[0].take()
+        self.ida_up(y, 0, len(y), fan)
+        return y[-1].take(), low
+
     def _head_order(self, dense=('hm',)):
         """The heads in the order they are evaluated: those whose gradient is a dense map (`dense`) LAST, so that the
         backward pass runs them first -- their input gradient takes the feature map's slot with a plain write and the
@@ -571,7 +600,17 @@ class DLASeg(nn.Module):
         out = {head: getattr(self, head)(f) for head, f in zip(order, fork(feat, len(order)))}
         return {h: out[h] for h in self.heads}        # (the dictionary keeps the heads' own order)
 
-    def forward_domains(self, source, target, target_grad_heads=('hm',)):
+    def forward_low_level(self, x, low_level_head):
+        """forward(x) with the output of `low_level_head` -- a module that is not one of this backend's -- on the
+        low-level tap added as 'hm_low' behind the heads' own."""
+        feat, low = self.features_with_low_level(x)
+        order = self._head_order()
+        out = {head: getattr(self, head)(f) for head, f in zip(order, fork(feat, len(order)))}
+        out = {h: out[h] for h in self.heads}
+        out['hm_low'] = low_level_head(low)
+        return out
+
+    def forward_domains(self, source, target, target_grad_heads=('hm',), low_level_head=None):
         """Both domains' forward passes of a UDA step (uda/entropy_minimization.py:18-19) as ONE pass over the
         concatenated batch: every layer runs once on twice the pixels (half the launches, fuller GEMM tiles on
         the small feature maps), each BatchNorm normalises the two halves by their own batch statistics and updates
@@ -580,14 +619,20 @@ class DLASeg(nn.Module):
 
         target_grad_heads: the heads whose TARGET output feeds a loss.  The other target heads are evaluated
         without a tape -- in the reference their outputs exist but no backward pass ever reaches them -- so that
-        the single backward pass of the batched graph does not pay for 16 images of zero gradient there."""
+        the single backward pass of the batched graph does not pay for 16 images of zero gradient there.
+
+        low_level_head: as in forward_low_level(); evaluated once on the low-level map of the whole 2B batch, with a tape, and
+        split into 'hm_low' of both returned dictionaries."""
         import hip_runtime as hr
         if source.shape != target.shape:
             raise RuntimeError("forward_domains: source %s and target %s batches differ in shape"
                                % (tuple(source.shape), tuple(target.shape)))
         B = source.shape[0]
         with hr.domain_groups(2 if self.training else 1):
-            feat = self.features(torch.cat([source, target], 0))
+            if low_level_head is None:
+                feat = self.features(torch.cat([source, target], 0))
+            else:
+                feat, low = self.features_with_low_level(torch.cat([source, target], 0))
         out_s, out_t = {}, {}
         f_t = feat[B:]
         # one alias of the feature map per head (hip_runtime.fanout).  The heads that only see the source half come first:
@@ -607,7 +652,11 @@ class DLASeg(nn.Module):
                 # it fails loudly in backward() instead of silently training nothing
                 out_t[head] = _TapeFreeTargetHead.apply(y_t, f_t, head) if f_t.requires_grad else y_t
         # (the dictionaries keep the heads' own order, like two forward() calls)
-        return {h: out_s[h] for h in self.heads}, {h: out_t[h] for h in self.heads}
+        out_s, out_t = {h: out_s[h] for h in self.heads}, {h: out_t[h] for h in self.heads}
+        if low_level_head is not None:
+            z = low_level_head(low)
+            out_s['hm_low'], out_t['hm_low'] = z[:B], z[B:]
+        return out_s, out_t
 
 
 def build(num_classes, num_keypoints=0, head_conv=256, down_ratio=4, freeze_base=False, rotated_boxes=False):

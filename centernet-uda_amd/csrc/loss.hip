@@ -6,6 +6,7 @@
 //   losses/entropy.py:10-28     EntropyLoss      losses/max_square.py:6-14 MaxSquareLoss
 //   utils/image.py:121-124      entropy_map      losses/advent.py:10-18    BCE-with-logits vs constant
 //   image-wise class-balanced max-squares (ICCV 2019, not in the reference): argmax histogram, weights, loss
+//   multi-level self-produced guidance (same paper, not in the reference): labels from two heat maps, their cross-entropy
 // Every loss is a pair (forward -> scalar(s) in device memory, backward ->
 // gradient w.r.t. the logits given a device-resident upstream scalar).
 // The shared pieces keep every order of operations and so the bits: tests/test_gpu_loss_bits.py.
@@ -21,7 +22,7 @@ __device__ __forceinline__ float sgnf(float v) { return v > 0.0f ? 1.0f : (v < 0
 __device__ __forceinline__ bool in_clamp(float s) { return s >= kProbLo && s <= kProbHi; }   // clamp passes gradient
 
 // ---------------- the reduction tail ----------------
-// Every thread's N fp64 sums -> the block's (valid in thread 0), one after the other through `red`.  N is 1 or 3: the
+// Every thread's N fp64 sums -> the block's (valid in thread 0), one after the other through `red`.  N is 1, 2 or 3: the
 // loops over the sums unroll, and the sums stay in registers (no loss kernel has scratch: profiles/loss_dedupe_ab.txt).
 template <int N>
 __device__ __forceinline__ void block_sums(double (&acc)[N], double* red) {
@@ -435,6 +436,64 @@ __global__ void iw_max_square_grad_kernel(const float* __restrict__ x, const flo
     }
 }
 
+// ---------------- multi-level self-produced guidance (the max-squares paper's third part) ----------------
+//   p = softmax_c(x) of the final heat map, q = softmax_c(z) of the low-level one;  e = (p + q) / 2
+//   a = argmax_c e, the lowest channel on a tie;  the pixel is guided when max_c e > threshold
+//   loss = sum_{guided} (logsumexp_c z - z[a]) / max(N_guided, 1);   labels[b,p] = a, or -1 where unguided
+// partial[blk*2 + {0,1}] = sum of the guided pixels' cross-entropies, their number (whole numbers in fp64: exact)
+__global__ __launch_bounds__(kT) void guidance_fwd_kernel(const float* __restrict__ x, const float* __restrict__ z,
+                                                          float threshold, int* __restrict__ labels,
+                                                          double* __restrict__ partial, int B, int C, long long HW) {
+    __shared__ double red[16];
+    double ce = 0.0, ng = 0.0;
+    const long long total = (long long)B * HW;
+    for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < total; i += (long long)gridDim.x * kT) {
+        const SoftmaxPixel p(x, i, C, HW), q(z, i, C, HW);
+        float best = 0.5f * (p.v(0) + q.v(0));
+        int a = 0;
+        for (int c = 1; c < C; ++c) {
+            const float e = 0.5f * (p.v(c) + q.v(c));
+            if (e > best) { best = e; a = c; }   // strict: the lowest channel keeps a tie
+        }
+        const bool guided = best > threshold;
+        labels[i] = guided ? a : -1;
+        if (guided) {
+            // -log q_a as logsumexp(z) - z[a]: finite whatever the logits (q_a itself underflows near |z| = 80)
+            ce += (double)(logf(q.den) + (q.mx - q.px[(size_t)a * q.HW]));
+            ng += 1.0;
+        }
+    }
+    double acc[2] = {ce, ng};
+    store_partials(acc, partial, red);
+}
+struct GuidanceEpilogue {   // out[0] = loss, out[1] = N_guided (kept for backward)
+    static constexpr int N = 2;
+    __device__ void operator()(const double (&s)[2], float* out) const {
+        out[0] = (float)(s[0] / (s[1] > 1.0 ? s[1] : 1.0));
+        out[1] = (float)s[1];
+    }
+};
+// dz_c = upstream * (q_c - [c == a]) / max(N_guided, 1) on a guided pixel, a plain 0 elsewhere: every element is written
+__global__ void guidance_grad_kernel(const float* __restrict__ z, const int* __restrict__ labels,
+                                     const float* __restrict__ fwd_out, const float* __restrict__ upstream,
+                                     float* __restrict__ grad, int B, int C, long long HW) {
+    const float up = upstream[0] / fmaxf(fwd_out[1], 1.0f);
+    const long long total = (long long)B * HW;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const int a = labels[i];
+        if (a < 0 || a >= C) {                    // unguided (a label outside the channels is treated as unguided too)
+            const long long b = i / HW;
+            float* pg = grad + (size_t)b * C * HW + (i - b * HW);
+            for (int c = 0; c < C; ++c) pg[(size_t)c * HW] = 0.0f;
+            continue;
+        }
+        const SoftmaxPixel q(z, i, C, HW);
+        float* pg = grad + q.base;
+        for (int c = 0; c < C; ++c) pg[(size_t)c * q.HW] = up * (q.v(c) - (c == a ? 1.0f : 0.0f));
+    }
+}
+
 // entropy_map: out_c = -f(v_c) / log2(C)
 __global__ void entropy_map_fwd_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int C,
                                        long long HW) {
@@ -788,6 +847,28 @@ extern "C" int cnuda_iw_max_square_backward(const float* logits, const float* we
     CNUDA_LAUNCH(iw_max_square_grad_kernel, dim3(stream_grid((long long)B * HW, kT)), dim3(kT), 0, (hipStream_t)stream,
                  logits, weights, upstream, (float)iw_max_square_scale(B, C), grad_logits, B, C, HW);
     return check_launch("cnuda_iw_max_square_backward");
+}
+extern "C" int cnuda_guidance_forward(const float* high, const float* low, float threshold, int32_t* labels,
+                                      float* out2, int B, int C, long long HW, void* workspace, size_t workspace_bytes,
+                                      cnuda_stream_t stream) {
+    CNUDA_REQUIRE(high && low && labels && out2 && B > 0 && C > 0 && HW > 0, "cnuda_guidance_forward: bad arguments");
+    CNUDA_REQUIRE(threshold >= 0.0f && threshold < 1.0f, "cnuda_guidance_forward: threshold %g outside [0, 1)",
+                  (double)threshold);
+    hipStream_t st = (hipStream_t)stream;
+    return reduced_loss("cnuda_guidance_forward", workspace, workspace_bytes, (long long)B * HW, st, GuidanceEpilogue{},
+                        out2, [&](int blocks, double* partial) {
+        CNUDA_LAUNCH(guidance_fwd_kernel, dim3(blocks), dim3(kT), 0, st, high, low, threshold, (int*)labels, partial, B,
+                     C, HW);
+    });
+}
+extern "C" int cnuda_guidance_backward(const float* low, const int32_t* labels, const float* out2,
+                                       const float* upstream, float* grad_low, int B, int C, long long HW,
+                                       cnuda_stream_t stream) {
+    CNUDA_REQUIRE(low && labels && out2 && upstream && grad_low && B > 0 && C > 0 && HW > 0,
+                  "cnuda_guidance_backward: bad arguments");
+    CNUDA_LAUNCH(guidance_grad_kernel, dim3(stream_grid((long long)B * HW, kT)), dim3(kT), 0, (hipStream_t)stream, low,
+                 (const int*)labels, out2, upstream, grad_low, B, C, HW);
+    return check_launch("cnuda_guidance_backward");
 }
 extern "C" int cnuda_entropy_map_forward(const float* logits, float* out, int B, int C, long long HW,
                                          cnuda_stream_t stream) {

@@ -160,6 +160,8 @@ class _Sig:
     cnuda_argmax_histogram = (_I, [_P, _P, _I, _I, _LL, _P])
     cnuda_iw_max_square_forward = (_I, [_P, _P, _F, _P, _P, _I, _I, _LL] + _WS)
     cnuda_iw_max_square_backward = (_I, [_P] * 4 + [_I, _I, _LL, _P])
+    cnuda_guidance_forward = (_I, [_P, _P, _F, _P, _P, _I, _I, _LL] + _WS)
+    cnuda_guidance_backward = (_I, [_P] * 5 + [_I, _I, _LL, _P])
     cnuda_bce_const_forward = (_I, [_P, _F, _P, _LL, _P])
     cnuda_bce_const_backward = (_I, [_P, _F, _P, _P, _LL, _P])
     cnuda_sigmoid_clamp_ = (_I, [_P, _P, _LL, _P])

@@ -1274,6 +1274,70 @@ def iw_max_square_loss(hm_logits, ratio=0.2):
     return _IWMaxSquare.apply(hm_logits, ratio)
 
 
+def _check_threshold(who, threshold):
+    threshold = float(threshold)
+    if not 0.0 <= threshold < 1.0:
+        raise ValueError("%s: threshold must be in [0, 1), got %r" % (who, threshold))
+    return threshold
+
+
+def _guidance_forward(low, high, threshold):
+    """low, high: contiguous fp32 [B, C, ...] on the GPU -> (labels int32 [B, ...], out2 = {loss, guided pixels})"""
+    if low.shape != high.shape or low.dim() < 2:
+        raise RuntimeError("guidance: low-level map %s vs final map %s" % (tuple(low.shape), tuple(high.shape)))
+    B, C = low.shape[0], low.shape[1]
+    shape = (B, C, low.numel() // (B * C))
+    labels = torch.empty((B,) + tuple(low.shape[2:]), dtype=torch.int32, device=low.device)
+    out2 = torch.empty(2, dtype=torch.float32, device=low.device)
+    check(lib().cnuda_guidance_forward(ptr(high), ptr(low), threshold, ptr(labels), ptr(out2), *shape, *_loss_ws(low),
+                                       stream()), 'guidance_forward')
+    return labels, out2, shape
+
+
+def guidance_labels(high, low, threshold=0.95):
+    """high, low [B, C, H, W] (the final and the low-level heat map's logits) -> int32 [B, H, W]: the channel where the
+    mean of the two class softmaxes is largest (the lowest on a tie) if that mean exceeds `threshold`, else -1.  No
+    gradient, no read-back; a fresh tensor every call."""
+    threshold = _check_threshold('guidance_labels', threshold)
+    require_gpu(high, low)
+    return _guidance_forward(f32c(low.detach()), f32c(high.detach()), threshold)[0]
+
+
+class _Guidance(Function):
+    """_IWMaxSquare's sibling with two inputs: the labels and their number, found from both maps in the forward, are
+    constants of the backward pass, and only `low` has a gradient."""
+
+    @staticmethod
+    def forward(ctx, low, high, threshold):
+        require_gpu(low, high)
+        low, high = f32c(low), f32c(high)
+        labels, out2, ctx.shape = _guidance_forward(low, high, threshold)
+        ctx.save_for_backward(low, labels, out2)
+        count = out2[1].clone()
+        ctx.mark_non_differentiable(count)
+        return out2[0].clone(), count
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gcount):
+        low, labels, out2 = ctx.saved_tensors
+        grad = torch.empty_like(low)
+        up = f32c(g.reshape(1))
+        check(lib().cnuda_guidance_backward(ptr(low), ptr(labels), ptr(out2), ptr(up), ptr(grad), *ctx.shape, stream()),
+              'guidance_backward')
+        return grad, None, None
+
+
+def guidance_loss(low, high, threshold=0.95, return_count=False):
+    """Multi-level self-produced guidance (Chen, Xue, Cai, ICCV 2019): the cross-entropy of softmax(low) against
+    guidance_labels(high, low, threshold), summed over the guided pixels and divided by max(their number, 1) -- an exact 0
+    with an all-zero gradient when there is none.  The gradient goes to `low` only: the labels are constants and `high`,
+    whether it requires grad or not, gets None.  return_count: also the number of guided pixels (a device scalar)."""
+    threshold = _check_threshold('guidance_loss', threshold)
+    loss, count = _Guidance.apply(low, high, threshold)
+    return (loss, count) if return_count else loss
+
+
 def bce_with_logits_const(logits, label):
     return _LogitsLoss.apply(logits, _BCE_CONST, float(label))
 

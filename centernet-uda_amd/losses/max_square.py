@@ -26,3 +26,24 @@ class IWMaxSquareLoss(torch.nn.Module):
     def forward(self, outputs, batch):
         loss = ops.iw_max_square_loss(outputs['hm'], self.ratio)
         return loss, {'iw_max_square_loss': loss}
+
+
+class GuidanceLoss(torch.nn.Module):
+    """The same paper's multi-level self-produced guidance: the low-level heat map `hm_low` learns the labels that it
+    and the final `hm` agree on.  With p, q the class softmaxes of `hm` and `hm_low` and e = (p + q) / 2, a pixel whose
+    max_c e exceeds `threshold` is guided towards a = argmax_c e (the lowest channel on a tie); the loss is the mean over
+    the guided pixels of -log q_a, an exact 0 when there is none.  Labels and mask are constants: `hm` gets no gradient."""
+
+    def __init__(self, threshold=0.95):
+        super().__init__()
+        if not 0.0 <= float(threshold) < 1.0:
+            raise ValueError("GuidanceLoss: threshold must be in [0, 1), got %r" % (threshold,))
+        self.threshold = float(threshold)
+
+    def terms(self, outputs):
+        """-> (loss, number of guided pixels in the batch), both device scalars"""
+        return ops.guidance_loss(outputs['hm_low'], outputs['hm'], self.threshold, return_count=True)
+
+    def forward(self, outputs, batch):
+        loss, _ = self.terms(outputs)
+        return loss, {'guidance_loss': loss}

@@ -9,6 +9,7 @@ _PLUGINS = {
     'EntropyMinimization': 'uda.entropy_minimization',
     'MaxSquaresMinimization': 'uda.max_squares_minimization',
     'IWMaxSquaresMinimization': 'uda.max_squares_minimization',
+    'MultiLevelMaxSquaresMinimization': 'uda.max_squares_minimization',
     'AdversarialEntropyMinimization': 'uda.adversarial_entropy_minimization',
     'MeanTeacher': 'uda.mean_teacher',
     'WeakStrongTeacher': 'uda.mean_teacher',

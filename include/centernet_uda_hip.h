@@ -671,6 +671,18 @@ int cnuda_iw_max_square_forward(const float* logits, const int32_t* hist, float 
                                 cnuda_stream_t stream);
 int cnuda_iw_max_square_backward(const float* logits, const float* weights, const float* upstream, float* grad_logits,
                                  int B, int C, long long HW, cnuda_stream_t stream);
+/* Multi-level self-produced guidance (the same paper's third part; neither in the reference).  high, low [B,C,HW]: the
+ * logits of the final and of the low-level heat map.  p = softmax_C(high), q = softmax_C(low), e = (p + q) / 2,
+ * a = argmax_c e (the lowest channel on a tie); a pixel is guided when max_c e > threshold, 0 <= threshold < 1.
+ *   labels[b,p] = a, or -1 where unguided (int32 [B,HW]);   N = number of guided pixels of the whole batch
+ *   out2 = {sum_{guided} (logsumexp_c low - low[a]) / max(N, 1), N}: finite for any logits, {0, 0} without a guided pixel.
+ * backward: grad_low = upstream * guided * (q_c - [c == a]) / max(N, 1), every element written (plain zeros where
+ * unguided); `high` has no gradient.  No call synchronises; fp64 sums in a fixed order, no float atomics: the same bits
+ * every run. */
+int cnuda_guidance_forward(const float* high, const float* low, float threshold, int32_t* labels, float* out2, int B,
+                           int C, long long HW, void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+int cnuda_guidance_backward(const float* low, const int32_t* labels, const float* out2, const float* upstream,
+                            float* grad_low, int B, int C, long long HW, cnuda_stream_t stream);
 int cnuda_bce_const_forward(const float* logits, float label, float* out1, long long n, cnuda_stream_t stream);
 int cnuda_bce_const_backward(const float* logits, float label, const float* upstream, float* grad_logits,
                              long long n, cnuda_stream_t stream);
