@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "evalcoco.cuh"
+#include "polyiou.cuh"
 
 // the axis IoU's last bit decides comparisons against a threshold: no fused multiply-add (the Makefile says so too)
 #pragma clang fp contract(off)
@@ -154,6 +155,27 @@ __global__ __launch_bounds__(256) void eval_iou_axis_kernel(const int* __restric
             o = i / (dw * dh + gw * gh - i);
         }
         iou[q.pair0 + p] = o;
+    }
+}
+
+// One thread per pair: the exact polygon IoU (polyiou.cuh), subject = detection, clipper = ground truth.  quads: float32
+// [ND + NGT, 4, 2], detections first.  The columns of the grid past the groups write the areas of all boxes, whatever
+// the groups say.
+__global__ __launch_bounds__(256) void eval_iou_quads_kernel(const int* __restrict__ groups, int num_groups, int ND, int NGT,
+                                                             long long num_pairs, const float* __restrict__ quads,
+                                                             double* __restrict__ iou, double* __restrict__ area) {
+    if ((int)blockIdx.x >= num_groups) {
+        const long long box = ((long long)(blockIdx.x - num_groups) * gridDim.y + blockIdx.y) * blockDim.x + threadIdx.x;
+        if (box < (long long)ND + NGT) area[box] = polyiou::quad_area(polyiou::load_quad(quads + 8 * box));
+        return;
+    }
+    Group q;
+    if (!load_group(groups, blockIdx.x, ND, NGT, num_pairs, q)) return;
+    const long long pairs = (long long)q.nd * q.ng;
+    for (long long p = (long long)blockIdx.y * blockDim.x + threadIdx.x; p < pairs; p += (long long)gridDim.y * blockDim.x) {
+        const float* D = quads + 8 * (size_t)(q.det0 + (int)(p / q.ng));
+        const float* Gt = quads + 8 * ((size_t)ND + (size_t)(q.gt0 + (int)(p % q.ng)));
+        iou[q.pair0 + p] = polyiou::convex_quad_iou(polyiou::load_quad(D), polyiou::load_quad(Gt)).iou;
     }
 }
 
@@ -341,6 +363,23 @@ extern "C" int cnuda_eval_iou_axis(const float* det_boxes, const float* gt_boxes
     CNUDA_REQUIRE(det_boxes && gt_boxes && groups && iou, "%s: null pointer", who);
     CNUDA_LAUNCH(eval_iou_axis_kernel, dim3((unsigned)num_groups, kPairChunks), dim3(256), 0, (hipStream_t)stream, groups,
                  num_det, num_gt, num_pairs, det_boxes, gt_boxes, iou);
+    return check_launch(who);
+}
+
+extern "C" int cnuda_eval_iou_quads(const float* quads, const int* groups, int num_groups, int num_det, int num_gt,
+                                    long long num_pairs, double* iou, double* area, void* stream) {
+    const char* who = "cnuda_eval_iou_quads";
+    const char* bad = groups_error(num_groups, num_det, num_gt, num_pairs);
+    CNUDA_REQUIRE(!bad, "%s: %s", who, bad);
+    const long long boxes = (long long)num_det + num_gt;
+    CNUDA_REQUIRE(boxes < (1ll << 31), "%s: too many boxes", who);
+    if (boxes == 0) return 0;
+    const bool any_pair = num_groups > 0 && num_pairs > 0;
+    CNUDA_REQUIRE(quads && area && (!any_pair || (groups && iou)), "%s: null pointer", who);
+    const int groups_run = any_pair ? num_groups : 0;
+    const unsigned area_columns = (unsigned)((boxes + 256ll * kPairChunks - 1) / (256ll * kPairChunks));
+    CNUDA_LAUNCH(eval_iou_quads_kernel, dim3((unsigned)groups_run + area_columns, kPairChunks), dim3(256), 0,
+                 (hipStream_t)stream, groups, groups_run, num_det, num_gt, num_pairs, quads, iou, area);
     return check_launch(who);
 }
 

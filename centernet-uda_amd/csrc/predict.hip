@@ -7,7 +7,8 @@
 //                    the resize matrix, clips axis-aligned boxes to the source image and counts the rows at or above
 //                    the score threshold.
 //   soft-NMS merge   cnuda_soft_nms_merge runs Gaussian soft-NMS per (image, class) over the candidates of several
-//                    scales and orders what survives per image.
+//                    scales and orders what survives per image; cnuda_soft_nms_merge_rotated is the same two kernels
+//                    on quadrilaterals, with the exact polygon IoU of polyiou.cuh.
 //
 // All of it is element-wise or tiny: the merge is one grid-stride pass (one float32 rounding per output, no contraction:
 // the build has -ffp-contract=off), the projection one workgroup per image, the soft-NMS a latency chain of arg-max
@@ -15,6 +16,7 @@
 // one integer LDS atomic (compaction of a class's members) cannot change a result, because every order below is
 // decided by explicit (score, class, index) keys.
 #include "common.h"
+#include "polyiou.cuh"
 
 #include <math.h>
 
@@ -158,12 +160,62 @@ __device__ __forceinline__ int image_candidates(const int* __restrict__ ncand, i
     return ncand ? min(max(ncand[b], 0), N) : N;
 }
 
+// The box record: what the two stages know about a candidate's geometry.  `Rec` is a row as it is stored (global memory
+// and LDS), `Winner` a round's winner widened once, `iou` the overlap of the winner with a candidate.
+struct AxisBox {                                      // (x1, y1, x2, y2)
+    using Rec = float4;
+    struct Winner { double x1, y1, x2, y2, area; };
+    static __device__ __forceinline__ Rec load(const float* rows, size_t row) {
+        return *reinterpret_cast<const float4*>(rows + row * 4);
+    }
+    static __device__ __forceinline__ void store(float* rows, size_t row, const Rec& r) {
+        *reinterpret_cast<float4*>(rows + row * 4) = r;
+    }
+    static __device__ __forceinline__ Rec zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+    static __device__ __forceinline__ Winner winner(const Rec& b) {
+        Winner w = {b.x, b.y, b.z, b.w, 0.0};
+        w.area = (w.x2 - w.x1) * (w.y2 - w.y1);
+        return w;
+    }
+    static __device__ __forceinline__ double iou(const Winner& w, const Rec& bj) {
+        const double jx1 = bj.x, jy1 = bj.y, jx2 = bj.z, jy2 = bj.w;
+        const double iw = fmin(w.x2, jx2) - fmax(w.x1, jx1), ih = fmin(w.y2, jy2) - fmax(w.y1, jy1);
+        double o = 0.0;
+        if (iw > 0.0 && ih > 0.0) {
+            const double inter = iw * ih, ua = (w.area + (jx2 - jx1) * (jy2 - jy1)) - inter;
+            if (ua > 0.0) o = inter / ua;
+        }
+        return o;
+    }
+};
+struct QuadBox {                                      // four (x, y) vertices; the overlap is polyiou.cuh's
+    struct Rec { float4 lo, hi; };
+    using Winner = polyiou::Quad;
+    static __device__ __forceinline__ Rec load(const float* rows, size_t row) {
+        const float4* p = reinterpret_cast<const float4*>(rows + row * 8);
+        return {p[0], p[1]};
+    }
+    static __device__ __forceinline__ void store(float* rows, size_t row, const Rec& r) {
+        float4* p = reinterpret_cast<float4*>(rows + row * 8);
+        p[0] = r.lo, p[1] = r.hi;
+    }
+    static __device__ __forceinline__ Rec zero() { return {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)}; }
+    static __device__ __forceinline__ Winner winner(const Rec& b) {
+        return {{b.lo.x, b.lo.z, b.hi.x, b.hi.z}, {b.lo.y, b.lo.w, b.hi.y, b.hi.w}};
+    }
+    static __device__ __forceinline__ double iou(const Winner& w, const Rec& bj) {
+        return polyiou::convex_quad_iou(w, winner(bj)).iou;           // subject = winner, clipper = candidate
+    }
+};
+
 // Stage 1: one workgroup per (image, class).  final_score [B,N] double: the emitted score of a candidate, -1 for every
 // candidate of this class that was not emitted (candidates of no class in [0, C) are never written: stage 2 skips them).
+// Static LDS: 56 KiB with AxisBox, 88 KiB with QuadBox (2048 quads are 64 KiB; a workgroup of gfx950 may hold 160 KiB).
+template <class Box>
 __global__ __launch_bounds__(kT) void soft_nms_class_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                             const int* __restrict__ classes, const int* __restrict__ ncand,
                                                             double* __restrict__ final_score, int N, int C) {
-    __shared__ float4 box[kMaxCand];
+    __shared__ typename Box::Rec box[kMaxCand];
     __shared__ double score[kMaxCand];
     __shared__ int index[kMaxCand];
     __shared__ Best wbest[kT / 64];
@@ -177,7 +229,7 @@ __global__ __launch_bounds__(kT) void soft_nms_class_kernel(const float* __restr
     for (int i = tid; i < n; i += kT) {
         if (classes[base + i] != c) continue;
         const int at = atomicAdd(&members, 1);        // (placement only: every decision below compares `index`)
-        box[at] = *reinterpret_cast<const float4*>(boxes + (base + i) * 4);
+        box[at] = Box::load(boxes, base + i);
         score[at] = (double)scores[base + i];
         index[at] = i;
         final_score[base + i] = -1.0;
@@ -196,9 +248,7 @@ __global__ __launch_bounds__(kT) void soft_nms_class_kernel(const float* __restr
         for (int w = 1; w < kT / 64; ++w)
             if (better(wbest[w].score, wbest[w].idx, best)) best = wbest[w];
         if (!(best.score >= 1e-3)) break;             // uniform: every thread reads the same four records
-        const float4 bi = box[best.pos];
-        const double ix1 = bi.x, iy1 = bi.y, ix2 = bi.z, iy2 = bi.w;
-        const double ai = (ix2 - ix1) * (iy2 - iy1);
+        const typename Box::Winner bi = Box::winner(box[best.pos]);
         for (int p = tid; p < m; p += kT) {
             if (p == best.pos) {
                 final_score[base + best.idx] = best.score;
@@ -206,14 +256,7 @@ __global__ __launch_bounds__(kT) void soft_nms_class_kernel(const float* __restr
                 continue;
             }
             if (score[p] == -INFINITY) continue;
-            const float4 bj = box[p];
-            const double jx1 = bj.x, jy1 = bj.y, jx2 = bj.z, jy2 = bj.w;
-            const double iw = fmin(ix2, jx2) - fmax(ix1, jx1), ih = fmin(iy2, jy2) - fmax(iy1, jy1);
-            double iou = 0.0;
-            if (iw > 0.0 && ih > 0.0) {
-                const double inter = iw * ih, ua = (ai + (jx2 - jx1) * (jy2 - jy1)) - inter;
-                if (ua > 0.0) iou = inter / ua;
-            }
+            const double iou = Box::iou(bi, box[p]);
             score[p] = score[p] * exp(-(iou * iou) / 0.5);
         }
         __syncthreads();                              // the scores of this round before the next arg-max; wbest reusable
@@ -222,6 +265,7 @@ __global__ __launch_bounds__(kT) void soft_nms_class_kernel(const float* __restr
 
 // Stage 2: one workgroup per image; rank of every emitted candidate by (score desc, class asc, index asc), by counting.
 constexpr int kT2 = 1024;
+template <class Box>
 __global__ __launch_bounds__(kT2) void soft_nms_order_kernel(
     const float* __restrict__ boxes, const int* __restrict__ classes, const float* __restrict__ kps,
     const int* __restrict__ ncand, const double* __restrict__ final_score, float* __restrict__ out_boxes,
@@ -255,7 +299,7 @@ __global__ __launch_bounds__(kT2) void soft_nms_order_kernel(
         }
         if (rank >= max_det) continue;
         const size_t row = (size_t)b * max_det + rank;
-        *reinterpret_cast<float4*>(out_boxes + row * 4) = *reinterpret_cast<const float4*>(boxes + (base + i) * 4);
+        Box::store(out_boxes, row, Box::load(boxes, base + i));
         const float sf = (float)s;
         out_scores[row] = sf;
         out_classes[row] = c;
@@ -264,13 +308,41 @@ __global__ __launch_bounds__(kT2) void soft_nms_order_kernel(
     }
     for (int r = min(emitted, max_det) + tid; r < max_det; r += kT2) {
         const size_t row = (size_t)b * max_det + r;
-        *reinterpret_cast<float4*>(out_boxes + row * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        Box::store(out_boxes, row, Box::zero());
         out_scores[row] = 0.0f;
         out_classes[row] = -1;
         for (int q = 0; q < 2 * J; ++q) out_kps[row * 2 * J + q] = 0.0f;
     }
     above = block_sum(above, red);
     if (tid == 0) counts[b] = above;
+}
+
+// Both entries: the checks, the two launches.
+template <class Box>
+int soft_nms_merge(const char* who, const float* boxes, const float* scores, const int* classes, const float* kps,
+                   const int* ncand, float* out_boxes, float* out_scores, int* out_classes, float* out_kps, int* counts,
+                   int B, int N, int C, int J, int max_detections, float threshold, void* workspace, size_t workspace_bytes,
+                   cnuda_stream_t stream) {
+    CNUDA_REQUIRE(out_boxes && out_scores && out_classes && counts, "%s: null pointer", who);
+    CNUDA_REQUIRE(B > 0 && N >= 0 && C > 0 && max_detections > 0, "%s: bad sizes", who);
+    CNUDA_REQUIRE(N <= kMaxCand, "%s: N=%d candidates per image exceed the supported %d", who, N, kMaxCand);
+    CNUDA_REQUIRE(N == 0 || (boxes && scores && classes), "%s: null pointer", who);
+    CNUDA_REQUIRE(J >= 0 && (J > 0 ? (out_kps && (kps || N == 0)) : (!kps && !out_kps)),
+                  "%s: kps and out_kps are given exactly when J > 0 (J=%d)", who, J);
+    CNUDA_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)out_boxes & 15) == 0,
+                  "%s: boxes and out_boxes must be 16-byte aligned", who);
+    CNUDA_REQUIRE(workspace && workspace_bytes >= (size_t)B * N * sizeof(double) + 256, "%s: workspace too small", who);
+    double* final_score = reinterpret_cast<double*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    hipStream_t st = (hipStream_t)stream;
+    if (N > 0) {
+        CNUDA_LAUNCH(soft_nms_class_kernel<Box>, dim3(B * C), dim3(kT), 0, st, boxes, scores, classes, ncand, final_score,
+                     N, C);
+        const int rc = check_launch(who);
+        if (rc) return rc;
+    }
+    CNUDA_LAUNCH(soft_nms_order_kernel<Box>, dim3(B), dim3(kT2), 0, st, boxes, classes, kps, ncand, final_score, out_boxes,
+                 out_scores, out_classes, out_kps, counts, N, C, J, max_detections, threshold);
+    return check_launch(who);
 }
 
 }  // namespace
@@ -329,24 +401,17 @@ extern "C" int cnuda_soft_nms_merge(const float* boxes, const float* scores, con
                                     const int* ncand, float* out_boxes, float* out_scores, int* out_classes,
                                     float* out_kps, int* counts, int B, int N, int C, int J, int max_detections,
                                     float threshold, void* workspace, size_t workspace_bytes, cnuda_stream_t stream) {
-    CNUDA_REQUIRE(out_boxes && out_scores && out_classes && counts, "cnuda_soft_nms_merge: null pointer");
-    CNUDA_REQUIRE(B > 0 && N >= 0 && C > 0 && max_detections > 0, "cnuda_soft_nms_merge: bad sizes");
-    CNUDA_REQUIRE(N <= kMaxCand, "cnuda_soft_nms_merge: N=%d candidates per image exceed the supported %d", N, kMaxCand);
-    CNUDA_REQUIRE(N == 0 || (boxes && scores && classes), "cnuda_soft_nms_merge: null pointer");
-    CNUDA_REQUIRE(J >= 0 && (J > 0 ? (out_kps && (kps || N == 0)) : (!kps && !out_kps)),
-                  "cnuda_soft_nms_merge: kps and out_kps are given exactly when J > 0 (J=%d)", J);
-    CNUDA_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)out_boxes & 15) == 0,
-                  "cnuda_soft_nms_merge: boxes and out_boxes must be 16-byte aligned");
-    CNUDA_REQUIRE(workspace && workspace_bytes >= (size_t)B * N * sizeof(double) + 256,
-                  "cnuda_soft_nms_merge: workspace too small");
-    double* final_score = reinterpret_cast<double*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    hipStream_t st = (hipStream_t)stream;
-    if (N > 0) {
-        CNUDA_LAUNCH(soft_nms_class_kernel, dim3(B * C), dim3(kT), 0, st, boxes, scores, classes, ncand, final_score, N, C);
-        const int rc = check_launch("cnuda_soft_nms_merge(stage 1)");
-        if (rc) return rc;
-    }
-    CNUDA_LAUNCH(soft_nms_order_kernel, dim3(B), dim3(kT2), 0, st, boxes, classes, kps, ncand, final_score, out_boxes,
-                 out_scores, out_classes, out_kps, counts, N, C, J, max_detections, threshold);
-    return check_launch("cnuda_soft_nms_merge(stage 2)");
+    return soft_nms_merge<AxisBox>("cnuda_soft_nms_merge", boxes, scores, classes, kps, ncand, out_boxes, out_scores,
+                                   out_classes, out_kps, counts, B, N, C, J, max_detections, threshold, workspace,
+                                   workspace_bytes, stream);
+}
+
+extern "C" int cnuda_soft_nms_merge_rotated(const float* boxes, const float* scores, const int* classes, const float* kps,
+                                            const int* ncand, float* out_boxes, float* out_scores, int* out_classes,
+                                            float* out_kps, int* counts, int B, int N, int C, int J, int max_detections,
+                                            float threshold, void* workspace, size_t workspace_bytes,
+                                            cnuda_stream_t stream) {
+    return soft_nms_merge<QuadBox>("cnuda_soft_nms_merge_rotated", boxes, scores, classes, kps, ncand, out_boxes,
+                                   out_scores, out_classes, out_kps, counts, B, N, C, J, max_detections, threshold,
+                                   workspace, workspace_bytes, stream);
 }

@@ -13,6 +13,10 @@ ranges); grouping, sorting and COCOeval's accumulate / the reference's summary a
 Differences from the reference, all documented in README.md:
   * the mask of a rotated box is the project's own convex fill (utils/image.py::_fill_convex_poly on the
     `rotate_bbox` vertices), not cv2.fillPoly; the two have not been compared;
+  * `rotated_iou = 'polygon'` (an attribute, default 'mask': the path above) measures rotated boxes without masks: the
+    exact float64 IoU of the two polygons on the untruncated vertices (`utils.box.rotate_bboxes_float`,
+    `cnuda_eval_iou_quads`), the polygon areas for COCO's area ranges, one launch, no workspace and no limit on the
+    image size;
   * an image id repeated within one evaluation raises ValueError (the reference merges the two images' annotations);
   * per-class values stay float64 (the reference rounds them to float32 before the mean over classes);
   * `num_workers` is accepted and unused (no pool); keypoints are ignored here, as in the reference (their metrics are
@@ -23,12 +27,13 @@ import numpy as np
 import torch
 
 import hip_runtime as hr
-from utils.box import rotate_bboxes
+from utils.box import rotate_bboxes, rotate_bboxes_float
 
 IOU_THRESHOLDS = np.linspace(0.5, 0.95, 10)
 RECALL_THRESHOLDS = np.linspace(0.0, 1.0, 101)
 MAX_DETECTIONS = (1, 10, 100)
 AREA_RANGES = np.array([[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]], dtype=np.float64)
+ROTATED_IOU_MODES = ('mask', 'polygon')
 _VERTEX_LIMIT = 1 << 24          # vertices are clamped to +-2^24 pixels: the kernels' fixed-point arithmetic stays in 64 bits
 
 # (mean name, per-class name, precision?, IoU threshold index or None, area range, detection limit): the reference's
@@ -173,6 +178,7 @@ class Evaluator:
         self.classes = None
         self.score_threshold = score_threshold
         self.use_rotated_boxes = False
+        self.rotated_iou = 'mask'            # how rotated boxes overlap: 'mask' (rasterised row spans) or 'polygon' (exact)
         self.num_workers = None
         self.existent_labels = {}
         self.ids = []
@@ -239,6 +245,8 @@ class Evaluator:
 
     def add_batch(self, pred_boxes, pred_classes, pred_scores, gt_boxes, gt_classes, gt_ids, gt_areas, image_shape,
                   pred_kps=None, gt_kps=None):
+        if self.rotated_iou not in ROTATED_IOU_MODES:
+            raise ValueError("Evaluator.rotated_iou must be one of %s, got %r" % (ROTATED_IOU_MODES, self.rotated_iou))
         B = len(gt_ids)
         H, W = int(image_shape[1]), int(image_shape[2])
         image_ids, det_src, gt_src, groups, keys = self._group(pred_classes, pred_scores, gt_classes, gt_ids)
@@ -250,7 +258,13 @@ class Evaluator:
         L, st = hr.lib(), hr.stream()
         d_groups = up(groups)
         iou = torch.empty(max(npairs, 1), dtype=torch.float64, device=dev)
-        if self.use_rotated_boxes:
+        if self.use_rotated_boxes and self.rotated_iou == 'polygon':
+            d_quads = up(rotate_bboxes_float(np.concatenate([det_boxes, gt_boxes_])))
+            area = torch.empty(max(nd + ngt, 1), dtype=torch.float64, device=dev)
+            hr.check(L.cnuda_eval_iou_quads(hr.ptr(d_quads), hr.ptr(d_groups), len(groups), nd, ngt, npairs, hr.ptr(iou),
+                                            hr.ptr(area), st), 'eval_iou_quads')
+            det_area, gt_area = area[:nd], area[nd:nd + ngt]
+        elif self.use_rotated_boxes:
             verts = np.clip(rotate_bboxes(np.concatenate([det_boxes, gt_boxes_])), -_VERTEX_LIMIT, _VERTEX_LIMIT)
             d_verts = up(verts.astype(np.int32))
             rows = torch.empty((max(nd + ngt, 1), 2), dtype=torch.int32, device=dev)

@@ -84,6 +84,7 @@ class _Sig:
     cnuda_eval_box_spans = (_I, [_P, _I, _I, _I, _P, _P] + _WS)
     cnuda_eval_iou_rotated = (_I, [_P, _I, _I, _I, _LL, _P, _P, _I, _P] + _WS)
     cnuda_eval_iou_axis = (_I, [_P, _P, _P, _I, _I, _I, _LL, _P, _P])
+    cnuda_eval_iou_quads = (_I, [_P, _P, _I, _I, _I, _LL, _P, _P, _P])
     cnuda_eval_match = (_I, [_P, _P, _I, _P, _P, _I, _I, _LL, _P, _I, _P, _P, _P, _P])
     cnuda_eval_match_flagged = (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _LL, _P, _I, _P, _P, _P, _P])
     cnuda_eval_oks = (_I, [_P] * 6 + [_I, _P, _I, _I, _I, _LL, _P, _P, _P, _P])
@@ -179,6 +180,8 @@ class _Sig:
     cnuda_project_detections = (_I, [_P] * 9 + [_I] * 4 + [_F, _F, _I, _I, _P])
     cnuda_predict_workspace_bytes = (c_size_t, [_I, _I])
     cnuda_soft_nms_merge = (_I, [_P] * 10 + [_I] * 5 + [_F] + _WS)
+    cnuda_soft_nms_merge_rotated = (_I, [_P] * 10 + [_I] * 5 + [_F] + _WS)
+    cnuda_quad_iou_pairs = (_I, [_P] * 5 + [_I] * 3 + [_P])
     cnuda_fda_workspace_bytes = (c_size_t, [_I] * 4)
     cnuda_fda_source_to_target = (_I, [_P] * 4 + [_I] * 4 + _WS)
     cnuda_adam_step = (_I, [_P] * 4 + [_LL] + [_F] * 5 + [_I, _P])

@@ -1665,3 +1665,26 @@ def dense_teacher_loss(hm, wh, teacher_hm, teacher_wh, tau, count, *, mirror, hm
         raise RuntimeError("dense_teacher_loss: tau must be contiguous float32 and count contiguous int32")
     return _DenseTeacher.apply(hm, wh, teacher_hm, teacher_wh, tau, count, 1 if mirror else 0, float(hm_weight),
                                float(wh_weight))
+
+
+def rotated_iou(a, b, return_areas=False):
+    """The exact IoU of every pair of two sets of convex quadrilaterals per image, in float64 (csrc/polyiou.cuh;
+    include/centernet_uda_hip.h, "Rotated IoU").  a [B, N, 4, 2], b [B, M, 4, 2] float32 (x, y) vertices in either
+    winding, as predict.project_detections and utils.box.rotate_bboxes_float give them -> iou [B, N, M] float64; with
+    `return_areas` also (area_a [B, N], area_b [B, M]) float64.  Subject a, clipper b; a quad with a coordinate that is
+    not finite or without area overlaps nothing; a quad that is not convex gives a finite value in [0, 1] that is
+    otherwise unspecified.  One launch, no gradient, no read-back."""
+    require_gpu(a, b)
+    a, b = f32c(a.detach()), f32c(b.detach())
+    if a.dim() != 4 or b.dim() != 4 or tuple(a.shape[2:]) != (4, 2) or tuple(b.shape[2:]) != (4, 2) \
+            or a.shape[0] != b.shape[0] or a.shape[0] < 1:
+        raise RuntimeError("rotated_iou: a must be [B, N, 4, 2] and b [B, M, 4, 2] with B >= 1, got %s and %s"
+                           % (tuple(a.shape), tuple(b.shape)))
+    B, N, M = a.shape[0], a.shape[1], b.shape[1]
+    iou = torch.empty((B, N, M), dtype=torch.float64, device=a.device)
+    area_a = torch.empty((B, N), dtype=torch.float64, device=a.device) if return_areas else None
+    area_b = torch.empty((B, M), dtype=torch.float64, device=a.device) if return_areas else None
+    check(lib().cnuda_quad_iou_pairs(ptr(a) if N else None, ptr(b) if M else None, ptr(iou) if N * M else None,
+                                     ptr(area_a) if N else None, ptr(area_b) if M else None, B, N, M, stream()),
+          'quad_iou_pairs')
+    return (iou, area_a, area_b) if return_areas else iou

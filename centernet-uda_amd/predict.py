@@ -2,7 +2,7 @@
 augmentation (DESIGN.md, "Prediction").
 
     python predict.py RUN_DIR IMAGE_OR_DIR_OR_GLOB... [--out results.json] [--best] [--teacher]
-        [--flip] [--scales 0.75,1,1.25] [--soft-nms] [--score-threshold T]
+        [--flip] [--scales 0.75,1,1.25] [--soft-nms] [--polygon-nms] [--score-threshold T]
         [--batch-size N] [--num-workers N] [--gpu I] [--annotation-file F]
         [--flip-pairs 1-2,3-4]
 
@@ -20,8 +20,10 @@ Per scale the images are stretched to the network size by `augment_images(Augmen
 `prepare_input` (the validation loader's resize: no aspect-preserving padding), the mirrors -- with `flip` -- ride in
 the same 2B forward and `cnuda_tta_merge` folds the two halves of the head maps, `decode_detection` picks the K best and
 `cnuda_project_detections` maps them through the float64 inverse of the resize matrix into source pixels.  Several
-scales (or `soft_nms=True`) end in `cnuda_soft_nms_merge`.  The call reads nothing back; apart from the kernels named
-here no torch compute kernel runs between the uint8 batch and the result.
+scales (or `soft_nms=True`) end in `cnuda_soft_nms_merge`; a rotated model takes `soft_nms='polygon'` instead, alone or
+with several scales, and ends in `cnuda_soft_nms_merge_rotated` (the same merge on the projected vertices, with the
+exact polygon IoU).  The call reads nothing back; apart from the kernels named here no torch compute kernel runs
+between the uint8 batch and the result.
 """
 import argparse
 import glob as globlib
@@ -256,39 +258,55 @@ def project_detections(dets, kps, matrix, sizes, threshold, rotated=False, scale
     return out
 
 
+def _soft_nms_merge(who, rotated, boxes, scores, classes, kps, num_classes, max_detections, threshold, ncand, out):
+    """the checks and the call of both merges; a box is [4] or, rotated, [4, 2]"""
+    hr.require_gpu(boxes, scores, classes, kps, ncand)
+    boxes, scores = hr.f32c(boxes), hr.f32c(scores)
+    kps = None if kps is None else hr.f32c(kps)
+    box = (4, 2) if rotated else (4,)
+    if boxes.dim() != 2 + len(box) or tuple(boxes.shape[2:]) != box or boxes.shape[0] < 1:
+        raise RuntimeError("%s: boxes must be [B, N, %s], got %s" % (who, ', '.join(map(str, box)), tuple(boxes.shape)))
+    B, N = boxes.shape[:2]
+    if N > MAX_CANDIDATES:
+        raise RuntimeError("%s: %d candidates per image exceed the supported %d" % (who, N, MAX_CANDIDATES))
+    if tuple(scores.shape) != (B, N) or tuple(classes.shape) != (B, N) or classes.dtype != torch.int32:
+        raise RuntimeError("%s: scores must be float32 [B, N] and classes int32 [B, N]" % who)
+    classes = classes.contiguous()
+    J = 0 if kps is None else kps.shape[2]
+    if kps is not None and (kps.dim() != 4 or tuple(kps.shape[:2]) != (B, N) or kps.shape[3] != 2 or J == 0):
+        raise RuntimeError("%s: kps must be [B, N, J, 2], got %s" % (who, tuple(kps.shape)))
+    if ncand is not None and (ncand.dtype != torch.int32 or tuple(ncand.shape) != (B,) or not ncand.is_contiguous()):
+        raise RuntimeError("%s: ncand must be a contiguous int32 [B]" % who)
+    K = int(max_detections)
+    if out is None:
+        out = _result_buffers(B, K, J, rotated, boxes.device)
+    if tuple(out['boxes'].shape) != (B, K) + box or (J and tuple(out['kps'].shape) != (B, K, J, 2)):
+        raise RuntimeError("%s: out does not hold %d rows of %d images" % (who, K, B))
+    L = hr.lib()
+    ws = hr.workspace(L.cnuda_predict_workspace_bytes(B, N), boxes.device)
+    merge = L.cnuda_soft_nms_merge_rotated if rotated else L.cnuda_soft_nms_merge
+    hr.check(merge(
+        hr.ptr(boxes) if N else None, hr.ptr(scores) if N else None, hr.ptr(classes) if N else None,
+        hr.ptr(kps) if J and N else None, hr.ptr(ncand), hr.ptr(out['boxes']), hr.ptr(out['scores']),
+        hr.ptr(out['classes']), hr.ptr(out['kps']) if J else None, hr.ptr(out['counts']), B, N, int(num_classes), J, K,
+        float(np.float32(threshold)), hr.ptr(ws), ws.numel(), hr.stream()), who)
+    return out
+
+
 def soft_nms_merge(boxes, scores, classes, kps, num_classes, max_detections, threshold, ncand=None, out=None):
     """Gaussian soft-NMS over boxes [B, N, 4], scores [B, N], classes [B, N] int32 (kps [B, N, J, 2] or None) per
     (image, class), then the per-image order (include/centernet_uda_hip.h).  ncand: int32 [B] device tensor, the
     candidates in use per image (None: all N).  -> dict of boxes [B, max_detections, 4], scores, classes, counts (kps)."""
-    hr.require_gpu(boxes, scores, classes, kps, ncand)
-    boxes, scores = hr.f32c(boxes), hr.f32c(scores)
-    kps = None if kps is None else hr.f32c(kps)
-    if boxes.dim() != 3 or boxes.shape[2] != 4 or boxes.shape[0] < 1:
-        raise RuntimeError("soft_nms_merge: boxes must be [B, N, 4], got %s" % (tuple(boxes.shape),))
-    B, N, _ = boxes.shape
-    if N > MAX_CANDIDATES:
-        raise RuntimeError("soft_nms_merge: %d candidates per image exceed the supported %d" % (N, MAX_CANDIDATES))
-    if tuple(scores.shape) != (B, N) or tuple(classes.shape) != (B, N) or classes.dtype != torch.int32:
-        raise RuntimeError("soft_nms_merge: scores must be float32 [B, N] and classes int32 [B, N]")
-    classes = classes.contiguous()
-    J = 0 if kps is None else kps.shape[2]
-    if kps is not None and (kps.dim() != 4 or tuple(kps.shape[:2]) != (B, N) or kps.shape[3] != 2 or J == 0):
-        raise RuntimeError("soft_nms_merge: kps must be [B, N, J, 2], got %s" % (tuple(kps.shape),))
-    if ncand is not None and (ncand.dtype != torch.int32 or tuple(ncand.shape) != (B,) or not ncand.is_contiguous()):
-        raise RuntimeError("soft_nms_merge: ncand must be a contiguous int32 [B]")
-    K = int(max_detections)
-    if out is None:
-        out = _result_buffers(B, K, J, False, boxes.device)
-    if tuple(out['boxes'].shape) != (B, K, 4) or (J and tuple(out['kps'].shape) != (B, K, J, 2)):
-        raise RuntimeError("soft_nms_merge: out does not hold %d rows of %d images" % (K, B))
-    L = hr.lib()
-    ws = hr.workspace(L.cnuda_predict_workspace_bytes(B, N), boxes.device)
-    hr.check(L.cnuda_soft_nms_merge(
-        hr.ptr(boxes) if N else None, hr.ptr(scores) if N else None, hr.ptr(classes) if N else None,
-        hr.ptr(kps) if J and N else None, hr.ptr(ncand), hr.ptr(out['boxes']), hr.ptr(out['scores']),
-        hr.ptr(out['classes']), hr.ptr(out['kps']) if J else None, hr.ptr(out['counts']), B, N, int(num_classes), J, K,
-        float(np.float32(threshold)), hr.ptr(ws), ws.numel(), hr.stream()), 'soft_nms_merge')
-    return out
+    return _soft_nms_merge('soft_nms_merge', False, boxes, scores, classes, kps, num_classes, max_detections, threshold,
+                           ncand, out)
+
+
+def soft_nms_merge_rotated(boxes, scores, classes, kps, num_classes, max_detections, threshold, ncand=None, out=None):
+    """`soft_nms_merge` over rotated boxes: boxes [B, N, 4, 2] vertices (x, y) as `project_detections(rotated=True)`
+    writes them, overlap = the exact polygon IoU of the round's winner and the candidate (hip_runtime.ops.rotated_iou).
+    -> dict of boxes [B, max_detections, 4, 2], scores, classes, counts (kps)."""
+    return _soft_nms_merge('soft_nms_merge_rotated', True, boxes, scores, classes, kps, num_classes, max_detections,
+                           threshold, ncand, out)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -296,7 +314,9 @@ def soft_nms_merge(boxes, scores, classes, kps, num_classes, max_detections, thr
 # ---------------------------------------------------------------------------------------------------------------------
 class Predictor:
     """backend: a CenterNet backend of backends/ (on the GPU, or moved there by the caller); input_size = (width,
-    height) of scale 1.  soft_nms=None: only with more than one scale (the published behaviour); True: always."""
+    height) of scale 1.  soft_nms=None: only with more than one scale (the published behaviour); True: always;
+    'polygon': always, on the vertices of a rotated model with the exact polygon IoU -- the one form a rotated model
+    takes, and what opens several scales to it."""
 
     def __init__(self, backend, input_size, *, max_detections=150, score_threshold=0.1, rotated=False, mean=MEAN,
                  std=STD, flip=False, scales=(1.0,), soft_nms=None, flip_pairs=None, nms=3):
@@ -309,11 +329,17 @@ class Predictor:
             raise ValueError("scales must be a sequence of positive numbers, got %r" % (scales,)) from None
         if not scales or not all(s > 0 and math.isfinite(s) for s in scales):
             raise ValueError("scales must be a non-empty sequence of positive numbers, got %r" % (scales,))
+        polygon = isinstance(soft_nms, str)
+        if polygon and soft_nms != 'polygon':
+            raise ValueError("soft_nms must be None, a bool or 'polygon', got %r" % (soft_nms,))
+        if polygon and not rotated:
+            raise ValueError("soft_nms='polygon' merges the vertices of a rotated model; this one is axis-aligned "
+                             "(soft_nms=True is its soft-NMS)")
         use_soft = len(scales) > 1 if soft_nms is None else bool(soft_nms)
-        if rotated and len(scales) > 1:
+        if rotated and len(scales) > 1 and not polygon:
             raise ValueError("scales: a rotated model is predicted at one scale (there is no rotated soft-NMS), got %r"
                              % (scales,))
-        if rotated and use_soft:
+        if rotated and use_soft and not polygon:
             raise ValueError("soft_nms is not available for rotated models")
         if len(scales) > 1 and not use_soft:
             raise ValueError("soft_nms=False cannot merge %d scales" % len(scales))
@@ -378,14 +404,15 @@ class Predictor:
         if self.flip and J and self._perm_dev is None:
             self._perm_dev = torch.from_numpy(self.perm).pin_memory().to(images.device, non_blocking=True)
         out = _result_buffers(B, K, J, self.rotated, images.device)
-        cand = _result_buffers(B, S * K, J, False, images.device) if self.soft_nms else out
+        cand = _result_buffers(B, S * K, J, self.rotated, images.device) if self.soft_nms else out
         for s in range(S):
             dets, kps = self._scale(images, params[s], B)
             project_detections(dets, kps, matrices[s], d_sizes, self.score_threshold, self.rotated,
                                scale=self.down_ratio, out=cand, first=s * K)
         if self.soft_nms:
-            soft_nms_merge(cand['boxes'], cand['scores'], cand['classes'], cand.get('kps'), self.num_classes, K,
-                           self.score_threshold, out=out)
+            merge = soft_nms_merge_rotated if self.rotated else soft_nms_merge
+            merge(cand['boxes'], cand['scores'], cand['classes'], cand.get('kps'), self.num_classes, K,
+                  self.score_threshold, out=out)
         return out
 
 
@@ -481,6 +508,8 @@ def parse_args(argv=None):
     ap.add_argument('--flip', action='store_true', help="average with the left-right mirror")
     ap.add_argument('--scales', type=_scales, default=(1.0,), help="comma-separated test scales (default: 1)")
     ap.add_argument('--soft-nms', action='store_true', help="soft-NMS for a single scale too")
+    ap.add_argument('--polygon-nms', action='store_true',
+                    help="rotated models: soft-NMS on the vertices with the exact polygon IoU (allows several scales)")
     ap.add_argument('--score-threshold', type=float, default=None, help="default: the run's score_threshold")
     ap.add_argument('--batch-size', type=int, default=None, help="default: the run's batch_size")
     ap.add_argument('--num-workers', type=int, default=None, help="decoding threads, at most 16 (default: the run's)")
@@ -488,6 +517,13 @@ def parse_args(argv=None):
     ap.add_argument('--annotation-file', default=None, help="COCO file whose file_name -> id table names the images")
     ap.add_argument('--flip-pairs', type=_pairs, default=None, help="mirrored joint pairs of a keypoint model: 1-2,3-4")
     return ap.parse_args(argv)
+
+
+def _soft_nms_setting(args):
+    """Predictor's `soft_nms` of the command line: --polygon-nms wins over --soft-nms"""
+    if getattr(args, 'polygon_nms', False):
+        return 'polygon'
+    return True if args.soft_nms else None
 
 
 def settings_from_run(args):
@@ -519,7 +555,7 @@ def settings_from_run(args):
                                  else args.score_threshold),
         'rotated': bool(spec['params'].get('rotated_boxes', False)),
         'mean': tuple(normalize.get('mean', MEAN)), 'std': tuple(normalize.get('std', STD)),
-        'flip': bool(args.flip), 'scales': tuple(args.scales), 'soft_nms': True if args.soft_nms else None,
+        'flip': bool(args.flip), 'scales': tuple(args.scales), 'soft_nms': _soft_nms_setting(args),
         'flip_pairs': args.flip_pairs,
     }
     return {'backend': spec, 'predictor': predictor, 'use_last': not args.best, 'gpu': int(gpu or 0),

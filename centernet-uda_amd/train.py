@@ -198,7 +198,10 @@ def run(cfg):
     evaluators = []
     for e in cfg.evaluation:
         params = {'score_threshold': cfg.score_threshold, **(cfg.evaluation[e] or {})}
+        rotated_iou = params.pop('rotated_iou', None)          # evaluation.coco.rotated_iou: 'mask' or 'polygon'
         e = import_module('evaluation.%s' % e).Evaluator(**params)
+        if rotated_iou is not None:
+            e.rotated_iou = rotated_iou
         e.classes = tensorboard_logger.classes
         e.num_workers = cfg.num_workers
         e.use_rotated_boxes = cfg.model.backend.params.rotated_boxes

@@ -348,6 +348,10 @@ int cnuda_dcn_v2_psroi_pooling_backward(const float* grad_output, const float* i
  *   e_j = (dx_j^2 + dy_j^2) / var_j / (area + 2^-52) / 2; oks = sum_j exp(-e_j) / n in ascending j, n = k1 or J.
  *   The same call writes det_area [num_det] double, (max x - min x) * (max y - min y) over a detection's J joints (the
  *   area COCO's loadRes gives a keypoint result), and gt_flags [num_gt] bytes, 1 where k1 == 0.  No fused multiply-add.
+ * cnuda_eval_iou_quads: the rotated mode without masks.  quads [num_det + num_gt, 4, 2] float32 (x, y) vertices, the
+ *   detections first; iou in the pair layout above is cnuda_quad_iou_pairs' exact polygon IoU with the detection as
+ *   subject and the ground truth as clipper; area [num_det + num_gt] double: the polygon areas, written for every box
+ *   whatever the groups say.  One launch, no workspace, no image size.
  * Integers and doubles only, no floating-point atomics: bit-stable.  Nothing synchronises the stream.
  * ---------------------------------------------------------------------- */
 size_t cnuda_eval_workspace_bytes(int num_boxes, int H);
@@ -358,6 +362,8 @@ int cnuda_eval_iou_rotated(const int* groups, int num_groups, int num_det, int n
                            void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
 int cnuda_eval_iou_axis(const float* det_boxes, const float* gt_boxes, const int* groups, int num_groups,
                         int num_det, int num_gt, long long num_pairs, double* iou, cnuda_stream_t stream);
+int cnuda_eval_iou_quads(const float* quads, const int* groups, int num_groups, int num_det, int num_gt,
+                         long long num_pairs, double* iou, double* area, cnuda_stream_t stream);
 int cnuda_eval_match(const double* iou, const int* groups, int num_groups, const double* det_area,
                      const double* gt_area, int num_det, int num_gt, long long num_pairs,
                      const double* thresholds, int num_thresholds, const double* area_ranges,
@@ -941,6 +947,35 @@ int cnuda_soft_nms_merge(const float* boxes, const float* scores, const int* cla
                          const int* ncand, float* out_boxes, float* out_scores, int* out_classes, float* out_kps,
                          int* counts, int B, int N, int C, int J, int max_detections, float threshold,
                          void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+/* cnuda_soft_nms_merge on rotated boxes: boxes [B,N,4,2] and out_boxes [B,max_detections,4,2] are quadrilaterals (x, y)
+ * as cnuda_project_detections writes them, and iou = cnuda_quad_iou_pairs' exact polygon IoU with the round's winner as
+ * subject and the candidate as clipper.  Everything else -- the two stages, the (score, class, index) keys, the 1e-3
+ * stop, the decay, ncand, kps, counts, the candidate limit, the workspace -- is cnuda_soft_nms_merge's (the same two
+ * kernels on another box record; the 2048 quads of a class sit in 64 KiB of LDS beside the scores: 88 KiB static). */
+int cnuda_soft_nms_merge_rotated(const float* boxes, const float* scores, const int* classes, const float* kps,
+                                 const int* ncand, float* out_boxes, float* out_scores, int* out_classes,
+                                 float* out_kps, int* counts, int B, int N, int C, int J, int max_detections,
+                                 float threshold, void* workspace, size_t workspace_bytes, cnuda_stream_t stream);
+
+/* -------------------------------------------------------------------------
+ * Rotated IoU (hip_runtime.ops.rotated_iou; csrc/polyiou.cuh, csrc/polyiou.hip; DESIGN.md, "Rotated IoU"): the exact
+ * IoU of two convex quadrilaterals in float64.  a [B,N,4,2], b [B,M,4,2] float32 (x, y) vertices in either winding;
+ * iou [B,N,M] double; area_a [B,N], area_b [B,M] double, each may be NULL.  Per pair, subject a, clipper b:
+ *   1. a coordinate that is not finite: iou 0 (and that quad's area 0);
+ *   2. a2 = sum_{i=0..3} (x_i y_{i+1} - x_{i+1} y_i), ascending i into one accumulator that starts at 0, indices mod 4;
+ *      a2 < 0: the vertex order becomes 3, 2, 1, 0 and a2 is negated; area = a2 / 2; a2 of a or of b not > 0: iou 0;
+ *   3. Sutherland-Hodgman over the edges k = 0..3 of b, a = b_k, e = b_{k+1} - a, d(p) = e.x (p.y - a.y) - e.y (p.x - a.x):
+ *      for the vertices p_j of the current polygon with successor q, emit p when d(p) >= 0, then p + t (q - p) with
+ *      t = d(p) / (d(p) - d(q)) when d(p) and d(q) have strictly opposite signs; an empty polygon ends the clipping;
+ *   4. i2 = the sum of 2 over the result (0 below three vertices), clamped to [0, min(a2_a, a2_b)];
+ *      u2 = a2_a + a2_b - i2; iou = i2 / u2 when u2 > 0, else 0.
+ * Doubles, + - * / and comparisons only, no fused multiply-add: the bits of the same steps in any IEEE float64
+ * arithmetic (tests/polyiou_oracle.py).  A convex subject never exceeds 8 vertices; a quad that is not convex or
+ * crosses itself gives a finite value in [0, 1] that is otherwise unspecified (vertices past the eighth are dropped).
+ * One launch, no workspace, no atomics.  B > 0; N or M may be 0.
+ * ---------------------------------------------------------------------- */
+int cnuda_quad_iou_pairs(const float* a, const float* b, double* iou, double* area_a, double* area_b,
+                         int B, int N, int M, cnuda_stream_t stream);
 
 /* -------------------------------------------------------------------------
  * Mean teacher (uda/mean_teacher.py; csrc/teacher.hip; DESIGN.md, "Mean teacher").  No reference counterpart.  No
