@@ -1,6 +1,8 @@
 // Exact IoU of two convex quadrilaterals in float64 ("Rotated IoU"): the one device function behind
 // cnuda_quad_iou_pairs, cnuda_eval_iou_quads (evalcoco.hip) and cnuda_soft_nms_merge_rotated (predict.hip), and what the
 // stand-alone host program of the tests (tests/polyiou_host.cpp) runs on the CPU.
+// Its clipping (steps 3 and 4, clipped_doubled_area) also gives cnuda_labels_transform (geomview.hip) the visible part of a
+// pseudo-label, with the output map's rectangle as the clipper.
 //
 // The definition is normative: the tests demand the bits of a Python float64 restatement (tests/polyiou_oracle.py).
 // Only + - * / and comparisons occur, every one rounded once: no fused multiply-add (the pragma below; the Makefile
@@ -96,12 +98,10 @@ CNUDA_HD inline void put(double (&ox)[kMaxVertices], double (&oy)[kMaxVertices],
 }
 }  // namespace detail
 
-CNUDA_HD inline QuadIou convex_quad_iou(Quad A, Quad B) {
-    QuadIou r = {0.0, 0.0, 0.0};
-    if (!finite(A) || !finite(B)) return r;
-    const double a2a = orient(A), a2b = orient(B);
-    r.area_a = a2a / 2.0, r.area_b = a2b / 2.0;
-    if (!(a2a > 0.0) || !(a2b > 0.0)) return r;
+// Steps 3 and 4's i2: the doubled area of A clipped by B, both counter-clockwise (orient) with doubled areas a2a, a2b > 0.
+// The one clipping routine of the library: convex_quad_iou below and the survivor filter of cnuda_labels_transform
+// (geomview.hip), whose clipper is the map's rectangle.
+CNUDA_HD inline double clipped_doubled_area(const Quad& A, const Quad& B, double a2a, double a2b) {
     double px[kMaxVertices], py[kMaxVertices];
 #pragma unroll
     for (int s = 0; s < kMaxVertices; ++s) px[s] = s < 4 ? A.x[s] : 0.0, py[s] = s < 4 ? A.y[s] : 0.0;
@@ -146,6 +146,16 @@ CNUDA_HD inline QuadIou convex_quad_iou(Quad A, Quad B) {
     if (i2 < 0.0) i2 = 0.0;
     if (i2 > a2a) i2 = a2a;
     if (i2 > a2b) i2 = a2b;
+    return i2;
+}
+
+CNUDA_HD inline QuadIou convex_quad_iou(Quad A, Quad B) {
+    QuadIou r = {0.0, 0.0, 0.0};
+    if (!finite(A) || !finite(B)) return r;
+    const double a2a = orient(A), a2b = orient(B);
+    r.area_a = a2a / 2.0, r.area_b = a2b / 2.0;
+    if (!(a2a > 0.0) || !(a2b > 0.0)) return r;
+    const double i2 = clipped_doubled_area(A, B, a2a, a2b);
     const double u2 = a2a + a2b - i2;
     r.iou = u2 > 0.0 ? i2 / u2 : 0.0;
     return r;

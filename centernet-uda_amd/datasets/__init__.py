@@ -10,4 +10,5 @@ from .augment import (AugmentParams, Augmentation, augment_images, build_batch, 
                       transform_points)
 from .prepare import prepare_input   # noqa: F401
 from .strong_view import StrongView, StrongViewParams   # noqa: F401  (the function: datasets.strong_view.strong_view)
+from .geometric_view import GeometricView, GeometricViewParams, warp_batch   # noqa: F401
 from .targets import encode_targets   # noqa: F401

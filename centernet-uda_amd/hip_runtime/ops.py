@@ -1586,6 +1586,58 @@ def pseudo_labels(dets, thresholds, map_width, *, rotated=False, mirror=False, m
     return out
 
 
+def transform_labels(labels, forward_map, map_h, map_w, *, rotated=False, min_size=0.0, min_visible=0.5):
+    """The pseudo-labels of `pseudo_labels` under a geometric view (cnuda_labels_transform; include/centernet_uda_hip.h,
+    "Geometric view").  labels: the dict `pseudo_labels` returns; forward_map [B, 6] (or [B, 2, 3]) float64, host or
+    device: the view's matrix at output-map resolution (datasets.geometric_view.GeometricViewParams.forward_map).
+    Rotated: the corners are mapped point by point; axis-aligned: the bounding box of the four mapped corners.  A row
+    survives iff both extents >= min_size, its area is positive and finite and at least `min_visible` of it lies inside
+    [0, map_w] x [0, map_h] (an exact convex clip in float64); an image with the identity matrix keeps every row.
+    -> a new dict with the same keys, dtypes and layout -- survivors first, in input order, unclipped, zeros behind them;
+    'counts' and 'kept' rewritten -- plus 'dropped' (0-dim float32: the mean number of rows removed per image).  The
+    input tensors are not written.  Two launches, no atomics, nothing read back."""
+    import numpy as np
+    key = 'corners' if rotated else 'boxes'
+    tail = (4, 2) if rotated else (4,)
+    if not isinstance(labels, dict) or any(k not in labels for k in (key, 'classes', 'counts')):
+        raise RuntimeError("transform_labels: labels must be the dict of pseudo_labels(rotated=%s) with '%s', 'classes' "
+                           "and 'counts'" % (bool(rotated), key))
+    geometry, classes, counts = labels[key], labels['classes'], labels['counts']
+    require_gpu(geometry, classes, counts)
+    if geometry.dim() != 2 + len(tail) or tuple(geometry.shape[2:]) != tail or geometry.numel() == 0 \
+            or geometry.dtype != torch.float64:
+        raise RuntimeError("transform_labels: %s must be a non-empty float64 [B, K, %s], got %s %s"
+                           % (key, ', '.join(map(str, tail)), geometry.dtype, tuple(geometry.shape)))
+    B, K = geometry.shape[:2]
+    if tuple(classes.shape) != (B, K) or tuple(counts.shape) != (B,) or classes.dtype != torch.int32 \
+            or counts.dtype != torch.int32:
+        raise RuntimeError("transform_labels: classes must be int32 [%d, %d] and counts int32 [%d], got %s %s and %s %s"
+                           % (B, K, B, classes.dtype, tuple(classes.shape), counts.dtype, tuple(counts.shape)))
+    if int(map_h) < 1 or int(map_w) < 1:
+        raise RuntimeError("transform_labels: map_h=%r, map_w=%r" % (map_h, map_w))
+    if not 0.0 <= float(min_visible) <= 1.0 or not float(min_size) == float(min_size):
+        raise RuntimeError("transform_labels: min_visible=%r outside [0, 1] or min_size=%r is NaN" % (min_visible, min_size))
+    dev = geometry.device
+    if isinstance(forward_map, torch.Tensor):
+        forward = forward_map.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    else:
+        host = np.ascontiguousarray(np.asarray(forward_map, dtype=np.float64).reshape(-1))
+        if not np.isfinite(host).all():
+            raise RuntimeError("transform_labels: forward_map must be finite")
+        forward = torch.from_numpy(host).to(dev)
+    if forward.numel() != 6 * B:
+        raise RuntimeError("transform_labels: forward_map must be [%d, 6], got %d values" % (B, forward.numel()))
+    geometry, classes, counts = geometry.contiguous(), classes.contiguous(), counts.contiguous()
+    out = {'classes': torch.empty_like(classes), 'counts': torch.empty_like(counts),
+           'kept': torch.empty((), dtype=torch.float32, device=dev), key: torch.empty_like(geometry),
+           'dropped': torch.empty((), dtype=torch.float32, device=dev)}
+    check(lib().cnuda_labels_transform(ptr(geometry), ptr(classes), ptr(counts), ptr(forward), ptr(out[key]),
+                                       ptr(out['classes']), ptr(out['counts']), ptr(out['kept']), ptr(out['dropped']),
+                                       B, K, 1 if rotated else 0, int(map_h), int(map_w), float(min_size),
+                                       float(min_visible), stream()), 'labels_transform')
+    return out
+
+
 # ---------------------------------------------------------------------------
 # Dense teacher (csrc/dense.hip; DESIGN.md, "Dense teacher")
 # ---------------------------------------------------------------------------

@@ -14,6 +14,7 @@ _PLUGINS = {
     'MeanTeacher': 'uda.mean_teacher',
     'WeakStrongTeacher': 'uda.mean_teacher',
     'DenseTeacher': 'uda.mean_teacher',
+    'GeometricTeacher': 'uda.mean_teacher',
 }
 __all__ = sorted(_PLUGINS)
 

@@ -167,10 +167,18 @@ class MeanTeacher(Model):
             H, W = hm.shape[2:]
             labels = ops.pseudo_labels(dets, self._thresholds, W, rotated=rotated, mirror=self.mirror_student,
                                        min_size=self.min_size)
+            labels = self.view_labels(labels, target_input, H, W, rotated)
             batch = encode_targets(labels.get('boxes'), labels['classes'], labels['counts'], hm.shape[1], H, W,
                                    corners=labels.get('corners'))
         batch['kept'] = labels['kept']
+        if 'dropped' in labels:
+            batch['dropped'] = labels['dropped']
         return batch
+
+    def view_labels(self, labels, target_input, map_h, map_w, rotated):
+        """The teacher's pseudo-labels as the student's view shows them: here the labels themselves (`pseudo_labels`
+        has mirrored them with `mirror_student`); GeometricTeacher: transformed and filtered."""
+        return labels
 
     def student_view(self, target_input):
         """What the student sees of the target batch the teacher labelled: the mirror with `mirror_student` (the
@@ -201,6 +209,8 @@ class MeanTeacher(Model):
             loss, stats = self.centernet_loss(dict(target_outputs), pseudo)
             stats = {'pseudo_' + k: v for k, v in stats.items()}
             stats['pseudo_boxes'] = pseudo['kept']
+            if 'dropped' in pseudo:
+                stats['pseudo_dropped'] = pseudo['dropped']
             return loss * self.pseudo_weight, stats
         return self.step_with_target_term(view, True, target_term)
 
@@ -250,14 +260,66 @@ class WeakStrongTeacher(MeanTeacher):
         self.strong_view = StrongView(strong_view)
 
     def student_view(self, target_input):
+        return self.strengthen(super().student_view(target_input))
+
+    def strengthen(self, x):
+        """The strong view of `x` under the parameters of step n = teacher_updates; never writes `x`."""
         import numpy as np
         from datasets.strong_view import strong_view
-        x = super().student_view(target_input)
         B, _, H, W = x.shape
         n = self.teacher_updates
         params = self.strong_view.sample(B, H, W, np.random.default_rng([int(self.cfg.seed), 0x57534B, n]),
                                          first_id=n * B)
         return strong_view(x, params, self.cfg.normalize.mean, self.cfg.normalize.std)
+
+
+class GeometricTeacher(WeakStrongTeacher):
+    """WeakStrongTeacher whose student also sees another GEOMETRY than the teacher labelled ("Geometric
+    view"): per image a rotation, an isotropic change of scale and a shift about the image centre, drawn by
+    datasets.geometric_view.GeometricView (`geometric_view`: its mapping; None: its defaults).  The teacher labels
+    `target_domain_input` as it is.  The student sees ONE bilinear warp of it by the inverse of A . F (A: the image's
+    similarity, F: the mirror with `mirror_student`, else the identity -- the mirror costs no launch of its own), then the
+    parent's strong view.  The pseudo-labels go the parent's way up to `ops.pseudo_labels(mirror=...)`, then through
+    `ops.transform_labels` with A at output-map resolution: a rotated-box model's corners are mapped point by point (any
+    angle, no loss), an axis-aligned model gets the bounding box of the mapped corners; a label survives when at least
+    `min_visible` of it lies inside the view and both extents reach `min_size`.  Statistics: the parent's, with
+    `pseudo_boxes` counted after the filter, plus `pseudo_dropped` (labels removed per image).
+
+    Step n (= teacher_updates) draws from np.random.default_rng([cfg.seed, 0x47454F, n]), a stream of its own: the strong
+    view's draws at step n are WeakStrongTeacher's, and a resumed run continues both.  With every component null (or
+    `p: 0`) the step is WeakStrongTeacher's bit for bit.  Burn-in, the EMA, checkpoints, evaluation and the keypoint
+    refusal are the parent's."""
+
+    def __init__(self, pseudo_weight, geometric_view=None, min_visible=0.5, strong_view=None, **mean_teacher_arguments):
+        super().__init__(pseudo_weight, strong_view=strong_view, **mean_teacher_arguments)
+        from datasets.geometric_view import GeometricView
+        if isinstance(min_visible, bool) or not isinstance(min_visible, (int, float)) or not 0.0 < float(min_visible) <= 1.0:
+            raise ValueError("GeometricTeacher: min_visible=%r outside (0, 1]" % (min_visible,))
+        self.min_visible = float(min_visible)
+        self.geometric_view = GeometricView(geometric_view)
+        self._drawn = None                  # (key, record): the labels and the view of one step share one draw
+
+    def geometry(self, target_input):
+        """The GeometricViewParams of step n = teacher_updates for this batch: a function of (cfg.seed, n, the shape),
+        drawn once per step."""
+        import numpy as np
+        B, _, H, W = target_input.shape
+        key = (int(self.cfg.seed), self.teacher_updates, B, H, W)
+        if self._drawn is None or self._drawn[0] != key:
+            self._drawn = (key, self.geometric_view.sample(B, H, W, np.random.default_rng([key[0], 0x47454F, key[1]])))
+        return self._drawn[1]
+
+    def student_view(self, target_input):
+        from datasets.geometric_view import warp_batch
+        params = self.geometry(target_input)
+        inverse = params.mirrored(target_input.shape[3])[1] if self.mirror_student else params.inverse
+        return self.strengthen(warp_batch(target_input, inverse))
+
+    def view_labels(self, labels, target_input, map_h, map_w, rotated):
+        from hip_runtime import ops
+        down_ratio = target_input.shape[3] / float(map_w)
+        return ops.transform_labels(labels, self.geometry(target_input).forward_map(down_ratio), map_h, map_w,
+                                    rotated=rotated, min_size=self.min_size, min_visible=self.min_visible)
 
 
 class DenseTeacher(WeakStrongTeacher):

@@ -1039,6 +1039,48 @@ int cnuda_strong_view(const float* x, float* y, const float* mean, const float* 
                       unsigned long long seed, const float* pivot, int B, int H, int W, cnuda_stream_t stream);
 
 /* -------------------------------------------------------------------------
+ * Geometric view (datasets/geometric_view.py, uda.GeometricTeacher; csrc/geomview.hip; DESIGN.md, "Geometric view").  No
+ * reference counterpart.  A similarity transform of a normalised batch and of the teacher's pseudo-labels.  Coordinates
+ * are those of datasets/augment.py: pixel (row i, column j) has its centre at (j + 0.5, i + 0.5); a matrix is the
+ * row-major 2 x 3 part (m0 .. m5) of a 3 x 3 float64 matrix acting on columns (x, y, 1).  No atomics, caller's stream.
+ * ---------------------------------------------------------------------- */
+/* y [B,C,H,W] f32 = the bilinear resampling of x [B,C,H,W] f32 (contiguous, not overlapping; x is never written) under
+ * inverse [B,6] float64 on the DEVICE: output pixel centres -> source positions.  Per output pixel (i, j) of image b:
+ *   dx = (double)j + 0.5, dy = (double)i + 0.5                                   (doubles, one rounding per operation)
+ *   u = ((m0 dx + m1 dy) + m2) - 0.5,   v = ((m3 dx + m4 dy) + m5) - 0.5
+ *   x0 = floor(u), y0 = floor(v),   fx = (float)(u - x0), fy = (float)(v - y0)
+ *   a, b, c, d = x[y0, x0], x[y0, x0 + 1], x[y0 + 1, x0], x[y0 + 1, x0 + 1]; a tap outside the image has the value `fill`
+ *   per channel, in float32:  top = a + fx (b - a),  bot = c + fx (d - c),  y = top + fy (bot - top)
+ * Every step is one IEEE operation, never contracted: numpy's arithmetic bit for bit (tests/geometric_view_oracle.py).
+ * Weights of exactly 0 (a mirror, a half turn, a shift by whole pixels, a quarter turn of a square image) reproduce the
+ * tap a for finite data (a = -0 comes out as +0).  An image whose six entries are exactly (1, 0, 0, 0, 1, 0) is copied
+ * and keeps every bit.  One launch; H W + W + 1 < 2^31. */
+int cnuda_warp_bilinear(const float* x, float* y, const double* inverse, float fill, int B, int C, int H, int W,
+                        cnuda_stream_t stream);
+/* The pseudo-labels of cnuda_pseudo_labels under the view: geometry_in [B,K,4] float64 (x1, y1, x2, y2) or, rotated,
+ * [B,K,4,2] float64 corners; classes_in [B,K] int32; counts_in [B] int32 (clamped to 0..K); forward [B,6] float64 on
+ * the DEVICE, the view's matrix at output-map resolution (map cells -> map cells).  The outputs have the inputs' layouts
+ * and are other buffers; the inputs are not written.  Per row below its image's count, in float64, with
+ * p' = ((m0 p.x + m1 p.y) + m2, (m3 p.x + m4 p.y) + m5):
+ *   rotated       the four corners mapped point by point (the label, in their order); extent = |p1' - p0'|, |p2' - p1'|;
+ *                 area and visible = area(quad clipped by [0, map_w] x [0, map_h]) / area(quad) by steps 1 to 4 of the
+ *                 rotated IoU above with the quad as subject and the map's rectangle as clipper (csrc/polyiou.cuh:
+ *                 the same routine), visible = i2 / a2;
+ *   axis-aligned  the corners (x1, y1), (x2, y1), (x2, y2), (x1, y2) mapped; the label is their bounding box (min and max
+ *                 per axis); extent = its width w and height h, area = w h,
+ *                 visible = max(min(x2, map_w) - max(x1, 0), 0) max(min(y2, map_h) - max(y1, 0), 0) / area.
+ * A row survives iff both extents >= min_size, its area is positive and finite (every mapped coordinate finite) and
+ * visible >= min_visible.  An image whose six entries are exactly (1, 0, 0, 0, 1, 0) keeps every row as it is.
+ * Survivors are compacted to the front in input order, unclipped; the other rows of every output are zero.
+ *   counts_out [B] int32; kept = float32(double(sum counts_out) / B);
+ *   dropped = float32(double(sum counts_in - sum counts_out) / B).
+ * Two launches: one workgroup per image (a ballot and a prefix count place the survivors), then the two means. */
+int cnuda_labels_transform(const double* geometry_in, const int* classes_in, const int* counts_in, const double* forward,
+                           double* geometry_out, int* classes_out, int* counts_out, float* kept, float* dropped, int B,
+                           int K, int rotated, int map_h, int map_w, double min_size, double min_visible,
+                           cnuda_stream_t stream);
+
+/* -------------------------------------------------------------------------
  * Dense teacher (uda.DenseTeacher; csrc/dense.hip; DESIGN.md, "Dense teacher").  No reference counterpart: Dense
  * Teacher (Zhou et al., ECCV 2022) on CenterNet's heads.  All maps are contiguous fp32; teacher_hm, hm [B,C,H,W] are
  * LOGITS, teacher_wh, wh [B,2,H,W].  With HW = H W, the score s[b,p] = max_c teacher_hm[b,c,p] (NaN if any channel is),
