@@ -121,6 +121,11 @@ __device__ __forceinline__ int wave_sum(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 // Block-wide sum for blockDim.x a multiple of 64 and <= 1024; result valid in
 // every thread.  `red` must hold >= 16 elements of T.
@@ -134,6 +139,15 @@ __device__ __forceinline__ T block_sum(T v, T* red) {
     T r = (lane < nw) ? red[lane] : T(0);
     r = wave_sum(r);
     return r;
+}
+
+// Orders ONE wave's LDS writes before its later LDS reads (other lanes' entries included) and the reverse, where the
+// waves of a workgroup run different trip counts and __syncthreads() cannot be used.  A wave's LDS operations complete in
+// order, so this costs no instruction: it keeps the compiler from moving them across it.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 }  // namespace cnuda

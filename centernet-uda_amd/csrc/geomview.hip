@@ -12,6 +12,9 @@
 //                             fraction from the exact convex clip of polyiou.cuh against the map's rectangle, survivors
 //                             compacted in input order by a ballot and a prefix count;
 //   labels_totals_kernel      the two means over the batch (`kept`, `dropped`) from the integer counts.
+//   labels_transform_kps_kernel, labels_totals_kps_kernel
+//                             the same two with the rows' joints in tow (uda.KeypointTeacher; DESIGN.md, "Keypoint
+//                             teacher"): mapped by the same matrix, visible while inside the map, and counted.
 //
 // No atomics: every result is the same from run to run.  The float32 arithmetic of the warp is one IEEE operation per step
 // in the order of include/centernet_uda_hip.h (-ffp-contract=off): numpy's float32 bit for bit (tests/
@@ -109,10 +112,24 @@ __device__ __forceinline__ bool is_finite(double v) { return v - v == 0.0; }
 // geometry_in / geometry_out [B, K, gcol] float64 (gcol 8: four (x, y) corners; 4: x1, y1, x2, y2); forward [B, 6] float64.
 // One wave per image: rows in chunks of 64, a ballot of the survivors, each survivor's place from the count of survivors
 // below its lane -- the input order, whatever the scheduling.
-__global__ __launch_bounds__(64) void labels_transform_kernel(
+//
+// kKps (cnuda_labels_transform_kps): the joints of a chunk's survivors follow their rows.  The chunk's 64 row -> slot
+// entries (-1: dropped) go to LDS, then the whole wave walks the chunk's (row, joint) pairs in memory order -- lane t takes
+// pair t, t + 64, ... -- so that a row's 2 J values never sit in a lane's registers and loads and stores are contiguous.
+struct ViewJoints {
+    const double* keypoints_in;      // [B, K, J, 2]
+    const int* visibility_in;        // [B, K, J]
+    double* keypoints_out;
+    int* visibility_out;
+    int J;
+};
+
+template <bool kKps>
+__device__ __forceinline__ void labels_transform_body(
     const double* __restrict__ geometry_in, const int* __restrict__ classes_in, const int* __restrict__ counts_in,
     const double* __restrict__ forward, double* __restrict__ geometry_out, int* __restrict__ classes_out,
-    int* __restrict__ counts_out, int K, int rotated, double map_w, double map_h, double min_size, double min_visible) {
+    int* __restrict__ counts_out, int K, int rotated, double map_w, double map_h, double min_size, double min_visible,
+    ViewJoints jt) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int gcol = rotated ? 8 : 4;
     const double* m = forward + 6 * (size_t)b;
@@ -184,6 +201,33 @@ __global__ __launch_bounds__(64) void labels_transform_kernel(
             double* o = geometry_out + row * gcol;
             for (int q = 0; q < gcol; ++q) o[q] = g[q];
         }
+        if constexpr (kKps) {
+            __shared__ int slot[64];
+            slot[lane] = keep ? base + __popcll(mask & ((1ull << lane) - 1ull)) : -1;
+            wave_lds_sync();
+            const int J = jt.J, n = min(64, count - k0);
+            // pair t = r J + j without a division per step: (r, j) advances by 64 = qstep J + jstep
+            const int qstep = 64 / J, jstep = 64 % J;
+            for (int r = lane / J, j = lane % J; r < n;) {
+                const int at = slot[r];
+                if (at >= 0) {
+                    const size_t i = ((size_t)b * K + (k0 + r)) * J + j, o = ((size_t)b * K + at) * J + j;
+                    double x = jt.keypoints_in[2 * i], y = jt.keypoints_in[2 * i + 1];
+                    int v = jt.visibility_in[i];
+                    if (!identity) {
+                        const double qx = (m0 * x + m1 * y) + m2, qy = (m3 * x + m4 * y) + m5;
+                        const bool fin = is_finite(qx) && is_finite(qy);
+                        v = (v == 2 && fin && qx >= 0.0 && qx < map_w && qy >= 0.0 && qy < map_h) ? 2 : 0;
+                        x = fin ? qx : 0.0, y = fin ? qy : 0.0;
+                    }
+                    jt.keypoints_out[2 * o] = x, jt.keypoints_out[2 * o + 1] = y;
+                    jt.visibility_out[o] = v;
+                }
+                r += qstep, j += jstep;
+                if (j >= J) j -= J, ++r;
+            }
+            wave_lds_sync();                                      // the next chunk rewrites the slots
+        }
         base += __popcll(mask);
     }
     // (rows below `base` were each written by exactly one survivor; the rest of every output is zero)
@@ -193,7 +237,31 @@ __global__ __launch_bounds__(64) void labels_transform_kernel(
         double* o = geometry_out + row * gcol;
         for (int q = 0; q < gcol; ++q) o[q] = 0.0;
     }
+    if constexpr (kKps) {
+        const size_t end = ((size_t)b * K + K) * jt.J;
+        for (size_t o = ((size_t)b * K + base) * jt.J + lane; o < end; o += 64) {
+            jt.keypoints_out[2 * o] = 0.0, jt.keypoints_out[2 * o + 1] = 0.0;
+            jt.visibility_out[o] = 0;
+        }
+    }
     if (lane == 0) counts_out[b] = base;
+}
+
+__global__ __launch_bounds__(64) void labels_transform_kernel(
+    const double* __restrict__ geometry_in, const int* __restrict__ classes_in, const int* __restrict__ counts_in,
+    const double* __restrict__ forward, double* __restrict__ geometry_out, int* __restrict__ classes_out,
+    int* __restrict__ counts_out, int K, int rotated, double map_w, double map_h, double min_size, double min_visible) {
+    labels_transform_body<false>(geometry_in, classes_in, counts_in, forward, geometry_out, classes_out, counts_out, K,
+                                 rotated, map_w, map_h, min_size, min_visible, ViewJoints{});
+}
+
+__global__ __launch_bounds__(64) void labels_transform_kps_kernel(
+    const double* __restrict__ geometry_in, const int* __restrict__ classes_in, const int* __restrict__ counts_in,
+    const double* __restrict__ forward, double* __restrict__ geometry_out, int* __restrict__ classes_out,
+    int* __restrict__ counts_out, int K, int rotated, double map_w, double map_h, double min_size, double min_visible,
+    ViewJoints jt) {
+    labels_transform_body<true>(geometry_in, classes_in, counts_in, forward, geometry_out, classes_out, counts_out, K,
+                                rotated, map_w, map_h, min_size, min_visible, jt);
 }
 
 // kept = float32(double(sum counts_out) / B); dropped = float32(double(sum min(max(counts_in, 0), K) - sum counts_out) / B)
@@ -210,6 +278,32 @@ __global__ __launch_bounds__(64) void labels_totals_kernel(const int* __restrict
     if (threadIdx.x == 0) {
         *kept = (float)((double)after / (double)B);
         *dropped = (float)((double)(before - after) / (double)B);
+    }
+}
+
+// labels_totals_kernel's two means, and joints = float32(double(number of v = 2 among the surviving rows) / B): one
+// workgroup, the rows below each image's count read in memory order, integer sums.
+constexpr int kJointsThreads = 256;
+
+__global__ __launch_bounds__(kJointsThreads) void labels_totals_kps_kernel(
+    const int* __restrict__ counts_in, const int* __restrict__ counts_out, const int* __restrict__ visibility_out,
+    float* __restrict__ kept, float* __restrict__ dropped, float* __restrict__ joints, int B, int K, int J) {
+    __shared__ long long red[16];
+    long long before = 0, after = 0, visible = 0;
+    for (int b = threadIdx.x; b < B; b += kJointsThreads) {
+        before += min(max(counts_in[b], 0), K);
+        after += counts_out[b];
+    }
+    for (int b = 0; b < B; ++b) {
+        const int* v = visibility_out + (size_t)b * K * J;
+        const size_t n = (size_t)counts_out[b] * J;
+        for (size_t i = threadIdx.x; i < n; i += kJointsThreads) visible += v[i] == 2;
+    }
+    before = block_sum(before, red), after = block_sum(after, red), visible = block_sum(visible, red);
+    if (threadIdx.x == 0) {
+        *kept = (float)((double)after / (double)B);
+        *dropped = (float)((double)(before - after) / (double)B);
+        *joints = (float)((double)visible / (double)B);
     }
 }
 
@@ -256,4 +350,35 @@ extern "C" int cnuda_labels_transform(const double* geometry_in, const int* clas
                  min_visible);
     CNUDA_LAUNCH(labels_totals_kernel, dim3(1), dim3(64), 0, st, counts_in, counts_out, kept, dropped, B, K);
     return check_launch("cnuda_labels_transform");
+}
+
+extern "C" int cnuda_labels_transform_kps(const double* geometry_in, const int* classes_in, const int* counts_in,
+                                          const double* keypoints_in, const int* visibility_in, const double* forward,
+                                          double* geometry_out, int* classes_out, int* counts_out, double* keypoints_out,
+                                          int* visibility_out, float* kept, float* dropped, float* joints, int B, int K,
+                                          int J, int rotated, int map_h, int map_w, double min_size, double min_visible,
+                                          cnuda_stream_t stream) {
+    CNUDA_REQUIRE(geometry_in && classes_in && counts_in && keypoints_in && visibility_in && forward && geometry_out
+                      && classes_out && counts_out && keypoints_out && visibility_out && kept && dropped && joints,
+                  "cnuda_labels_transform_kps: null pointer");
+    CNUDA_REQUIRE(B > 0 && K > 0 && J > 0, "cnuda_labels_transform_kps: bad sizes (B=%d, K=%d, J=%d)", B, K, J);
+    CNUDA_REQUIRE(map_h > 0 && map_w > 0, "cnuda_labels_transform_kps: bad map (map_h=%d, map_w=%d)", map_h, map_w);
+    CNUDA_REQUIRE(min_size == min_size && min_visible == min_visible, "cnuda_labels_transform_kps: a threshold is NaN");
+    CNUDA_REQUIRE((((uintptr_t)geometry_in | (uintptr_t)geometry_out | (uintptr_t)forward | (uintptr_t)keypoints_in
+                    | (uintptr_t)keypoints_out) & 7) == 0
+                      && (((uintptr_t)classes_in | (uintptr_t)classes_out | (uintptr_t)counts_in | (uintptr_t)counts_out
+                           | (uintptr_t)visibility_in | (uintptr_t)visibility_out | (uintptr_t)kept | (uintptr_t)dropped
+                           | (uintptr_t)joints) & 3) == 0,
+                  "cnuda_labels_transform_kps: arrays must be aligned to their element size");
+    CNUDA_REQUIRE(geometry_in != geometry_out && classes_in != classes_out && counts_in != counts_out
+                      && keypoints_in != keypoints_out && visibility_in != visibility_out,
+                  "cnuda_labels_transform_kps: the outputs must not be the inputs");
+    hipStream_t st = (hipStream_t)stream;
+    const ViewJoints jt{keypoints_in, visibility_in, keypoints_out, visibility_out, J};
+    CNUDA_LAUNCH(labels_transform_kps_kernel, dim3((unsigned)B), dim3(64), 0, st, geometry_in, classes_in, counts_in,
+                 forward, geometry_out, classes_out, counts_out, K, rotated ? 1 : 0, (double)map_w, (double)map_h, min_size,
+                 min_visible, jt);
+    CNUDA_LAUNCH(labels_totals_kps_kernel, dim3(1), dim3(kJointsThreads), 0, st, counts_in, counts_out, visibility_out, kept,
+                 dropped, joints, B, K, J);
+    return check_launch("cnuda_labels_transform_kps");
 }

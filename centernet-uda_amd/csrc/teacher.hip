@@ -7,6 +7,7 @@
 //   pseudo-labels   cnuda_pseudo_labels filters the teacher's decoded detection table (class, per-class score
 //                   threshold, finite geometry, minimum extent), compacts the survivors to the front in their input
 //                   order, optionally mirrors the geometry, and leaves what datasets.targets.encode_targets takes.
+//                   cnuda_pseudo_labels_kps (uda.KeypointTeacher) is the same body with the rows' decoded joints in tow.
 //
 // Both are element-wise or tiny.  The EMA is two rounded float32 products and one rounded sum (spelled with the
 // never-contracted intrinsics, on top of the build's -ffp-contract=off); the filter's order is decided by wave ballots
@@ -104,11 +105,26 @@ __global__ __launch_bounds__(kEmaThreads) void ema_update_kernel(const EmaSegmen
 // survivor's place from the count of survivors below its lane -- the input order, whatever the scheduling.
 constexpr int kPseudoMaxThreads = 1024;
 
-__global__ __launch_bounds__(kPseudoMaxThreads) void pseudo_labels_kernel(
+// What the keypoint form (cnuda_pseudo_labels_kps) carries beside the boxes; the box form passes an empty record.
+struct PseudoJoints {
+    const float* kps;         // [B, K, J, 2]
+    const int* perm;          // [J] or null
+    double* keypoints;        // [B, K, J, 2]
+    int* visibility;          // [B, K, J]
+    float* joints;
+    int J, map_height;
+};
+
+// kKps: the joints of a chunk's survivors follow their rows.  The chunk's 64 row -> slot entries (-1: dropped) go to this
+// wave's part of LDS, then the whole wave walks the chunk's (row, joint) pairs in memory order -- lane t takes pair t,
+// t + 64, ... -- so that a row's 2 J values never sit in a lane's registers and loads and stores are contiguous.
+template <bool kKps>
+__device__ __forceinline__ void pseudo_labels_body(
     const float* __restrict__ dets, const float* __restrict__ thresholds, double* __restrict__ geometry,
     int* __restrict__ classes, int* __restrict__ counts, float* __restrict__ kept, int B, int K, int C, int rotated,
-    int mirror, int map_width, float min_size) {
+    int mirror, int map_width, float min_size, PseudoJoints jt) {
     __shared__ int red[16];
+    long long visible = 0;                            // this lane's joints with v = 2 (kKps)
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int ncol = rotated ? 7 : 6, gcol = rotated ? 8 : 4;
     const double Wd = (double)map_width, smin = (double)min_size;
@@ -162,6 +178,40 @@ __global__ __launch_bounds__(kPseudoMaxThreads) void pseudo_labels_kernel(
                 double* o = geometry + row * gcol;
                 for (int q = 0; q < gcol; ++q) o[q] = g[q];
             }
+            if constexpr (kKps) {
+                __shared__ int slots[kPseudoMaxThreads];
+                int* slot = slots + 64 * wid;
+                slot[lane] = keep ? base + __popcll(mask & ((1ull << lane) - 1ull)) : -1;
+                wave_lds_sync();
+                const int J = jt.J, n = min(64, K - k0);
+                const double Hd = (double)jt.map_height;
+                // pair t = r J + j without a division per step: (r, j) advances by 64 = qstep J + jstep
+                const int qstep = 64 / J, jstep = 64 % J;
+                for (int r = lane / J, j = lane % J; r < n;) {
+                    const int at = slot[r];
+                    if (at >= 0) {
+                        const int p = jt.perm ? jt.perm[j] : j;
+                        float fx = NAN, fy = NAN;             // (an entry of perm outside [0, J) reads nothing)
+                        if ((unsigned)p < (unsigned)J) {
+                            const float* src = jt.kps + (((size_t)b * K + (k0 + r)) * J + p) * 2;
+                            fx = src[0], fy = src[1];
+                        }
+                        double x = 0.0, y = 0.0;
+                        int v = 0;
+                        if (isfinite(fx) && isfinite(fy)) {
+                            x = mirror ? Wd - (double)fx : (double)fx, y = (double)fy;
+                            v = (x >= 0.0 && x < Wd && y >= 0.0 && y < Hd) ? 2 : 0;
+                        }
+                        const size_t o = ((size_t)b * K + at) * J + j;
+                        jt.keypoints[2 * o] = x, jt.keypoints[2 * o + 1] = y;
+                        jt.visibility[o] = v;
+                        visible += v == 2;
+                    }
+                    r += qstep, j += jstep;
+                    if (j >= J) j -= J, ++r;
+                }
+                wave_lds_sync();                              // the next chunk rewrites the slots
+            }
             base += __popcll(mask);
         }
         // (rows below `base` were each written by exactly one survivor; the rest of every output is zero)
@@ -171,11 +221,39 @@ __global__ __launch_bounds__(kPseudoMaxThreads) void pseudo_labels_kernel(
             double* o = geometry + row * gcol;
             for (int q = 0; q < gcol; ++q) o[q] = 0.0;
         }
+        if constexpr (kKps) {
+            const size_t end = ((size_t)b * K + K) * jt.J;
+            for (size_t o = ((size_t)b * K + base) * jt.J + lane; o < end; o += 64) {
+                jt.keypoints[2 * o] = 0.0, jt.keypoints[2 * o + 1] = 0.0;
+                jt.visibility[o] = 0;
+            }
+        }
         if (lane == 0) counts[b] = base;
         total += base;
     }
     total = block_sum(lane == 0 ? total : 0, red);
     if (threadIdx.x == 0) *kept = (float)((double)total / (double)B);
+    if constexpr (kKps) {
+        __shared__ long long red_joints[16];
+        visible = block_sum(visible, red_joints);
+        if (threadIdx.x == 0) *jt.joints = (float)((double)visible / (double)B);
+    }
+}
+
+__global__ __launch_bounds__(kPseudoMaxThreads) void pseudo_labels_kernel(
+    const float* __restrict__ dets, const float* __restrict__ thresholds, double* __restrict__ geometry,
+    int* __restrict__ classes, int* __restrict__ counts, float* __restrict__ kept, int B, int K, int C, int rotated,
+    int mirror, int map_width, float min_size) {
+    pseudo_labels_body<false>(dets, thresholds, geometry, classes, counts, kept, B, K, C, rotated, mirror, map_width,
+                              min_size, PseudoJoints{});
+}
+
+__global__ __launch_bounds__(kPseudoMaxThreads) void pseudo_labels_kps_kernel(
+    const float* __restrict__ dets, const float* __restrict__ thresholds, double* __restrict__ geometry,
+    int* __restrict__ classes, int* __restrict__ counts, float* __restrict__ kept, int B, int K, int C, int rotated,
+    int mirror, int map_width, float min_size, PseudoJoints jt) {
+    pseudo_labels_body<true>(dets, thresholds, geometry, classes, counts, kept, B, K, C, rotated, mirror, map_width,
+                             min_size, jt);
 }
 
 }  // namespace
@@ -208,4 +286,25 @@ extern "C" int cnuda_pseudo_labels(const float* dets, const float* thresholds, d
     CNUDA_LAUNCH(pseudo_labels_kernel, dim3(1), dim3(64 * waves), 0, (hipStream_t)stream, dets, thresholds, geometry,
                  classes, counts, kept, B, K, C, rotated ? 1 : 0, mirror ? 1 : 0, map_width, min_size);
     return check_launch("cnuda_pseudo_labels");
+}
+
+extern "C" int cnuda_pseudo_labels_kps(const float* dets, const float* kps, const float* thresholds, const int* perm,
+                                       double* geometry, int* classes, int* counts, float* kept, double* keypoints,
+                                       int* visibility, float* joints, int B, int K, int C, int J, int rotated, int mirror,
+                                       int map_height, int map_width, float min_size, cnuda_stream_t stream) {
+    CNUDA_REQUIRE(dets && kps && thresholds && geometry && classes && counts && kept && keypoints && visibility && joints,
+                  "cnuda_pseudo_labels_kps: null pointer");
+    CNUDA_REQUIRE(B > 0 && K > 0 && C > 0 && J > 0, "cnuda_pseudo_labels_kps: bad sizes (B=%d, K=%d, C=%d, J=%d)", B, K,
+                  C, J);
+    CNUDA_REQUIRE(map_height > 0 && map_width > 0, "cnuda_pseudo_labels_kps: bad map (map_height=%d, map_width=%d)",
+                  map_height, map_width);
+    CNUDA_REQUIRE(min_size == min_size, "cnuda_pseudo_labels_kps: min_size is NaN");
+    CNUDA_REQUIRE(((uintptr_t)keypoints & 7) == 0
+                      && (((uintptr_t)kps | (uintptr_t)perm | (uintptr_t)visibility | (uintptr_t)joints) & 3) == 0,
+                  "cnuda_pseudo_labels_kps: arrays must be aligned to their element size");
+    const int waves = B < kPseudoMaxThreads / 64 ? B : kPseudoMaxThreads / 64;
+    const PseudoJoints jt{kps, perm, keypoints, visibility, joints, J, map_height};
+    CNUDA_LAUNCH(pseudo_labels_kps_kernel, dim3(1), dim3(64 * waves), 0, (hipStream_t)stream, dets, thresholds, geometry,
+                 classes, counts, kept, B, K, C, rotated ? 1 : 0, mirror ? 1 : 0, map_width, min_size, jt);
+    return check_launch("cnuda_pseudo_labels_kps");
 }

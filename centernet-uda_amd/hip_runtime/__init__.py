@@ -196,11 +196,13 @@ class _Sig:
     cnuda_pack_refresh_ranges = (_I, [_P, _P, _I, ctypes.c_ulonglong, ctypes.c_ulonglong, _P, ctypes.c_size_t, _P])
     cnuda_ema_update = (_I, [_P, _I, ctypes.c_uint, _F, _F, _P])
     cnuda_pseudo_labels = (_I, [_P] * 6 + [_I] * 6 + [_F, _P])
-    cnuda_strong_view_pivot = (_I, [_P] * 5 + [_I] * 3 + [_P])
+    cnuda_pseudo_labels_kps = (_I, [_P] * 11 + [_I] * 8 + [_F, _P])
+    cnuda_strong_view_pivot =(_I, [_P] * 5 + [_I] * 3 + [_P])
     cnuda_strong_view = (_I, [_P] * 7 + [_I] + [_P] * 2 + [ctypes.c_ulonglong, _P] + [_I] * 3 + [_P])
     cnuda_warp_bilinear = (_I, [_P] * 3 + [_F] + [_I] * 4 + [_P])
     cnuda_labels_transform = (_I, [_P] * 9 + [_I] * 5 + [_D, _D, _P])
-    cnuda_dense_select_workspace_bytes = (c_size_t, [_I, _LL])
+    cnuda_labels_transform_kps = (_I, [_P] * 14 + [_I] * 6 + [_D, _D, _P])
+    cnuda_dense_select_workspace_bytes =(c_size_t, [_I, _LL])
     cnuda_dense_select = (_I, [_P, _D, _P, _P, _I, _I, _LL] + _WS)
     cnuda_dense_teacher_forward = (_I, [_P] * 7 + [_I] * 5 + [_F, _F] + _WS)
     cnuda_dense_teacher_backward = (_I, [_P] * 9 + [_I] * 5 + [_F, _F, _P])

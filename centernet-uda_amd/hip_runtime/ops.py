@@ -1557,13 +1557,59 @@ class EmaPlan:
               'ema_update')
 
 
-def pseudo_labels(dets, thresholds, map_width, *, rotated=False, mirror=False, min_size=0.0):
+_CHECKED_PERMS = {}           # id(tensor) -> (weak reference, the tensor's version when it was validated)
+
+
+def _flip_perm(flip_perm, J, dev):
+    """`flip_perm` (None, an int32 [J] device tensor or a sequence) -> None or a validated int32 [J] tensor on `dev`.  A
+    device tensor is read back the first time it is seen and again only after it was written."""
+    import weakref
+    import numpy as np
+    if flip_perm is None:
+        return None
+    if isinstance(flip_perm, torch.Tensor):
+        if flip_perm.dtype != torch.int32 or tuple(flip_perm.shape) != (J,) or flip_perm.device != dev:
+            raise RuntimeError("pseudo_labels: flip_perm must be an int32 [%d] tensor on dets' device, got %s %s"
+                               % (J, flip_perm.dtype, tuple(flip_perm.shape)))
+        seen = _CHECKED_PERMS.get(id(flip_perm))
+        if seen is not None and seen[0]() is flip_perm and seen[1] == flip_perm._version:
+            return flip_perm.contiguous()
+        host = flip_perm.detach().cpu().numpy()
+    else:
+        host = np.asarray(flip_perm)
+        if host.shape != (J,) or host.dtype.kind not in 'iu':
+            raise RuntimeError("pseudo_labels: flip_perm must list %d joint indices, got %r" % (J, flip_perm))
+    if sorted(int(v) for v in host) != list(range(J)):
+        raise RuntimeError("pseudo_labels: flip_perm %r is not a permutation of 0..%d" % (host.tolist(), J - 1))
+    if isinstance(flip_perm, torch.Tensor):
+        key = id(flip_perm)
+        _CHECKED_PERMS[key] = (weakref.ref(flip_perm, lambda _, key=key: _CHECKED_PERMS.pop(key, None)),
+                               flip_perm._version)
+        return flip_perm.contiguous()
+    return torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(dev)
+
+
+def pseudo_labels(dets, thresholds, map_width, *, rotated=False, mirror=False, min_size=0.0, kps=None, flip_perm=None,
+                  map_height=None):
     """A decoded detection table -> the inputs of datasets.targets.encode_targets at output-map resolution
     (cnuda_pseudo_labels; include/centernet_uda_hip.h).  dets [B, K, 6] (or [B, K, 7] with rotated) float32 as
     decode_detection leaves it, thresholds [C] float32 on the device.  -> {'classes' [B, K] int32, 'counts' [B] int32,
     'kept' 0-dim float32 (the mean of counts), and 'boxes' [B, K, 4] float64 or, rotated, 'corners' [B, K, 4, 2]
-    float64}: the surviving rows first, in input order, zeros behind them.  One launch, nothing read back."""
-    require_gpu(dets, thresholds)
+    float64}: the surviving rows first, in input order, zeros behind them.  One launch, nothing read back.
+
+    With kps [B, K, J, 2] float32 (decode_detection's second result) and `map_height` the call goes through
+    cnuda_pseudo_labels_kps: the same rows survive -- the joints never decide it --, and the dict gains 'keypoints'
+    [B, K, J, 2] float64, 'visibility' [B, K, J] int32 (2: inside [0, map_width) x [0, map_height); else 0) and 'joints'
+    (0-dim float32: the mean number of visible joints per image).  flip_perm: an int32 [J] device tensor or a sequence,
+    a permutation of 0..J-1 (predict.flip_permutation): output joint j takes input joint flip_perm[j].  It is validated
+    on the host: a sequence on every call, a tensor when it is first seen and after it was written (one read-back)."""
+    if kps is None:
+        if flip_perm is not None or map_height is not None:
+            raise RuntimeError("pseudo_labels: flip_perm and map_height belong to kps, which is not given")
+    else:
+        if map_height is None or int(map_height) < 1:
+            raise RuntimeError("pseudo_labels: kps needs map_height >= 1, got %r" % (map_height,))
+    require_gpu(dets, thresholds, kps)
     ncol = 7 if rotated else 6
     if dets.dim() != 3 or dets.shape[2] != ncol or dets.numel() == 0:
         raise RuntimeError("pseudo_labels: dets must be a non-empty [B, K, %d], got %s" % (ncol, tuple(dets.shape)))
@@ -1580,6 +1626,23 @@ def pseudo_labels(dets, thresholds, map_width, *, rotated=False, mirror=False, m
            'counts': torch.empty((B,), dtype=torch.int32, device=dev),
            'kept': torch.empty((), dtype=torch.float32, device=dev),
            'corners' if rotated else 'boxes': geometry}
+    if kps is not None:
+        if kps.dim() != 4 or tuple(kps.shape[:2]) != (B, K) or kps.shape[2] < 1 or kps.shape[3] != 2 \
+                or kps.dtype != torch.float32 or kps.device != dev:
+            raise RuntimeError("pseudo_labels: kps must be a float32 [%d, %d, J, 2] on dets' device, got %s %s"
+                               % (B, K, kps.dtype, tuple(kps.shape)))
+        J = kps.shape[2]
+        kps, perm = kps.detach().contiguous(), _flip_perm(flip_perm, J, dev)
+        out['keypoints'] = torch.empty((B, K, J, 2), dtype=torch.float64, device=dev)
+        out['visibility'] = torch.empty((B, K, J), dtype=torch.int32, device=dev)
+        out['joints'] = torch.empty((), dtype=torch.float32, device=dev)
+        check(lib().cnuda_pseudo_labels_kps(ptr(dets), ptr(kps), ptr(thresholds), ptr(perm), ptr(geometry),
+                                            ptr(out['classes']), ptr(out['counts']), ptr(out['kept']),
+                                            ptr(out['keypoints']), ptr(out['visibility']), ptr(out['joints']), B, K,
+                                            thresholds.numel(), J, 1 if rotated else 0, 1 if mirror else 0,
+                                            int(map_height), int(map_width), float(min_size), stream()),
+              'pseudo_labels_kps')
+        return out
     check(lib().cnuda_pseudo_labels(ptr(dets), ptr(thresholds), ptr(geometry), ptr(out['classes']), ptr(out['counts']),
                                     ptr(out['kept']), B, K, thresholds.numel(), 1 if rotated else 0,
                                     1 if mirror else 0, int(map_width), float(min_size), stream()), 'pseudo_labels')
@@ -1595,13 +1658,19 @@ def transform_labels(labels, forward_map, map_h, map_w, *, rotated=False, min_si
     [0, map_w] x [0, map_h] (an exact convex clip in float64); an image with the identity matrix keeps every row.
     -> a new dict with the same keys, dtypes and layout -- survivors first, in input order, unclipped, zeros behind them;
     'counts' and 'kept' rewritten -- plus 'dropped' (0-dim float32: the mean number of rows removed per image).  The
-    input tensors are not written.  Two launches, no atomics, nothing read back."""
+    input tensors are not written.  Two launches, no atomics, nothing read back.
+
+    A dict that holds 'keypoints' [B, K, J, 2] float64 and 'visibility' [B, K, J] int32 (pseudo_labels(kps=...)) goes
+    through cnuda_labels_transform_kps: the same rows survive, their joints are mapped by the same matrix and stay
+    visible (2) only where they were and the mapped point lies inside [0, map_w) x [0, map_h); 'joints' is recomputed."""
     import numpy as np
     key = 'corners' if rotated else 'boxes'
     tail = (4, 2) if rotated else (4,)
     if not isinstance(labels, dict) or any(k not in labels for k in (key, 'classes', 'counts')):
         raise RuntimeError("transform_labels: labels must be the dict of pseudo_labels(rotated=%s) with '%s', 'classes' "
                            "and 'counts'" % (bool(rotated), key))
+    if ('keypoints' in labels) != ('visibility' in labels):
+        raise RuntimeError("transform_labels: labels hold only one of 'keypoints' and 'visibility'")
     geometry, classes, counts = labels[key], labels['classes'], labels['counts']
     require_gpu(geometry, classes, counts)
     if geometry.dim() != 2 + len(tail) or tuple(geometry.shape[2:]) != tail or geometry.numel() == 0 \
@@ -1631,6 +1700,27 @@ def transform_labels(labels, forward_map, map_h, map_w, *, rotated=False, min_si
     out = {'classes': torch.empty_like(classes), 'counts': torch.empty_like(counts),
            'kept': torch.empty((), dtype=torch.float32, device=dev), key: torch.empty_like(geometry),
            'dropped': torch.empty((), dtype=torch.float32, device=dev)}
+    if 'keypoints' in labels:
+        keypoints, visibility = labels['keypoints'], labels['visibility']
+        require_gpu(keypoints, visibility)
+        if keypoints.dim() != 4 or tuple(keypoints.shape[:2]) != (B, K) or keypoints.shape[2] < 1 \
+                or keypoints.shape[3] != 2 or keypoints.dtype != torch.float64 or keypoints.device != dev:
+            raise RuntimeError("transform_labels: keypoints must be a float64 [%d, %d, J, 2], got %s %s"
+                               % (B, K, keypoints.dtype, tuple(keypoints.shape)))
+        J = keypoints.shape[2]
+        if tuple(visibility.shape) != (B, K, J) or visibility.dtype != torch.int32 or visibility.device != dev:
+            raise RuntimeError("transform_labels: visibility must be an int32 [%d, %d, %d], got %s %s"
+                               % (B, K, J, visibility.dtype, tuple(visibility.shape)))
+        keypoints, visibility = keypoints.contiguous(), visibility.contiguous()
+        out['keypoints'], out['visibility'] = torch.empty_like(keypoints), torch.empty_like(visibility)
+        out['joints'] = torch.empty((), dtype=torch.float32, device=dev)
+        check(lib().cnuda_labels_transform_kps(ptr(geometry), ptr(classes), ptr(counts), ptr(keypoints), ptr(visibility),
+                                               ptr(forward), ptr(out[key]), ptr(out['classes']), ptr(out['counts']),
+                                               ptr(out['keypoints']), ptr(out['visibility']), ptr(out['kept']),
+                                               ptr(out['dropped']), ptr(out['joints']), B, K, J, 1 if rotated else 0,
+                                               int(map_h), int(map_w), float(min_size), float(min_visible), stream()),
+              'labels_transform_kps')
+        return out
     check(lib().cnuda_labels_transform(ptr(geometry), ptr(classes), ptr(counts), ptr(forward), ptr(out[key]),
                                        ptr(out['classes']), ptr(out['counts']), ptr(out['kept']), ptr(out['dropped']),
                                        B, K, 1 if rotated else 0, int(map_h), int(map_w), float(min_size),

@@ -15,6 +15,7 @@ _PLUGINS = {
     'WeakStrongTeacher': 'uda.mean_teacher',
     'DenseTeacher': 'uda.mean_teacher',
     'GeometricTeacher': 'uda.mean_teacher',
+    'KeypointTeacher': 'uda.mean_teacher',
 }
 __all__ = sorted(_PLUGINS)
 

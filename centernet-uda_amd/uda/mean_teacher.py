@@ -18,6 +18,10 @@ DenseTeacher replaces 2 and the target term of 3: the teacher's heads stay dense
 encoding), hip_runtime.ops.dense_select picks the top `ratio` of every image's positions and ops.dense_teacher_loss
 regresses the student's `hm` and `wh` onto the teacher's there ("Dense teacher").
 
+KeypointTeacher extends 2 for a model with a keypoint head: the decoded joints travel with their boxes through
+pseudo_labels, the geometric view and encode_targets, and the detection loss adds its keypoint term on the target half
+(DESIGN.md, "Keypoint teacher").
+
 The teacher is a copy of the unwrapped backend made in `to()`.  It is not a submodule of the backend (the backend's
 state_dict, the optimizer and a data-parallel wrapper never see it); its trainable parameters are views of one flat
 float32 buffer laid out like the student's arena, so that they are ONE segment of the update against
@@ -156,24 +160,31 @@ class MeanTeacher(Model):
     # -- the step ----------------------------------------------------------------------
     def pseudo_batch(self, target_input):
         """The teacher's detections on `target_input` as a batch for the detection loss (+ 'kept')."""
-        from backends.decode import decode_detection
         from datasets.targets import encode_targets
         from hip_runtime import ops
         rotated = bool(self._model_params().rotated_boxes)
         with torch.no_grad():
             heads = self.teacher(target_input)
             hm = ops.sigmoid_clamp_(heads['hm'])
-            dets = decode_detection(hm, heads['wh'], heads['reg'], K=self.cfg.max_detections, rotated=rotated)
+            dets, joints = self.decode_teacher(hm, heads, rotated)
             H, W = hm.shape[2:]
             labels = ops.pseudo_labels(dets, self._thresholds, W, rotated=rotated, mirror=self.mirror_student,
-                                       min_size=self.min_size)
+                                       min_size=self.min_size, **joints)
             labels = self.view_labels(labels, target_input, H, W, rotated)
             batch = encode_targets(labels.get('boxes'), labels['classes'], labels['counts'], hm.shape[1], H, W,
-                                   corners=labels.get('corners'))
+                                   corners=labels.get('corners'), keypoints=labels.get('keypoints'),
+                                   visibility=labels.get('visibility'))
         batch['kept'] = labels['kept']
-        if 'dropped' in labels:
-            batch['dropped'] = labels['dropped']
+        for name in ('dropped', 'joints'):
+            if name in labels:
+                batch[name] = labels[name]
         return batch
+
+    def decode_teacher(self, hm, heads, rotated):
+        """-> (the teacher's decoded detection table, further keyword arguments of `ops.pseudo_labels`: none here;
+        KeypointTeacher: the decoded joints)."""
+        from backends.decode import decode_detection
+        return decode_detection(hm, heads['wh'], heads['reg'], K=self.cfg.max_detections, rotated=rotated), {}
 
     def view_labels(self, labels, target_input, map_h, map_w, rotated):
         """The teacher's pseudo-labels as the student's view shows them: here the labels themselves (`pseudo_labels`
@@ -211,6 +222,8 @@ class MeanTeacher(Model):
             stats['pseudo_boxes'] = pseudo['kept']
             if 'dropped' in pseudo:
                 stats['pseudo_dropped'] = pseudo['dropped']
+            if 'joints' in pseudo:
+                stats['pseudo_joints'] = pseudo['joints']
             return loss * self.pseudo_weight, stats
         return self.step_with_target_term(view, True, target_term)
 
@@ -320,6 +333,58 @@ class GeometricTeacher(WeakStrongTeacher):
         down_ratio = target_input.shape[3] / float(map_w)
         return ops.transform_labels(labels, self.geometry(target_input).forward_map(down_ratio), map_h, map_w,
                                     rotated=rotated, min_size=self.min_size, min_visible=self.min_visible)
+
+
+class KeypointTeacher(GeometricTeacher):
+    """GeometricTeacher for a model with a keypoint head ("Keypoint teacher"): the teacher's `kps` head is
+    decoded with its boxes, and every pseudo-label carries its J joints through the score filter and the mirror
+    (`ops.pseudo_labels(kps=...)`; with `mirror_student` the joints of `flip_pairs` -- [[left, right], ...], as
+    predict.py --flip-pairs -- change places), through the geometric view (`ops.transform_labels`) and into
+    `encode_targets(keypoints=, visibility=)`: the pseudo batch has `kps`, `gt_kps` and `kp_reg_mask`, and the detection
+    loss (which must have its keypoint term: `kp_weight`) adds that term on the target half; the student's `kps` head
+    records a tape there.  The teacher gives no confidence per joint: a joint is "visible" when it lies inside the
+    student's map, and the joints never decide whether a label survives.  Statistics: the parent's, with
+    `pseudo_kp_loss` among the `pseudo_` ones, plus `pseudo_joints` (visible joints per image).
+
+    With every `geometric_view` component null the view is WeakStrongTeacher's.  Rotated-box models are allowed.  Burn-in,
+    the EMA, checkpoints, evaluation and the two random streams are the parent's."""
+    target_grad_heads = ('hm', 'wh', 'reg', 'kps')
+
+    def __init__(self, pseudo_weight, flip_pairs=None, geometric_view=None, min_visible=0.5, strong_view=None,
+                 **mean_teacher_arguments):
+        super().__init__(pseudo_weight, geometric_view=geometric_view, min_visible=min_visible, strong_view=strong_view,
+                         **mean_teacher_arguments)
+        self.flip_pairs = None if flip_pairs is None else [tuple(pair) for pair in flip_pairs]
+        self._flip_perm = None              # (host int32 [J], its device copy once moved)
+
+    def init_done(self):
+        from predict import flip_permutation
+        params = self._model_params()
+        J = int(params.get('num_keypoints', 0) or 0)
+        if J <= 0:
+            raise ValueError("KeypointTeacher: model.backend.params.num_keypoints=%r: there is no keypoint head to "
+                             "teach; use uda.GeometricTeacher for this model" % (params.get('num_keypoints', 0),))
+        try:
+            self._flip_perm = (flip_permutation(self.flip_pairs, J), None)
+        except ValueError as err:
+            raise ValueError("KeypointTeacher: %s (num_keypoints=%d)" % (err, J)) from None
+        if not getattr(self.centernet_loss, 'with_keypoints', False):
+            raise ValueError("KeypointTeacher: the detection loss has no keypoint term: set "
+                             "model.backend.loss.params.kp_weight")
+        self._threshold_list()
+
+    def decode_teacher(self, hm, heads, rotated):
+        from backends.decode import decode_detection
+        dets, kps = decode_detection(hm, heads['wh'], heads['reg'], kps=heads['kps'], K=self.cfg.max_detections,
+                                     rotated=rotated)
+        joints = {'kps': kps, 'map_height': hm.shape[2]}
+        if self.mirror_student:
+            host, dev = self._flip_perm
+            if dev is None or dev.device != kps.device:
+                dev = torch.from_numpy(host).to(kps.device)
+                self._flip_perm = (host, dev)
+            joints['flip_perm'] = dev
+        return dets, joints
 
 
 class DenseTeacher(WeakStrongTeacher):

@@ -1005,6 +1005,21 @@ int cnuda_ema_update(const void* table, int segments, unsigned blocks, float dec
 int cnuda_pseudo_labels(const float* dets, const float* thresholds, double* geometry, int* classes, int* counts,
                         float* kept, int B, int K, int C, int rotated, int mirror, int map_width, float min_size,
                         cnuda_stream_t stream);
+/* cnuda_pseudo_labels with the detections' decoded keypoints (uda.KeypointTeacher; DESIGN.md, "Keypoint teacher"):
+ * kps [B,K,J,2] float32 (x, y) at map resolution, as cnuda_decode_keypoints leaves them; perm [J] int32 or null (the
+ * identity): the joint that takes joint j's place in a mirrored image.  Row survival is cnuda_pseudo_labels' rule -- the
+ * joints never decide it -- and geometry, classes, counts and kept are its results bit for bit.  In addition, for the
+ * survivor in slot s that was input row k, output joint j takes input joint p = perm[j]:
+ *   x' = mirror ? (double)map_width - (double)x : (double)x,  y' = (double)y          (the rule of the box edges)
+ *   v = 2 iff x and y are finite, 0 <= x' < map_width and 0 <= y' < map_height; else v = 0
+ *   keypoints [B,K,J,2] float64 = (x', y'), visibility [B,K,J] int32 = v; a joint that is not finite is (0, 0) with v = 0,
+ *   and so is one whose perm entry lies outside [0, J) (nothing is read for it).
+ * Rows behind the survivors are zero in every output.  joints: one float32 = float32(double(number of v = 2) / B), from
+ * integer counts.  One launch, one wave per image, no atomics: the same bits on every run.  Any J > 0. */
+int cnuda_pseudo_labels_kps(const float* dets, const float* kps, const float* thresholds, const int* perm,
+                            double* geometry, int* classes, int* counts, float* kept, double* keypoints, int* visibility,
+                            float* joints, int B, int K, int C, int J, int rotated, int mirror, int map_height,
+                            int map_width, float min_size, cnuda_stream_t stream);
 
 /* -------------------------------------------------------------------------
  * Strong view (datasets/strong_view.py, uda.WeakStrongTeacher; csrc/strongview.hip; DESIGN.md, "Strong view").  No
@@ -1079,6 +1094,21 @@ int cnuda_labels_transform(const double* geometry_in, const int* classes_in, con
                            double* geometry_out, int* classes_out, int* counts_out, float* kept, float* dropped, int B,
                            int K, int rotated, int map_h, int map_w, double min_size, double min_visible,
                            cnuda_stream_t stream);
+/* cnuda_labels_transform with the rows' joints (cnuda_pseudo_labels_kps' keypoints [B,K,J,2] float64 and visibility
+ * [B,K,J] int32): the same survival rule, compaction, kept and dropped -- the joints never decide a row's survival, and a
+ * dropped row's joints disappear with it.  Every joint of a surviving row, in float64:
+ *   p' = ((m0 x + m1 y) + m2, (m3 x + m4 y) + m5)
+ *   v' = 2 iff v == 2, p' is finite, 0 <= p'.x < map_w and 0 <= p'.y < map_h; else v' = 0;  a p' that is not finite is
+ *   written as (0, 0).
+ * An image whose six entries are exactly (1, 0, 0, 0, 1, 0) keeps its joints and v as they are.  Rows behind the
+ * survivors are zero.  joints = float32(double(number of v' = 2 in surviving rows) / B).  The outputs are other buffers than
+ * the inputs.  Two launches: one wave per image, then the three means from integer sums.  Any J > 0. */
+int cnuda_labels_transform_kps(const double* geometry_in, const int* classes_in, const int* counts_in,
+                               const double* keypoints_in, const int* visibility_in, const double* forward,
+                               double* geometry_out, int* classes_out, int* counts_out, double* keypoints_out,
+                               int* visibility_out, float* kept, float* dropped, float* joints, int B, int K, int J,
+                               int rotated, int map_h, int map_w, double min_size, double min_visible,
+                               cnuda_stream_t stream);
 
 /* -------------------------------------------------------------------------
  * Dense teacher (uda.DenseTeacher; csrc/dense.hip; DESIGN.md, "Dense teacher").  No reference counterpart: Dense
